@@ -23,7 +23,7 @@ together, every step one launch with the problem index in the grid; `--batch-mod
 thread pool of cip_conicip_problems instead); no data-path collective, one all-reduce of the
 counts (SUM) and of the wall time (MAX).  A step is then one pass over the whole batch and
 `value` = KKT solves (factorisations) of all ranks per second; total work is fixed as N grows
-(`"scaling": "strong"`).  `--workload c5` runs that workload on one GPU; the default N = 1 line
+(`"scaling": "strong"`).  `--workload c5` runs that workload on one GPU; the `--full` N = 1 line
 (the n = 8192 headline) carries the same figure as `c5_single_gpu`, and every N > 1 line carries its own
 `c5_single_gpu` (rank 0 alone on all 64 problems, timed before the sharded passes), `ranks_seen`, a `roofline` of the
 batch's trailing-update launches and a bounded `cpu_baseline`, so that a 1 -> N curve can be read off the N > 1 lines.
@@ -33,6 +33,14 @@ Inputs come from the portable SplitMix64 generator (cipkkt/workloads.py), genera
 Output: ONE JSON line on rank 0 with `roofline` (LDL' trailing-update kernel, fp64 MFMA,
 HIP-event timed per launch on the launch stream) and `cpu_baseline` (the oracle's
 reference-faithful kktsolver_qr restatement timed on the host cores).
+
+A plain run of the headline (`--gpus 1 --steps K --warmup W`) does what its figure needs: set-up, the convergence passes the
+step is taken from (`converge`), W warm-up steps, the K timed steps (`value`, `ms_per_step`, and the `roofline` of the
+trailing-update events inside them, its traffic replayed from the committed PMC passes), the line.  `--full` adds everything
+else of the report, each part still subject to its `--no-*` switch: the live PMC passes, the profiling-cost A/B, the factor /
+solve split with `roofline_solve`, `plugin_boundary` with its host loop, `secondary` (the 3x3 route, configs 3 and 4), the
+config-5 figures and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step handed its caller (c2: `lam`,
+`dz` and the packed scaling, float64) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -123,18 +131,22 @@ def cpu_baseline(Q_host, n, solves_per_factor, budget_s=100.0):
     probe = {}
     limiter = None
     try:
-        from threadpoolctl import threadpool_limits
+        from threadpoolctl import threadpool_info, threadpool_limits
     except Exception:
         threadpool_limits = None
     if threadpool_limits is not None:
         # OpenBLAS does not scale to every hardware thread of a 2-socket box: probe dgemm (the faithful leg is GEMM + QR) and
-        # potrf (the strong leg) at a few thread counts and run each leg at its fastest one.
+        # potrf (the strong leg) at a few thread counts and run each leg at its fastest one.  Never above the thread count the
+        # BLAS pools were loaded with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else every CPU): OpenBLAS sizes its per-thread
+        # buffers at load time, and scipy's crashes in potrf when raised beyond them.
+        start = [p["num_threads"] for p in threadpool_info() if p.get("user_api") == "blas" and p.get("num_threads")]
+        top = min([logical] + start)
         rngp = np.random.default_rng(0)
         npb = 4096 if n >= 4096 else max(256, n)
         Mp = rngp.standard_normal((npb, npb))
         Sp = np.asfortranarray(Mp @ Mp.T / npb + np.eye(npb))      # column-major, as LAPACK wants it (a C-ordered input is transposed first)
-        best_g, best_p = (1e30, cores), (1e30, cores)
-        for nt in sorted({c for c in (8, 16, 32, 64, 128, logical) if c <= logical}):
+        best_g, best_p = (1e30, top), (1e30, top)
+        for nt in sorted({c for c in (8, 16, 32, 64, 128, top) if c <= top}):
             with threadpool_limits(limits=nt):
                 Mp[:512] @ Mp                      # (thread pool warm-up)
                 dg = dp = 1e30
@@ -571,6 +583,17 @@ def c5_cpu_baseline(seed=4000, n=2048):
                 iters=sol.Iter, status=sol.status)
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64 host copy) per array the timed path handed its caller in its last step."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).astype(np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > 64 << 20:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the 64 MB the dump may take" % total)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def fixture_iters(key):
     """Iteration count of the ORACLE on the same inputs, from the committed full-size fixture
     (tests/golden/fullsize_trajectories.json, generated by tests/golden/make_fullsize_fixtures.py)."""
@@ -604,9 +627,16 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="c2: do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes before the GPU is "
                          "touched); replay the committed passes instead")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: the whole report besides the timed steps (live PMC passes, profiling-cost A/B, factor / solve split, "
+                         "plugin boundary, secondary configs, config-5 figures, CPU baselines; each subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: write what the last timed step computed (lam, dz, packed scaling; float64) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and (args.workload == "c5" or args.gpus > 1):
+        raise SystemExit("bench.py: --dump-outputs is written for the c2 workload (--gpus 1)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start one rank per GPU as a child process -- before anything here touches the GPU
@@ -617,9 +647,9 @@ def main():
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but the launcher started WORLD_SIZE=%d ranks" % (args.gpus, world))
     live_traffic = (None, "not requested", None)
-    if (world == 1 and args.gpus == 1 and (args.workload in (None, "c2")) and not args.no_live_pmc and not args.no_cpu_baseline
-            and not os.environ.get("CIP_BENCH_PMC_CHILD") and torch.cuda.device_count() > 0):
-        # (only in the full default run -- the A/B and profiling invocations pass --no-cpu-baseline.  The children are fresh
+    if (args.full and world == 1 and args.gpus == 1 and (args.workload in (None, "c2")) and not args.no_live_pmc
+            and not args.no_cpu_baseline and not os.environ.get("CIP_BENCH_PMC_CHILD") and torch.cuda.device_count() > 0):
+        # (only in the --full run -- the A/B and profiling invocations pass --no-cpu-baseline.  The children are fresh
         #  subprocesses started before this process makes its first HIP call that creates a context -- so far it has only
         #  counted devices -- and it never execs: each child opens the GPU for itself)
         live_traffic = live_pmc_traffic(args)
@@ -808,44 +838,51 @@ def main():
     prof = ks.profile_get()
     ks.profile_trailing(False)
     ks.check_factor()
-    # what the HIP events around every trailing-update launch cost the number above: the same K steps again without them
-    # (same session A/B; round-4 review)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    elapsed_noprof = time.perf_counter() - t0
-    ks.check_factor()
-
-    # separate factor / solve split (untimed region, for the report)
-    ks.set_timing(True)
-    ks.factor()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as its caller holds them: lam (cip_set_scaling_from_iterate_dev), dz (cip_solve4x4_dev)
+        # and the scaling the factorisation was built from (cip_get_scaling_packed)
+        dump_outputs(args.dump_outputs, {"lam": lam, "dz": dz, "scaling": ks.get_scaling_packed()})
     st = ks.stats()
-    ks.set_timing(False)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(5):
-        ks.solve4x4_dev(lam, rhs, dz)
-    torch.cuda.synchronize()
-    solve_ms = (time.perf_counter() - t1) / 5 * 1e3
+    elapsed_noprof = solve_ms = None
+    if args.full:
+        # what the HIP events around every trailing-update launch cost the number above: the same K steps again without them
+        # (same session A/B; round-4 review)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        elapsed_noprof = time.perf_counter() - t0
+        ks.check_factor()
+
+        # separate factor / solve split (untimed region, for the report)
+        ks.set_timing(True)
+        ks.factor()
+        st = ks.stats()
+        ks.set_timing(False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(5):
+            ks.solve4x4_dev(lam, rhs, dz)
+        torch.cuda.synchronize()
+        solve_ms = (time.perf_counter() - t1) / 5 * 1e3
 
     pb = None
-    if rank == 0 and not args.no_plugin_boundary and not os.environ.get("CIP_BENCH_PMC_CHILD"):
+    if args.full and rank == 0 and not args.no_plugin_boundary and not os.environ.get("CIP_BENCH_PMC_CHILD"):
         pb = plugin_boundary(ks, v_mid, s_mid, lam, spf)
     ks.close()
     c5_single = None
     c5_shards = None
-    if world == 1 and not args.no_c5 and n == 8192 and args.route == "schur":
+    if args.full and world == 1 and not args.no_c5 and n == 8192 and args.route == "schur":
         c5_single = config5(2, 1)                     # single-GPU config-5 figure, for cross-checking a SCALE run
         if rank == 0 and not os.environ.get("CIP_BENCH_PMC_CHILD") and args.batch_mode == "lockstep":
             try:
                 c5_shards = c5_shard_passes(device, args.in_flight, full=c5_single)
             except Exception as e:                   # a side figure never takes the bench line down
                 c5_shards = {"error": repr(e)}
-    Qh = Q.cpu().numpy() if (rank == 0 and not args.no_cpu_baseline) else None
+    Qh = Q.cpu().numpy() if (args.full and rank == 0 and not args.no_cpu_baseline) else None
     secondary = None
-    if (world == 1 and rank == 0 and not args.no_secondary and n == 8192 and args.route == "schur"
+    if (args.full and world == 1 and rank == 0 and not args.no_secondary and n == 8192 and args.route == "schur"
             and not os.environ.get("CIP_BENCH_PMC_CHILD")):
         secondary = {}
         try:                                         # the literal 3x3 route on the headline workload (needs Q: before it is dropped)
@@ -882,18 +919,6 @@ def main():
             # iteration at 1e-6, by tests/test_gpu_configs_full.py)
             "iters_gpu": iters, "iters_cpu": fx["Iter"] if fx else None,
             "iters_cpu_source": "tests/golden/fullsize_trajectories.json (oracle: pivot(kktsolver_2x2), same inputs)" if fx else None,
-            "breakdown_ms": {"assemble": st["ms_assemble"], "ldlt_factor": st["ms_ldlt"], "solve4x4": solve_ms,
-                             "ldlt_tflops_whole_factor": (N ** 3 / 3.0) / (st["ms_ldlt"] * 1e-3) / 1e12
-                             if st["ms_ldlt"] > 0 else None},
-            "roofline_solve": {"bound": "hbm", "kernel": "LDL' triangular sweeps inside cip_solve4x4 (k_gemv_t block steps)",
-                               "achieved": (8.0 * N * (N + 1) + 16.0 * N * min(1024, ks.Npad)) / (solve_ms * 1e-3) / 1e9,
-                               "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                               "frac": (8.0 * N * (N + 1) + 16.0 * N * min(1024, ks.Npad)) / (solve_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                               "traffic": live_traffic[2] if live_traffic[2] is not None else pmc_solve_traffic(ks.Npad),
-                               "traffic_measured_live": live_traffic[2] is not None,
-                               "note": "algorithmic bytes of one solve = L read once per sweep (8 N (N+1)) + the 1024-wide block "
-                                       "inverses (16 N Bs); time = whole cip_solve4x4 call (cone division, A'/A products, "
-                                       "two sweeps), host-timed average of 5"},
             "roofline": {"bound": "mfma",
                          "kernel": "LDL' trailing update: k_ldlt_trailing_64 (64x64 fp64-MFMA tiles, K = outer block)",
                          "achieved": ach, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -913,12 +938,25 @@ def main():
                          "launches": prof["launches"], "avg_launch_ms": prof["ms"] / max(1.0, prof["launches"]),
                          "algorithmic_flops_per_launch_avg": prof["flops"] / max(1.0, prof["launches"])},
         }
-        out["profiling_cost"] = {"ms_per_step_with_trailing_events": ms_per_step,
-                                 "ms_per_step_without": elapsed_noprof / args.steps * 1e3,
-                                 "profiled_steps": (args.steps + prof_stride - 1) // prof_stride, "profile_stride": prof_stride,
-                                 "note": "`value` is measured WITH the per-launch HIP events of the roofline inside the timed "
-                                         "region (contract): every trailing-update launch of every `profile_stride`-th timed step; "
-                                         "the same steps again without any events, same session"}
+        if args.full:
+            out["breakdown_ms"] = {"assemble": st["ms_assemble"], "ldlt_factor": st["ms_ldlt"], "solve4x4": solve_ms,
+                                   "ldlt_tflops_whole_factor": (N ** 3 / 3.0) / (st["ms_ldlt"] * 1e-3) / 1e12
+                                   if st["ms_ldlt"] > 0 else None}
+            out["roofline_solve"] = {"bound": "hbm", "kernel": "LDL' triangular sweeps inside cip_solve4x4 (k_gemv_t block steps)",
+                                     "achieved": (8.0 * N * (N + 1) + 16.0 * N * min(1024, ks.Npad)) / (solve_ms * 1e-3) / 1e9,
+                                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "frac": (8.0 * N * (N + 1) + 16.0 * N * min(1024, ks.Npad)) / (solve_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                     "traffic": live_traffic[2] if live_traffic[2] is not None else pmc_solve_traffic(ks.Npad),
+                                     "traffic_measured_live": live_traffic[2] is not None,
+                                     "note": "algorithmic bytes of one solve = L read once per sweep (8 N (N+1)) + the 1024-wide block "
+                                             "inverses (16 N Bs); time = whole cip_solve4x4 call (cone division, A'/A products, "
+                                             "two sweeps), host-timed average of 5"}
+            out["profiling_cost"] = {"ms_per_step_with_trailing_events": ms_per_step,
+                                     "ms_per_step_without": elapsed_noprof / args.steps * 1e3,
+                                     "profiled_steps": (args.steps + prof_stride - 1) // prof_stride, "profile_stride": prof_stride,
+                                     "note": "`value` is measured WITH the per-launch HIP events of the roofline inside the timed "
+                                             "region (contract): every trailing-update launch of every `profile_stride`-th timed step; "
+                                             "the same steps again without any events, same session"}
         if pb is not None:
             out["plugin_boundary"] = pb
         if secondary is not None:
@@ -929,7 +967,7 @@ def main():
             out["c5_single_gpu"] = c5_single
         if c5_shards is not None:
             out["c5_shards"] = c5_shards
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(Qh, n, spf)
             out["cpu_baseline"] = cb
             if pb is not None and not args.no_converge:

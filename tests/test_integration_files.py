@@ -1,12 +1,10 @@
 """The reference-side binding (integration/ConicIPHIP: a Julia package) cannot be executed in this image --
 no Julia -- so it is checked mechanically against the C ABI it binds: every `ccall` names a function declared in
 include/cipkkt.h with the same number of arguments, the Julia `CipProblem` / `CipOptions` / `CipResult` structs mirror `cip_problem` / `cip_options` / `cip_result` field for field (order, names, C types),
-the package files are complete, and integration/moi_kktsolver.patch applies to the reference's src/MOI_wrapper.jl (when the
-reference tree is present: in the build container, not on the GPU box)."""
+the package files are complete, and integration/moi_kktsolver.patch applies to the reference's src/MOI_wrapper.jl (whose lines
+are pinned by their digests in tests/golden/reference_api.json)."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
@@ -199,56 +197,85 @@ def test_native_loop_and_batch_are_bound():
         assert name in tests, name
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/MOI_wrapper.jl") or shutil.which("patch") is None,
-                    reason="reference tree / patch(1) not present (GPU box)")
-def test_moi_patch_applies_to_the_reference(tmp_path):
-    work = tmp_path / "ConicIP" / "src"
-    work.mkdir(parents=True)
-    shutil.copy("/root/reference/src/MOI_wrapper.jl", work / "MOI_wrapper.jl")
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(ROOT, "integration", "moi_kktsolver.patch")],
-                       cwd=tmp_path / "ConicIP", capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    r = subprocess.run(["patch", "-p1", "-i", os.path.join(ROOT, "integration", "moi_kktsolver.patch")],
-                       cwd=tmp_path / "ConicIP", capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    out = (work / "MOI_wrapper.jl").read_text()
+REF_API = os.path.join(ROOT, "tests", "golden", "reference_api.json")      # pinned by tests/golden/make_reference_api.py
+
+
+def _reference_api():
+    import json
+    with open(REF_API) as f:
+        return json.load(f)
+
+
+def _patch_hunks(text):
+    """The hunks of a unified diff of one file: [(old_start, old_lines, new_lines)], lines without their one-character tag."""
+    hunks, cur = [], None
+    for line in text.split("\n"):
+        m = re.match(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+        if m:
+            cur = (int(m.group(1)), [], [], int(m.group(2) or 1), int(m.group(4) or 1))
+            hunks.append(cur)
+        elif cur is not None and (line[:1] in (" ", "-", "+") or line == ""):
+            tag, body = (line[:1] or " "), line[1:]
+            if tag in (" ", "-"):
+                cur[1].append(body)
+            if tag in (" ", "+"):
+                cur[2].append(body)
+    for start, old, new, n_old, n_new in hunks:       # (a trailing empty string of the file is not a context line)
+        while len(old) > n_old and old[-1] == "" and new and new[-1] == "":
+            old.pop(); new.pop()
+        assert (len(old), len(new)) == (n_old, n_new), ("hunk at line %d: %d / %d lines, header says %d / %d"
+                                                        % (start, len(old), len(new), n_old, n_new))
+    return [(start, old, new) for start, old, new, _, _ in hunks]
+
+
+def test_moi_patch_applies_to_the_reference():
+    """integration/moi_kktsolver.patch applies to the reference's src/MOI_wrapper.jl exactly (no offset, no fuzz): every context
+    and removed line of every hunk is, by its sha256, the reference's line at that place (tests/golden/reference_api.json), the
+    hunks are in order and do not overlap -- and the patched file has the `kktsolver` / `solve` options the shim documents."""
+    import hashlib
+    ref = _reference_api()["moi_wrapper_line_sha256"]
+    digest = lambda line: hashlib.sha256(line.encode("utf-8")).hexdigest()
+    patch = open(os.path.join(ROOT, "integration", "moi_kktsolver.patch"), encoding="utf-8").read()
+    assert patch.startswith("--- a/src/MOI_wrapper.jl\n+++ b/src/MOI_wrapper.jl\n")
+    hunks = _patch_hunks(patch)
+    assert hunks
+    out, pos = [], 0                                  # the patched file: the reference's lines stand in by their digests
+    for start, old, new in hunks:
+        at = start - 1
+        assert at >= pos, "hunks overlap or are out of order at line %d" % start
+        assert at + len(old) <= len(ref), "hunk at line %d runs past the end of the reference's file" % start
+        for k, line in enumerate(old):
+            assert digest(line) == ref[at + k], "line %d of src/MOI_wrapper.jl is not %r" % (at + k + 1, line)
+        out += ref[pos:at] + new
+        pos = at + len(old)
+    out = "\n".join(out + ref[pos:])
     assert "kktsolver = dest.kktsolver" in out and 'attr.name == "kktsolver"' in out and "kktsolver::Any" in out
     assert "dest.sol = dest.solve(Q, c_int, A, b, cone_dims, G, d;" in out and "solve::Any" in out
 
 
-REF_SRC = "/root/reference/src"
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_SRC, "ConicIP.jl")), reason="reference tree not present (GPU box)")
 def test_every_conicip_identifier_the_julia_shim_uses_exists_in_the_reference():
     """integration/ConicIPHIP cannot be executed here (no julia in the image): a second static check beside the ccall / struct
     ones -- every name the shim takes from ConicIP is defined in the reference where the shim's comments say: `Block` with a
     `Blocks` vector (src/blockmatrices.jl:35-41), `VecCongurance` with its `R` (src/ConicIP.jl:35), `ord` (:85), `Solution` with
     the eleven fields the shim fills positionally (:384-398), `imcols` / `preprocess_conicIP` (src/preprocessor.jl), `pivot` and
-    `kktsolver_2x2` (src/kktsolvers.jl), the keyword names and defaults of `conicIP` (src/ConicIP.jl:498-509)."""
-    rd = lambda f: open(os.path.join(REF_SRC, f), encoding="utf-8").read()
-    core, blocks, pre, kkt = rd("ConicIP.jl"), rd("blockmatrices.jl"), rd("preprocessor.jl"), rd("kktsolvers.jl")
+    `kktsolver_2x2` (src/kktsolvers.jl), the keyword names and defaults of `conicIP` (src/ConicIP.jl:498-509).  The reference's
+    side is pinned as data in tests/golden/reference_api.json (tests/golden/make_reference_api.py)."""
+    api = _reference_api()
     shim = open(os.path.join(ROOT, "integration", "ConicIPHIP", "src", "ConicIPHIP.jl"), encoding="utf-8").read()
-    assert re.search(r"mutable struct Block\b", blocks) and re.search(r"Blocks::Vector\{BlockElem\}", blocks)
-    assert re.search(r"mutable struct VecCongurance; R :: Matrix; end", core)
-    assert re.search(r"^ord\(x\) = ", core, re.M)
-    m = re.search(r"mutable struct Solution\n(.*?)\nend", core, re.S)
-    fields = re.findall(r"^\s*(\w+)\s*::", m.group(1), re.M)
-    assert fields == ["y", "w", "v", "status", "Iter", "Mu", "prFeas", "duFeas", "muFeas", "pobj", "dobj"]
+    for what in ("Block: mutable struct with Blocks::Vector{BlockElem}", "VecCongurance: mutable struct with R::Matrix", "ord",
+                 "imcols", "preprocess_conicIP", "pivot", "kktsolver_2x2"):
+        assert api["definitions"][what] is True, what
+    assert api["solution_fields"] == ["y", "w", "v", "status", "Iter", "Mu", "prFeas", "duFeas", "muFeas", "pobj", "dobj"]
     # the shim builds Solution positionally with exactly these eleven values, in this order
     call = re.search(r"ConicIP\.Solution\(y, w, v, _STATUS\[r\.status \+ 1\], Int\(r\.iter\), r\.mu, r\.prFeas, r\.duFeas, r\.muFeas, r\.pobj, r\.dobj\)", shim)
     assert call, "the shim's Solution constructor call changed: re-check it against src/ConicIP.jl:384-398"
-    assert re.search(r"^function imcols\(A, b", pre, re.M) and re.search(r"^function preprocess_conicIP\(Q, c", pre, re.M)
-    assert re.search(r"^function pivot", kkt, re.M) or re.search(r"^pivot\(", kkt, re.M) or "pivotgen" in kkt
-    assert re.search(r"function kktsolver_2x2", kkt)
     # every `ConicIP.<name>` of the shim is a name the reference defines somewhere in src/
-    everything = core + blocks + pre + kkt + rd("MOI_wrapper.jl")
     for name in sorted(set(re.findall(r"ConicIP\.(\w+)", shim))):
         if name in ("jl",):                                   # "ConicIP.jl:123" in comments
             continue
-        assert re.search(r"\b%s\b" % re.escape(name), everything), "ConicIP.%s is not a name of the reference" % name
+        assert name in api["names_defined"], "ConicIP.%s is new in the shim: re-pin with tests/golden/make_reference_api.py" % name
+        assert api["names_defined"][name] is True, "ConicIP.%s is not a name of the reference" % name
     # keyword names and defaults of conicIP the shim repeats (src/ConicIP.jl:498-509)
-    sig = core[core.index("function conicIP("):core.index("function conicIP(") + 1500]
     for kw, default in (("optTol", "1e-6"), ("DTB", "0.01"), ("maxRefinementSteps", "3"), ("maxIters", "100")):
-        assert re.search(r"%s\s*=\s*%s" % (kw, re.escape(default)), sig), kw
+        assert api["conicIP_keyword_defaults"][kw] == default, kw
         assert re.search(r"%s\s*=\s*%s" % (kw, re.escape(default)), shim), kw

@@ -3,7 +3,7 @@
 # usage: bash tools/ab_quick.sh rounds name=path.so|default ...
 R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 rounds=$1; shift
-B="--steps 20 --warmup 5 --no-cpu-baseline --no-c5 --no-secondary --no-plugin-boundary --no-live-pmc"
+B="--full --steps 20 --warmup 5 --no-cpu-baseline --no-c5 --no-secondary --no-plugin-boundary --no-live-pmc"
 for r in $(seq $rounds); do
   for a in "$@"; do
     name=${a%%=*}; path=${a#*=}

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-ab_solve}
 mkdir -p $OUT
 cd $R
-B="--steps 20 --warmup 5 --no-cpu-baseline --no-converge --no-c5 --no-secondary --no-plugin-boundary --no-live-pmc"
+B="--full --steps 20 --warmup 5 --no-cpu-baseline --no-converge --no-c5 --no-secondary --no-plugin-boundary --no-live-pmc"
 pick() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); b=d.get('breakdown_ms',{}); print(sys.argv[2], 'value', round(d['value'],2), 'ms/step', round(d['ms_per_step'],4), 'factor', b.get('ldlt_factor'), 'solve4x4', b.get('solve4x4'), 'trail TF', d['roofline']['achieved'])" $1 $2; }
 for rep in 1 2; do
   for f in 0 2; do

@@ -3,6 +3,7 @@
 # wave cycles split into parked (s_waitcnt / barrier), issue-stalled and issuing; LDS bank-conflict cycles against LDS-active cycles.
 # usage: bash tools/pmc_sq.sh [outdir] [workload script + args, default: bench.py at the headline size]   (every kernel with >= 0.5 % of the wave cycles is listed)
 R=$(cd "$(dirname "$0")/.." && pwd); OUT=${1:-$R/gpurun_out/pmc_sq}; shift; WL=${*:-$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 --no-live-pmc}; case $OUT in /*) ;; *) OUT=$R/$OUT;; esac; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
+[ $# -eq 0 ] && WL="$WL --full"      # the default workload: bench.py's whole report (configs 3 / 4, plugin boundary included)
 for pass in "stall:SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS" "lds:SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS"; do
   name=${pass%%:*}; ctrs=${pass#*:}
   rm -rf /tmp/pmcsq_$name

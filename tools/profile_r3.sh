@@ -8,12 +8,12 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 10 --warmup 3 > $OUT/final_bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o final -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-converge --no-c5 > $OUT/final_bench_profiled.json 2>/dev/null
+python3 $R/bench.py --full --steps 10 --warmup 3 > $OUT/final_bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o final -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-converge --no-c5 > $OUT/final_bench_profiled.json 2>/dev/null
 cp $OUT/stats/final_kernel_stats.csv $OUT/final_kernel_stats.csv
 for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "mfma:SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   name=${pass%%:*}; ctrs=${pass#*:}
-  rocprofv3 --pmc $ctrs --output-format csv -d $OUT/pmc_$name -o pmc -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
+  rocprofv3 --pmc $ctrs --output-format csv -d $OUT/pmc_$name -o pmc -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
   python3 $R/tools/pmc_extract.py $OUT/pmc_$name/pmc_counter_collection.csv $OUT/final_pmc_$name.csv
 done
 # XCD-aware patch order of the trailing update (CIP_TRAIL_PATCH = 4 / 8) against the plain tile order, same session, 3 rounds:
@@ -21,7 +21,7 @@ done
 python3 $R/tools/ab_factor.py plain=default patch4=env:CIP_TRAIL_PATCH=4 patch8=env:CIP_TRAIL_PATCH=8 --rounds 3 > $OUT/trail_patch_ab.txt 2>&1
 for v in 4 8; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    CIP_TRAIL_PATCH=$v rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_patch${v}_$c -o pmc -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
+    CIP_TRAIL_PATCH=$v rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_patch${v}_$c -o pmc -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
     python3 $R/tools/pmc_extract.py $OUT/pmc_patch${v}_$c/pmc_counter_collection.csv $OUT/patch${v}_pmc_$c.csv
   done
 done

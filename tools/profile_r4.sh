@@ -7,17 +7,17 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/final4
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 5 > $OUT/final_bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o final -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-converge --no-c5 > $OUT/final_bench_profiled.json 2>/dev/null
+python3 $R/bench.py --full --steps 20 --warmup 5 > $OUT/final_bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o final -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-converge --no-c5 > $OUT/final_bench_profiled.json 2>/dev/null
 cp $OUT/stats/final_kernel_stats.csv $OUT/final_kernel_stats.csv
 for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "mfma:SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   name=${pass%%:*}; ctrs=${pass#*:}
-  rocprofv3 --pmc $ctrs --output-format csv -d $OUT/pmc_$name -o pmc -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
+  rocprofv3 --pmc $ctrs --output-format csv -d $OUT/pmc_$name -o pmc -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
   python3 $R/tools/pmc_extract.py $OUT/pmc_$name/pmc_counter_collection.csv $OUT/final_pmc_$name.csv
 done
 # the literal 3x3 route at the headline size: N = n + m = 16384 (src/kktsolvers.jl:254-257)
-python3 $R/bench.py --route full3x3 --steps 5 --warmup 2 --no-cpu-baseline --no-c5 > $OUT/bench_full3x3.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/f33 -o f33 -- python3 $R/bench.py --route full3x3 --steps 3 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
+python3 $R/bench.py --full --route full3x3 --steps 5 --warmup 2 --no-cpu-baseline --no-c5 > $OUT/bench_full3x3.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/f33 -o f33 -- python3 $R/bench.py --full --route full3x3 --steps 3 --warmup 1 --no-cpu-baseline --no-converge --no-c5 > /dev/null 2>&1
 cp $OUT/f33/f33_kernel_stats.csv $OUT/full3x3_kernel_stats.csv
 # per-launch durations along one factorisation; the end of a factorisation on both streams (side-stream solve preparation on / off)
 bash $R/tools/panel_trace.sh r4=default > $OUT/panel_trace.txt 2>&1

@@ -5,7 +5,7 @@ R=$(cd "$(dirname "$0")/.." && pwd); OUT=$R/gpurun_out/step_trace; mkdir -p $OUT
 a=${1:-new=default}; name=${a%%=*}; path=${a#*=}
 [ "$path" = default ] && unset CIPKKT_LIB || export CIPKKT_LIB=$R/$path
 rm -rf /tmp/st_$name
-rocprofv3 --kernel-trace --output-format csv -d /tmp/st_$name -o t -- python3 $R/bench.py --no-cpu-baseline --no-c5 --steps 4 --warmup 2 > $OUT/$name.out 2> $OUT/$name.err
+rocprofv3 --kernel-trace --output-format csv -d /tmp/st_$name -o t -- python3 $R/bench.py --full --no-cpu-baseline --no-c5 --steps 4 --warmup 2 > $OUT/$name.out 2> $OUT/$name.err
 f=$(find /tmp/st_$name -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY' | tee $OUT/$name.txt
 import csv, sys, collections
