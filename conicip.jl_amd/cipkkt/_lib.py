@@ -17,6 +17,7 @@ FLAG_DEVICE_PTRS = 1
 FLAG_CSR_HOST = 2
 E_SINGULAR = -5
 E_UNSUPPORTED = -6
+E_RETRY = -7
 
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)

@@ -560,7 +560,7 @@ static bool graph_wanted(cip_handle *h) {
 }
 thread_local CipGraphBuilder *cip_tl_builder = nullptr;
 template <class F>
-static int graph_run(cip_handle *h, hipGraphExec_t *exec, F &&enqueue) {
+static int graph_run(cip_handle *h, hipGraphExec_t *exec, F &&enqueue, bool *replayed = nullptr) {
     if (cip_in_batch() || !graph_wanted(h) || h->timing || h->ws.prof) return enqueue();
     if (!*exec) {
         CipGraphBuilder b = {nullptr, nullptr, false, true};
@@ -574,6 +574,7 @@ static int graph_run(cip_handle *h, hipGraphExec_t *exec, F &&enqueue) {
         if (ei != hipSuccess) { (void)hipGetLastError(); *exec = nullptr; h->graph_state = -1; return enqueue(); }
     }
     CIP_HIP_CHECK(hipGraphLaunch(*exec, h->stream));
+    if (replayed) *replayed = true;
     return 0;
 }
 
@@ -615,11 +616,22 @@ static int factor_enqueue(cip_handle *h) {
     if (h->timing) CIP_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
     {
         CipRange rg("cip:ldlt");
-        if (h->gx_factor && h->gx_factor_lazyC != h->ws.lazyC) {     // recorded under another lazy-copy state: record again
+        // recorded under another lazy-copy state or chain form (a replay after a give-up must not run the fused chain again): record again
+        if (h->gx_factor && (h->gx_factor_lazyC != h->ws.lazyC || h->gx_factor_unfused != h->ws.unfused)) {
             (void)hipGraphExecDestroy(h->gx_factor); h->gx_factor = nullptr;
         }
         h->gx_factor_lazyC = h->ws.lazyC;
-        if ((rc = graph_run(h, &h->gx_factor, [&]() { return cip_ldlt_factor(h->stream, h->K, h->Npad, h->ldk, h->ws); }))) return rc;
+        h->gx_factor_unfused = h->ws.unfused;
+        bool replayed = false;
+        if ((rc = graph_run(h, &h->gx_factor, [&]() {
+                 const int r = cip_ldlt_factor(h->stream, h->K, h->Npad, h->ldk, h->ws);
+                 if (cip_tl_builder) h->gx_factor_fused = cip_ldlt_last_factor_fused();
+                 return r;
+             }, &replayed)))
+            return rc;
+        // the give-up test hook of a replay decides from the chain the graph holds (a direct launch: cip_ldlt_factor has seen to it)
+        if (replayed && (rc = cip_ldlt_debug_giveup(h->stream, h->K, h->Npad, h->ldk, h->ws, h->gx_factor_fused)))
+            return rc;
     }
     h->n_factor += 1;
     if (!h->info_host) {
@@ -646,6 +658,19 @@ static int factor_enqueue(cip_handle *h) {
 // regularised factorisation, once, for good -- and if that one fails too the error is reported (CIP_E_SINGULAR).
 static int factor_resolve(cip_handle *h, bool wait);
 int cip_factor_resolve(cip_handle *h, int wait) { return factor_resolve(h, wait != 0); }
+// enqueue the factorisation again and wait for its flags (after a give-up, or with the regularisation switched on).  A give-up of
+// the fused chain in THIS factorisation is answered at once: the handle switches to the three-launch chain and redoes it.
+static int refactor_and_wait(cip_handle *h) {
+    for (;;) {
+        int rc;
+        if ((rc = factor_enqueue(h))) return rc;
+        { bool landed = false; if ((rc = info_landed(h, true, &landed))) return rc; }
+        h->info_pending = false;
+        if (h->info_host[3] == 0 || h->info_host[1] != 0 || h->ws.unfused) return 0;
+        h->ws.unfused = 1;
+        h->n_chain_fallbacks += 1;
+    }
+}
 static int factor_resolve(cip_handle *h, bool wait) {
     if (!h->info_pending) return 0;
     {
@@ -655,26 +680,23 @@ static int factor_resolve(cip_handle *h, bool wait) {
         if (!landed) return 0;
     }
     h->info_pending = false;
+    // solves enqueued on the factorisation being resolved: if it is redone below, they ran on another factor -- repeat them
+    const int spec = h->spec_solves;
+    bool redone = false;
     // info_host: [0] first bad pivot of any kind (1-based column), [1] bail-out flag of the sweep kernels,
-    //            [2] first zero / non-finite pivot
+    //            [2] first zero / non-finite pivot, [3] an in-launch wait of the fused chain gave up
     if (h->info_host[3] != 0 && h->info_host[1] == 0 && !h->ws.unfused) {
         // An in-launch wait of the fused panel chain gave up.  Its waits are for workgroups of the same launch and end within
         // microseconds when the launch has the GPU's attention; on a GPU SHARED WITH OTHER PROCESSES the hardware scheduler can take
         // a launch's workgroups off the chip for longer than the bound (seen with eight processes on one MI355X: round 6).  The
         // three-launch chain has no in-launch wait and produces the same bits: this handle keeps it from now on, and the
-        // factorisation is redone (assembly included: K holds a partial factor).
-        const int spec0 = h->spec_solves;
+        // factorisation is redone (assembly included: K holds a partial factor).  The redo's own pivot flags go through the
+        // checks below like any factorisation's.
         h->ws.unfused = 1;
         h->n_chain_fallbacks += 1;
         int rc;
-        if ((rc = factor_enqueue(h))) return rc;
-        { bool landed = false; if ((rc = info_landed(h, true, &landed))) return rc; }
-        h->info_pending = false;
-        if (spec0 > 0) {
-            cip_set_error("LDL': %d solve(s) were enqueued on a factorisation whose panel chain gave up an in-launch wait; the handle has "
-                          "switched to the three-launch chain -- repeat them", spec0);
-            return CIP_E_SINGULAR;
-        }
+        if ((rc = refactor_and_wait(h))) return rc;
+        redone = true;
     }
     if (h->info_host[3] != 0 || h->info_host[1] != 0) {
         cip_set_error("LDL': in-launch wait of the panel chain gave up (%d)", h->info_host[3]);
@@ -682,26 +704,35 @@ static int factor_resolve(cip_handle *h, bool wait) {
         return CIP_E_HIP;
     }
     int info = h->info_host[0];
-    if (info == 0) { h->pivots_verified = true; return 0; }
-    const int spec = h->spec_solves;
+    if (info == 0 || (h->reg_rel > 0.0 && h->info_host[2] == 0)) {
+        // (regularised factor: a wrong-sign pivot -- |d| ~ delta, rounding decides its sign -- is harmless, the refinement in
+        //  solve3x3 works against the true operator; a zero / non-finite one is not)
+        h->pivots_verified = true;
+        if (redone && spec > 0) {
+            cip_set_error("LDL': %d solve(s) were enqueued on a factorisation whose panel chain gave up an in-launch wait; the handle has "
+                          "switched to the three-launch chain -- repeat them", spec);
+            return CIP_E_RETRY;
+        }
+        return 0;
+    }
     if (h->reg_rel > 0.0) {
-        // regularised factor: a wrong-sign pivot (|d| ~ delta, rounding decides its sign) is harmless -- the refinement in
-        // solve3x3 works against the true operator -- but a zero / non-finite one is not
-        if (h->info_host[2] == 0) { h->pivots_verified = true; return 0; }
         info = h->info_host[2];
     } else if (h->auto_reg) {
         h->reg_rel = getenv("CIP_AUTO_REG") ? atof(getenv("CIP_AUTO_REG")) : CIP_AUTO_REG;
         h->n_regularized += 1;
         int rc;
-        if ((rc = factor_enqueue(h))) return rc;
-        { bool landed = false; if ((rc = info_landed(h, true, &landed))) return rc; }
-        h->info_pending = false;
+        if ((rc = refactor_and_wait(h))) return rc;
+        if (h->info_host[3] != 0 || h->info_host[1] != 0) {
+            cip_set_error("LDL': in-launch wait of the panel chain gave up (%d)", h->info_host[3]);
+            h->factored = false;
+            return CIP_E_HIP;
+        }
         if (h->info_host[2] == 0) {
             h->pivots_verified = true;
             if (spec > 0) {
                 cip_set_error("LDL': %d solve(s) were enqueued on a factorisation that met a bad pivot; the handle has switched "
                               "to the regularised factorisation -- repeat them", spec);
-                return CIP_E_SINGULAR;
+                return CIP_E_RETRY;
             }
             return 0;
         }
@@ -1061,26 +1092,48 @@ extern "C" int cip_ldlt_workspace_bytes(int N, size_t *bytes) {
     *bytes = cip_ldlt_ws_bytes(N, -1);                  // room for the one-launch block steps whatever the mode is now or later
     return 0;
 }
+// N and ld multiples of 128 (cipkkt.h), checked here before anything is enqueued
+static bool ldlt_dims_ok(const double *K, int N, int ld, const void *workspace) {
+    return K && workspace && N > 0 && N % CIP_NB == 0 && ld >= N && ld % CIP_NB == 0;
+}
 extern "C" int cip_ldlt_factor_dev(void *stream, double *K, int N, int ld, void *workspace, int *info_host) {
-    if (!K || !workspace || N <= 0 || N % CIP_NB || ld < N || ld % 2) { cip_set_error("bad argument"); return CIP_E_INVALID; }
+    if (!ldlt_dims_ok(K, N, ld, workspace)) {
+        cip_set_error("cip_ldlt_factor_dev: bad argument (K, workspace non-NULL; N > 0 and ld >= N multiples of 128)");
+        return CIP_E_INVALID;
+    }
     LdltWorkspace ws{};
     cip_ldlt_ws_carve(workspace, N, &ws, cip_ldlt_fused_for(N));      // (the workspace has room for either mode: cip_ldlt_workspace_bytes)
     int rc = cip_ldlt_factor((hipStream_t)stream, K, N, ld, ws);
     if (rc) return rc;
-    if (info_host) {
-        CIP_HIP_CHECK(hipMemcpyAsync(info_host, ws.info, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        CIP_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    // all four flag words: [3] != 0 -- an in-launch wait of the fused chain gave up and K holds a partial factor
+    int flags[4] = {0, 0, 0, 0};
+    CIP_HIP_CHECK(hipMemcpyAsync(flags, ws.info, sizeof(flags), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    CIP_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    if (info_host) *info_host = flags[0];
+    if (flags[3] != 0) {
+        cip_set_error("cip_ldlt_factor_dev: an in-launch wait of the panel chain gave up (%d): K holds a partial factor -- supply K "
+                      "again and repeat the call", flags[3]);
+        return CIP_E_RETRY;
     }
     return 0;
 }
 extern "C" int cip_ldlt_solve_dev(void *stream, const double *K, int N, int ld, const void *workspace, double *rhs) {
-    if (!K || !workspace || !rhs || N <= 0 || N % CIP_NB) { cip_set_error("bad argument"); return CIP_E_INVALID; }
+    if (!ldlt_dims_ok(K, N, ld, workspace) || !rhs) {
+        cip_set_error("cip_ldlt_solve_dev: bad argument (K, workspace, rhs non-NULL; N > 0 and ld >= N multiples of 128)");
+        return CIP_E_INVALID;
+    }
     LdltWorkspace ws{};
     cip_ldlt_ws_carve((void *)workspace, N, &ws, cip_ldlt_fused_for(N));   // same mode as at the factorisation: cip_set_solve_fused must not change between a factor and its solves
     return cip_ldlt_solve((hipStream_t)stream, K, N, ld, ws, rhs);
 }
 extern "C" int cip_gemm_nt_dev(void *stream, int M, int N, int K, double alpha, const double *A, int lda, const double *B,
                                int ldb, double *C, int ldc, int lower_only) {
+    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || M % CIP_NB || N % CIP_NB || K % 16 || lda < M || ldb < N || ldc < M ||
+        (lower_only && M != N)) {
+        cip_set_error("cip_gemm_nt_dev: bad argument (A, B, C non-NULL; M, N > 0 multiples of 128, K > 0 a multiple of 16, "
+                      "lda >= M, ldb >= N, ldc >= M; M == N with lower_only)");
+        return CIP_E_INVALID;
+    }
     GemmArgs g = {};
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.alpha = alpha;
     g.lower = lower_only ? 1 : 0;

@@ -89,6 +89,8 @@ struct cip_handle {
     // its C operand (ws.lazyC: Q while the copy is lazy, else null).  A replay under another state would read stale data
     // (ADVICE r3): factor_enqueue drops the graph and records a new one when it differs.
     const double *gx_factor_lazyC = nullptr;
+    int gx_factor_unfused = 0;     // ws.unfused when gx_factor was recorded
+    bool gx_factor_fused = false;  // gx_factor holds a fused panel chain (the give-up test hook fires on its replays)
     int graph_state = 0;            // 0 undecided, 1 in use, -1 off (null stream, large system, capture failed, CIP_GRAPH=0)
 
     // ---- stats

@@ -180,6 +180,10 @@ int cip_ldlt_side_join(hipStream_t s, const struct LdltWorkspace &ws, int J);   
 int cip_kernels_init(void);                // diag.hip: one-time kernel attributes (before any hipGraph capture)
 int cip_ldlt_set_side_prep(int on);       // 1 (default): solve preparation beside the last outer block's panel chain; returns the previous setting
 int cip_debug_chain_giveup_set(int n);    // test hook: the next n fused-chain factorisations report an in-launch wait that gave up; returns the previous count
+// the hook's action behind a factorisation of K (fused: it ran the fused panel chain) -- cip_ldlt_factor calls it, and the handle after a
+// graph replay with the chain form the graph was recorded with
+int cip_ldlt_debug_giveup(hipStream_t s, double *K, int Npad, long ld, const struct LdltWorkspace &ws, bool fused);
+bool cip_ldlt_last_factor_fused(void);    // did this thread's last cip_ldlt_factor enqueue (or record) a fused panel launch?
 int cip_ldlt_set_fused_chain(int on);     // 1 (default): diag + previous in-block update in one launch; returns the previous setting
 int cip_solve_block(int Npad);
 int cip_solve_block_max_set(int b);              // 128 | 256 | 512 | 1024 (0: query); returns the previous limit

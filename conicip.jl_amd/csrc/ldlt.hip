@@ -295,6 +295,9 @@ static int update_rest_of_block(hipStream_t s, double *K, int Npad, long ld, dou
 // CIP_FUSE_DIAG=0 / cip_set_ldlt_fused_chain(0): the unfused chain (diag -> TRSM -> update per panel), for A/B runs and tests
 int cip_ldlt_set_fused_chain(int on) { fuse_env(); const int prev = g_fuse_diag; if (on == 0 || on == 1 || on == 3) g_fuse_diag = on; return prev; }
 
+// did the last factorisation this thread enqueued (or recorded) launch a panel with an in-launch wait? (the give-up hook, below)
+static thread_local bool tl_ran_fused = false;
+
 // one inner-panel sweep of an outer block: [strip update] -> diagonal kernel -> TRSM, for each 128 columns
 static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws, double *Wb, int C0,
                                int wblk, int t0 = 0, int t1 = -1) {
@@ -327,6 +330,7 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
         const bool small_group = cip_in_batch() && g_fuse_diag == 3 && cip_tl_bz.B <= lsmax && (long)cip_tl_bz.B * (10 + Npad / 64) <= lscus;
         const bool fuse = g_fuse_diag && !ws.unfused && (!cip_in_batch() || small_group);
         if (fuse && g_fuse_diag == 3) {
+            tl_ran_fused = true;
             const bool upd = t > 0 && rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t - 1, gu);
             unsigned *ctr = (unsigned *)(ws.info + 16);
             if ((rc = cip_launch_panel(s, K + c0 + (long)c0 * ld, ld, ws.Xm + (size_t)jb * 2048, ws.dvec + c0, ws.dinv + c0, ws.info, c0,
@@ -336,6 +340,7 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
             continue;
         }
         if (fuse && t > 0 && rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t - 1, gu)) {
+            tl_ran_fused = true;
             if ((rc = cip_launch_diag_upd(s, K + c0 + (long)c0 * ld, ld, ws.Xm + (size_t)jb * 2048, ws.dvec + c0, ws.dinv + c0,
                                           ws.info, c0, ws.signs, (unsigned *)(ws.info + 16) + jb, gu)))
                 return rc;
@@ -591,14 +596,27 @@ int cip_ldlt_side_join(hipStream_t s, const LdltWorkspace &ws, int J) {
     return 0;
 }
 
-// test hook (cip_debug_chain_giveup): the next `n` factorisations on a fused panel chain report that an in-launch wait gave up (info[3]),
-// as a GPU shared with other processes can make them do -- so that the fall-back to the three-launch chain can be tested on one process
-// (n = count + 65536 * skip: the first `skip` fused factorisations from now on are left alone, the `count` after them give up)
-// (+ 2^28: they report a wrong-sign pivot at column 1 instead -- what the automatic regularisation answers)
-static std::atomic<int> g_debug_giveup{0}, g_debug_giveup_skip{0}, g_debug_giveup_kind{0};
+// test hook (cip_debug_chain_giveup): the next `n` factorisations that ran a fused panel chain report that an in-launch wait gave up
+// (info[3]), as a GPU shared with other processes can make them do -- so that the fall-back to the three-launch chain can be tested on
+// one process.  n = count + 65536 * skip: the first `skip` fused factorisations from now on are left alone, the `count` after them give
+// up.  Kinds (bits of n):
+//   2^28  they report a wrong-sign pivot at column 1 instead -- what the automatic regularisation answers
+//   2^29  POISON: besides info[3], the factor is left as stale strips would leave it: the strictly-lower 64 x 64 block under the first
+//         64 x 64 diagonal block (rows 64..127, columns 0..63: there at every order) is multiplied by 1 + 2^-20 and the solve
+//         preparation of the first solve block is redone from it -- a consumer that ignores info[3] then computes a wrong answer
+//   2^30  the first factorisation on the three-launch chain after each give-up of this hook reports a wrong-sign pivot at column 1
+//         (what the redo of a give-up meets when its matrix is not quasi-definite)
+// The hook decides from the chain the factorisation really ran: in a recorded graph, from the chain the graph holds (api.hip).
+static std::atomic<int> g_debug_giveup{0}, g_debug_giveup_skip{0}, g_debug_giveup_kind{0}, g_debug_redo_pivot{0}, g_debug_redo_armed{0};
 int cip_debug_chain_giveup_set(int n) {
     const int prev = g_debug_giveup.load();
-    if (n >= 0) { g_debug_giveup_kind.store((n >> 28) & 1); g_debug_giveup_skip.store((n >> 16) & 0xfff); g_debug_giveup.store(n & 0xffff); }
+    if (n >= 0) {
+        g_debug_giveup_kind.store((n >> 28) & 3);
+        g_debug_redo_pivot.store((n >> 30) & 1);
+        g_debug_redo_armed.store(0);
+        g_debug_giveup_skip.store((n >> 16) & 0xfff);
+        g_debug_giveup.store(n & 0xffff);
+    }
     return prev;
 }
 __global__ void k_debug_set_word(int *p, int v, CipBatch cb) {
@@ -606,14 +624,46 @@ __global__ void k_debug_set_word(int *p, int v, CipBatch cb) {
     CIP_BO1(cb, p);
     if (threadIdx.x == 0) *p = v;
 }
+// K[64:128, 0:64] *= 1 + 2^-20: strictly below the diagonal, inside the N x N lower triangle for every N >= 128 (ld >= N)
+__global__ __launch_bounds__(256) void k_debug_poison_strip(double *K, long ld, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO1(cb, K);
+    const int i = 64 + (threadIdx.x & 63);
+    for (int j = threadIdx.x >> 6; j < 64; j += 4) K[i + (long)j * ld] *= 1.0 + 0x1p-20;
+}
+int cip_ldlt_debug_giveup(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws, bool fused) {
+    if (!fused) {
+        int armed = 1;
+        if (g_debug_redo_armed.load() > 0 && g_debug_redo_armed.compare_exchange_strong(armed, 0)) {
+            cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 0, 1);
+            CIP_HIP_CHECK(hipGetLastError());
+        }
+        return 0;
+    }
+    if (g_debug_giveup.load() <= 0 || g_debug_giveup_skip.fetch_sub(1) > 0 || g_debug_giveup.fetch_sub(1) <= 0) return 0;
+    const int kind = g_debug_giveup_kind.load();
+    if (kind & 1) {
+        cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 0, 1);
+    } else {
+        cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 3, -9);
+        if (g_debug_redo_pivot.load()) g_debug_redo_armed.store(1);
+    }
+    CIP_HIP_CHECK(hipGetLastError());
+    if ((kind & 2) && !(kind & 1)) {
+        int rc;
+        if ((rc = cip_ldlt_side_join(s, ws, -1))) return rc;         // the side stream's preparation reads the block too
+        cip_launch_b(k_debug_poison_strip, dim3(1), dim3(256), 0, s, K, ld);
+        CIP_HIP_CHECK(hipGetLastError());
+        if (!ws.no_prep && (rc = build_solve_blocks(s, K, Npad, ld, ws, 0, 1))) return rc;
+    }
+    return 0;
+}
+bool cip_ldlt_last_factor_fused(void) { return tl_ran_fused; }
 static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws);
 int cip_ldlt_factor(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws) {
+    tl_ran_fused = false;
     const int rc = ldlt_factor_body(s, K, Npad, ld, ws);
-    if (rc == 0 && !ws.unfused && !cip_tl_builder && g_debug_giveup.load() > 0 && g_debug_giveup_skip.fetch_sub(1) <= 0 && g_debug_giveup.fetch_sub(1) > 0) {
-        if (g_debug_giveup_kind.load()) cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 0, 1);
-        else cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 3, -9);
-        CIP_HIP_CHECK(hipGetLastError());
-    }
+    if (rc == 0 && !cip_tl_builder) return cip_ldlt_debug_giveup(s, K, Npad, ld, ws, tl_ran_fused);     // (a recording: api.hip fires it on the replay)
     return rc;
 }
 static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws) {

@@ -636,6 +636,9 @@ int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out) {
     cip_ldlt_ws_carve(w->ldl_s, rp, &w->ws, 0);
     w->wz.signs = w->ws.signs = PivotSigns{0, rp, rp};       // a Cholesky in disguise: every pivot must be positive
     w->wz.x_zeroed = &w->xz_z; w->ws.x_zeroed = &w->xz_s;
+    // the three-launch panel chain: no in-launch wait that could give up (the consumers of these factors -- NT scaling, inertia
+    // certificate, max-step -- read the pivot flags only, not info[3]); same bits as the fused chain
+    w->wz.unfused = w->ws.unfused = 1;
     *out = w;
     return 0;
 }

@@ -71,6 +71,7 @@ typedef struct cip_handle cip_handle;
 #define CIP_E_NOTFACTORED -4
 #define CIP_E_SINGULAR   -5   /* zero / non-finite pivot met in the LDL' */
 #define CIP_E_UNSUPPORTED -6
+#define CIP_E_RETRY      -7   /* nothing is wrong with the input: repeat the call (cip_ldlt_factor_dev: supply K again), or the solves it names */
 
 /* Problem description for cip_create_ex.  A may be given dense (A != NULL) or
  * in CSR (A == NULL, A_rowptr/A_colind/A_val != NULL, 0-based) -- with any mix of cone types (the rows of S cones are expanded
@@ -119,9 +120,11 @@ int cip_get_scaling_packed(cip_handle *h, double *packedF);             /* host 
  * cip_check_factor, by the host-pointer solves (which are synchronous anyway) and by the *_dev solves: those WAIT for
  * the flag until one factorisation of the handle has been seen clean (the factorisation that meets a bad pivot is the
  * first one: LPs, singular Q), afterwards they resolve it only if the read-back has already landed and go ahead
- * speculatively otherwise (a later bad pivot then surfaces from the next resolving call as CIP_E_SINGULAR "repeat
- * them"; cip_check_factor after cip_factor rules that out).  A bad pivot triggers the regularised re-factorisation
- * described below; if that fails too the resolving call returns CIP_E_SINGULAR. */
+ * speculatively otherwise.  When the resolving call has to redo the factorisation (a bad pivot: the regularised
+ * re-factorisation described below; a give-up of the fused panel chain: see cip_debug_chain_giveup) and solves were
+ * enqueued speculatively on the first one, it returns CIP_E_RETRY "repeat them": the handle now holds the good factor,
+ * repeat those solves (cip_check_factor after cip_factor rules that out).  If the regularised re-factorisation fails too
+ * the resolving call returns CIP_E_SINGULAR. */
 int cip_factor(cip_handle *h);
 /* wait for the factorisation and report its status: CIP_OK or CIP_E_SINGULAR */
 int cip_check_factor(cip_handle *h);
@@ -243,8 +246,12 @@ int cip_conicip_many(cip_handle *const *handles, int count, const double *const 
                      double *const *v, cip_result *res, int in_flight);
 
 /* ---- dense symmetric LDL' building blocks (device pointers), usable on their own.
- * K is N x N column-major with leading dimension ld; only the lower triangle is
- * referenced.  N and ld must be multiples of 128 (pad with an identity block).
+ * K is N x N column-major with leading dimension ld >= N; only the lower triangle is
+ * referenced.  N and ld must be multiples of 128 (pad with an identity block); K, workspace and rhs non-NULL -- else
+ * CIP_E_INVALID before anything is enqueued.  Rows N..ld-1 of K are never touched.
+ * cip_ldlt_factor_dev waits for the factorisation and stores its first bad pivot in *info_host (0: none; 1-based column;
+ * info_host may be NULL); it returns CIP_E_RETRY when an in-launch wait of the fused panel chain gave up (see
+ * cip_debug_chain_giveup): K then holds a partial factor and must be supplied again.
  * After a factorisation K holds L strictly below the diagonal, D on it and L' above it OUTSIDE the 128 x 128 diagonal blocks;
  * the upper triangle of the diagonal blocks is undefined.  The workspace size covers either mode of cip_set_solve_fused; the
  * mode in force at cip_ldlt_factor_dev must still be in force at its cip_ldlt_solve_dev calls, and the solve-block limit
@@ -252,7 +259,9 @@ int cip_conicip_many(cip_handle *const *handles, int count, const double *const 
 int cip_ldlt_workspace_bytes(int N, size_t *bytes);
 int cip_ldlt_factor_dev(void *hip_stream, double *K, int N, int ld, void *workspace, int *info_host);
 int cip_ldlt_solve_dev(void *hip_stream, const double *K, int N, int ld, const void *workspace, double *rhs);
-/* C(lower or full) += alpha * A * B'   (A: M x K, B: N x K, all column-major; M,N % 128 == 0, K % 16 == 0) */
+/* C(lower or full) += alpha * A * B'   (A: M x K, B: N x K, all column-major; M,N % 128 == 0, K % 16 == 0, K > 0;
+ * lda >= M, ldb >= N, ldc >= M; A, B, C non-NULL; lower_only needs M == N and leaves the 128 x 128 tiles above the diagonal
+ * untouched -- else CIP_E_INVALID before anything is enqueued) */
 int cip_gemm_nt_dev(void *hip_stream, int M, int N, int K, double alpha,
                     const double *A, int lda, const double *B, int ldb, double *C, int ldc, int lower_only);
 
@@ -284,12 +293,24 @@ int cip_lockstep_solve_block_for(int B);
  * micro-panel through a stage counter; 1 = diagonal kernel + previous panel's update in one launch, TRSM in its own;
  * 0 = three launches per panel.  Same factor bit for bit.  Process-wide; returns the previous setting (other values: query). */
 int cip_set_ldlt_fused_chain(int on);
-/* The fused panel chain waits INSIDE a launch for workgroups of the same launch (bounded: ~1 s, then the factorisation reports that the
- * wait gave up).  On a GPU shared with other processes the hardware scheduler can keep a launch's workgroups apart for longer than that
- * (seen with eight processes on one MI355X).  The library then redoes the factorisation with the three-launch chain -- no in-launch wait,
- * same bits -- and keeps that chain for the handle; a problem of a lock-step group leaves the group and is solved alone.  TEST HOOK: the
- * next n fused-chain factorisations of the process report such a give-up (n < 0: query; n = count + 65536 * skip: the `count` ones after
- * the next `skip`); returns the previous count. */
+/* The fused panel chain waits INSIDE a launch for workgroups of the same launch (bounded: 2e9 ticks of the s_memtime counter, which
+ * counts shader clock cycles -- about 0.8 s at the 2.4 GHz peak clock, longer at a lower clock -- then the factorisation reports
+ * that the wait gave up).  On a GPU shared with other processes the
+ * hardware scheduler can keep a launch's workgroups apart for longer than the wait expects (seen with eight processes on one MI355X).
+ * Every path that runs the fused chain either falls back or reports it: a handle redoes the factorisation with the three-launch
+ * chain -- no in-launch wait, same bits -- and keeps that chain (solves enqueued speculatively on the first one: CIP_E_RETRY, repeat
+ * them); a problem of a lock-step group leaves the group and is solved alone; cip_ldlt_factor_dev returns CIP_E_RETRY; the
+ * factorisations inside large S cones (order >= 133) always run on the three-launch chain.
+ * TEST HOOK: the next `count` factorisations of the process that run the fused chain (directly or as the replay of a recorded
+ * graph that holds it) report such a give-up.  n < 0: query; else n = count + 65536 * skip (+ kind bits): the `count` ones after
+ * the next `skip` (count < 65536, skip < 4096).  Kind bits:
+ *   + 2^28  they report a wrong-sign pivot at column 1 instead of a give-up
+ *   + 2^29  POISON: besides the give-up, the factor is left as a real give-up can leave it -- the strictly-lower 64 x 64 block
+ *           K[64:128, 0:64] is multiplied by 1 + 2^-20 (inside the N x N lower triangle at every order) and the solves follow
+ *           it -- so that whoever ignores the give-up computes a measurably wrong answer
+ *   + 2^30  the first factorisation on the three-launch chain after each give-up of the hook reports a wrong-sign pivot at
+ *           column 1 (the redo meets a bad pivot)
+ * Returns the previous count. */
 int cip_debug_chain_giveup(int n);
 /* how many factorisations of this handle were redone on the three-launch chain after such a give-up (-1: NULL handle) */
 int cip_get_chain_fallbacks(cip_handle *h);

@@ -8,7 +8,7 @@
 //      problem with a chip-wide S cone (lock-step refuses it: thread pool), and a batch holding an S cone beyond the envelope
 //      (refused at level 1: the call must fail cleanly and free everything);
 //   4. the same entry points from several caller threads at once (thread-local batch contexts, the cached arena, the pool);
-//   5. the stand-alone LDL' entry points with a caller-owned workspace in both solve modes.
+//   5. the stand-alone LDL' entry points with a caller-owned workspace in both solve modes, and their refusals of bad arguments.
 // At the end every "device" allocation must have been returned (the fake runtime counts them).
 #include "cipkkt.h"
 #include <cstdio>
@@ -203,6 +203,37 @@ static void standalone_ldlt(void) {
         cip_set_solve_block_max(pb);
         cip_set_solve_fused(prev);
     }
+    // refusals (include/cipkkt.h): a leading dimension below the order or not a multiple of 128, NULL pointers -- CIP_E_INVALID from
+    // the host-side check, with nothing enqueued (the buffers are large enough for every stride tried, should one get through)
+    long l0, l1, e, b, a;
+    std::vector<double> K((size_t)(N + 128) * (N + 128), 0.0), rhs(N + 128, 1.0);
+    std::vector<char> ws(bytes);
+    int info = -1;
+    fake_hip_stats(&l0, &e, &b, &a);
+    for (int ld : {N - 128, N + 64, N + 2, N - 1, 0, -N}) {
+        REQUIRE(cip_ldlt_factor_dev(nullptr, K.data(), N, ld, ws.data(), &info) == CIP_E_INVALID);
+        REQUIRE(cip_ldlt_solve_dev(nullptr, K.data(), N, ld, ws.data(), rhs.data()) == CIP_E_INVALID);
+    }
+    REQUIRE(cip_ldlt_factor_dev(nullptr, nullptr, N, N, ws.data(), &info) == CIP_E_INVALID);
+    REQUIRE(cip_ldlt_factor_dev(nullptr, K.data(), N, N, nullptr, &info) == CIP_E_INVALID);
+    REQUIRE(cip_ldlt_solve_dev(nullptr, nullptr, N, N, ws.data(), rhs.data()) == CIP_E_INVALID);
+    REQUIRE(cip_ldlt_solve_dev(nullptr, K.data(), N, N, nullptr, rhs.data()) == CIP_E_INVALID);
+    REQUIRE(cip_ldlt_solve_dev(nullptr, K.data(), N, N, ws.data(), nullptr) == CIP_E_INVALID);
+    const int M = 256, Nn = 128, Kk = 16;                            // A: M x Kk, B: Nn x Kk, C: M x Nn
+    double *A = K.data(), *B = K.data(), *C = K.data();
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M - 1, B, Nn, C, M, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M, B, Nn - 16, C, M, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M, B, Nn, C, M - 128, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, nullptr, M, B, Nn, C, M, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M, nullptr, Nn, C, M, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M, B, Nn, nullptr, M, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, 0, 1.0, A, M, B, Nn, C, M, 0) == CIP_E_INVALID);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M, B, Nn, C, M, 1) == CIP_E_INVALID);      // lower_only needs M == N
+    fake_hip_stats(&l1, &e, &b, &a);
+    REQUIRE(l1 == l0);
+    // the valid strides of the same calls go through
+    REQUIRE(cip_ldlt_factor_dev(nullptr, K.data(), N, N + 128, ws.data(), &info) == CIP_OK);
+    REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M + 16, B, Nn + 2, C, M + 128, 0) == CIP_OK);
 }
 
 int main(int argc, char **argv) {

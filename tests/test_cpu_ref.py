@@ -32,7 +32,7 @@ def _header_codes():
 
 
 _CODES = _header_codes()
-E_INVALID, E_NOTFACTORED, E_SINGULAR, E_UNSUPPORTED = (_CODES[k] for k in ("CIP_E_INVALID", "CIP_E_NOTFACTORED", "CIP_E_SINGULAR", "CIP_E_UNSUPPORTED"))
+E_INVALID, E_NOTFACTORED, E_SINGULAR, E_UNSUPPORTED, E_RETRY = (_CODES[k] for k in ("CIP_E_INVALID", "CIP_E_NOTFACTORED", "CIP_E_SINGULAR", "CIP_E_UNSUPPORTED", "CIP_E_RETRY"))
 
 
 @pytest.fixture(scope="module")
@@ -55,6 +55,8 @@ def cpu():
 def test_error_codes_match_the_header(cpu):
     from cipkkt import _lib as L
     assert L.E_SINGULAR == E_SINGULAR and len({E_INVALID, E_NOTFACTORED, E_SINGULAR, E_UNSUPPORTED}) == 4
+    # "call again" is told apart from every failure
+    assert L.E_RETRY == E_RETRY and len({E_INVALID, E_NOTFACTORED, E_SINGULAR, E_UNSUPPORTED, E_RETRY, _CODES["CIP_E_NODEVICE"], _CODES["CIP_E_HIP"]}) == 7
 
 
 def _ptr(a):

@@ -138,6 +138,142 @@ def test_ldlt_quasidefinite(lib):
     assert np.all(D[:n] > 0) and np.all(D[n:] < 0)
 
 
+# ----------------------------------------------------------------- the stand-alone entry points at their documented strides
+def _sym_dev(N, seed, quasi):
+    """SPD (quasi = 0) or [S G'; G 0] with the last `quasi` pivots negative (as test_ldlt_quasidefinite), on the device"""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    n = N - quasi
+    M = torch.randn(n, n, generator=g, dtype=torch.float64, device="cuda")
+    K = torch.zeros(N, N, dtype=torch.float64, device="cuda")
+    K[:n, :n] = M @ M.t() / n + torch.eye(n, dtype=torch.float64, device="cuda")
+    if quasi:
+        G = torch.randn(quasi, n, generator=g, dtype=torch.float64, device="cuda") / np.sqrt(n)
+        K[n:, :n] = G
+        K[:n, n:] = G.t()
+    return K
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int64)
+
+
+@pytest.mark.parametrize("N", [384, 1024, 4608])
+@pytest.mark.parametrize("quasi", [0, 1], ids=["spd", "quasidefinite"])
+def test_ldlt_standalone_at_every_leading_dimension(lib, N, quasi):
+    """cip_ldlt_factor_dev / cip_ldlt_solve_dev with ld in {N, N + 128, N + 256} (cipkkt.h: ld >= N, a multiple of 128; 4608 =
+    5 x 896 + 128 runs the automatic 896-column outer block), rows N..ld-1 of K filled with NaN: the factor and the solution are
+    bit-identical across ld (same arithmetic, other addresses), the padding keeps its bits, L D L' reconstructs K to 1e-13 and the
+    solve's normwise backward error is below 1e-14 -- computed on the device against the input K."""
+    from cipkkt import _lib as L
+    Kmat = _sym_dev(N, 700 + N, N // 5 if quasi else 0)
+    nbytes = C.c_size_t()
+    L.check(lib.cip_ldlt_workspace_bytes(N, C.byref(nbytes)))
+    ws = torch.zeros(nbytes.value // 8 + 8, dtype=torch.float64, device="cuda")
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N + 1)
+    rhs0 = torch.randn(N, generator=g, dtype=torch.float64, device="cuda")
+    first = None
+    for ld in (N, N + 128, N + 256):
+        buf = torch.full((N, ld), float("nan"), dtype=torch.float64, device="cuda")    # column j = row j of this view
+        buf[:, :N] = Kmat                                        # symmetric: column-major K
+        pad0 = _bits(buf[:, N:]).clone()
+        info = C.c_int(-1)
+        L.check(lib.cip_ldlt_factor_dev(None, buf.data_ptr(), N, ld, ws.data_ptr(), C.byref(info)))
+        assert info.value == 0, (ld, info.value)
+        x = rhs0.clone()
+        L.check(lib.cip_ldlt_solve_dev(None, buf.data_ptr(), N, ld, ws.data_ptr(), x.data_ptr()))
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(buf[:, N:]), pad0), "ld=%d: the padding rows changed" % ld
+        F = buf[:, :N].t()                                       # the factor, row-major
+        Fl = torch.tril(F)
+        if first is None:
+            Lf = torch.tril(F, -1) + torch.eye(N, dtype=torch.float64, device="cuda")
+            D = torch.diagonal(F)
+            rec = (Lf * D[None, :]) @ Lf.t()
+            err = float(torch.tril(rec - Kmat).abs().max() / Kmat.abs().max())
+            assert err < 1e-13, "||L D L' - K|| / ||K|| = %g" % err
+            if quasi:
+                n = N - N // 5
+                assert bool((D[:n] > 0).all()) and bool((D[n:] < 0).all())
+            res = float(torch.linalg.norm(Kmat @ x - rhs0) / (torch.linalg.matrix_norm(Kmat, 2) * torch.linalg.norm(x)))
+            assert res < 1e-14, "normwise backward error of the solve = %g" % res
+            first = (_bits(Fl).clone(), _bits(x).clone())
+        else:
+            assert torch.equal(_bits(Fl), first[0]), "ld=%d: another factor than at ld=N" % ld
+            assert torch.equal(_bits(x), first[1]), "ld=%d: another solution than at ld=N" % ld
+
+
+@pytest.mark.parametrize("alpha", [0.5, -3.0])
+@pytest.mark.parametrize("lower", [0, 1])
+def test_gemm_nt_at_wider_leading_dimensions(lib, alpha, lower):
+    """cip_gemm_nt_dev with lda > M, ldb > N, ldc > M (NaN in every padding row), K = 16 (the smallest), alpha other than +-1; with
+    lower = 1 the 128 x 128 tiles above the diagonal hold NaN and must keep their bits.  Against numpy at test_gemm_nt's tolerance."""
+    from cipkkt import _lib as L
+    M, N, K = (384, 384, 16) if lower else (256, 384, 16)
+    lda, ldb, ldc = M + 64, N + 128, M + 128
+    rng = np.random.default_rng(int(10 * alpha) + lower + 40)
+    A, B, Cm = rng.standard_normal((M, K)), rng.standard_normal((N, K)), rng.standard_normal((M, N))
+    if lower:
+        for bi in range(M // 128):
+            for bj in range(bi + 1, N // 128):
+                Cm[bi * 128:(bi + 1) * 128, bj * 128:(bj + 1) * 128] = np.nan
+
+    def padded(X, ld):
+        P = np.full((ld, X.shape[1]), np.nan)
+        P[:X.shape[0]] = X
+        return colmajor_dev(P)
+    dA, dB, dC = padded(A, lda), padded(B, ldb), padded(Cm, ldc)
+    c0 = from_colmajor(dC, ldc, N).copy()
+    L.check(lib.cip_gemm_nt_dev(None, M, N, K, alpha, dA.data_ptr(), lda, dB.data_ptr(), ldb, dC.data_ptr(), ldc, lower))
+    torch.cuda.synchronize()
+    full = from_colmajor(dC, ldc, N)
+    np.testing.assert_array_equal(full[M:].view(np.int64), c0[M:].view(np.int64))     # padding rows: same bits
+    got = full[:M]
+    ref = Cm + alpha * (A @ B.T)
+    tol = 1e-11 * K * abs(alpha)
+    for bi in range(M // 128):
+        for bj in range(N // 128):
+            blk = (slice(bi * 128, bi * 128 + 128), slice(bj * 128, bj * 128 + 128))
+            if not lower or bi > bj:
+                np.testing.assert_allclose(got[blk], ref[blk], rtol=0, atol=tol)
+            elif bi == bj:
+                np.testing.assert_allclose(np.tril(got[blk]), np.tril(ref[blk]), rtol=0, atol=tol)
+            else:
+                np.testing.assert_array_equal(got[blk].view(np.int64), c0[blk].view(np.int64))
+
+
+def test_standalone_entry_points_refuse_bad_strides_and_null_pointers(lib):
+    """cipkkt.h: ld >= N and a multiple of 128 for the LDL', lda >= M / ldb >= N / ldc >= M for the GEMM, no NULL pointer -- refused
+    with CIP_E_INVALID by the host-side check, before anything is enqueued (tests/hostsan/drive.cpp counts the launches: none).  The
+    buffers are sized for every stride tried and must keep their bits."""
+    from cipkkt import _lib as L
+    N = 256
+    nbytes = C.c_size_t()
+    L.check(lib.cip_ldlt_workspace_bytes(N, C.byref(nbytes)))
+    ws = torch.zeros(nbytes.value // 8 + 8, dtype=torch.float64, device="cuda")
+    K = torch.full(((N + 256) * (N + 256),), 3.0, dtype=torch.float64, device="cuda")
+    rhs = torch.ones(N + 256, dtype=torch.float64, device="cuda")
+    k0, r0 = K.clone(), rhs.clone()
+    info = C.c_int(-1)
+    for ld in (N - 128, N + 64, N + 2, N - 1, 0):
+        assert lib.cip_ldlt_factor_dev(None, K.data_ptr(), N, ld, ws.data_ptr(), C.byref(info)) == -1, ld
+        assert lib.cip_ldlt_solve_dev(None, K.data_ptr(), N, ld, ws.data_ptr(), rhs.data_ptr()) == -1, ld
+    assert lib.cip_ldlt_factor_dev(None, None, N, N, ws.data_ptr(), C.byref(info)) == -1
+    assert lib.cip_ldlt_factor_dev(None, K.data_ptr(), N, N, None, C.byref(info)) == -1
+    assert lib.cip_ldlt_solve_dev(None, None, N, N, ws.data_ptr(), rhs.data_ptr()) == -1
+    assert lib.cip_ldlt_solve_dev(None, K.data_ptr(), N, N, None, rhs.data_ptr()) == -1
+    assert lib.cip_ldlt_solve_dev(None, K.data_ptr(), N, N, ws.data_ptr(), None) == -1
+    M, Nn, Kk = 256, 128, 16
+    p = K.data_ptr()
+    for args in ((p, M - 1, p, Nn, p, M), (p, M, p, Nn - 16, p, M), (p, M, p, Nn, p, M - 128),
+                 (None, M, p, Nn, p, M), (p, M, None, Nn, p, M), (p, M, p, Nn, None, M)):
+        a, la, b, lb, c, lc = args
+        assert lib.cip_gemm_nt_dev(None, M, Nn, Kk, 1.0, a, la, b, lb, c, lc, 0) == -1, (la, lb, lc)
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(K), _bits(k0)) and torch.equal(_bits(rhs), _bits(r0))
+
+
 @pytest.mark.parametrize("N,bmax", [(384, 128), (640, 128), (1536, 512), (2048, 256), (2048, 512), (3072, 1024)])
 def test_ldlt_solve_one_launch_per_block_step(lib, N, bmax):
     """The triangular sweeps with the pre-multiplied neighbour blocks (one launch per block step, cip_set_solve_fused) against the
