@@ -138,89 +138,15 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
         }
 }
 
-
-// K = 128 with the WHOLE of both operands resident in LDS (128 KB): one global round trip, one barrier, then 32 MFMA
-// steps -- for launches that own a CU's LDS anyway (diag.hip: k_ldlt_diag_upd).  The k-loop of gemm_tile_64 waits for a
-// global load in each of its eight iterations (~1 us each when the tile is alone on its CU).  Same accumulation order
-// as gemm_tile_64: bit-identical results.  Accumulate epilogue.  SC1C: the C tile is written through (`sc1`): its reader
-// is another workgroup of the same launch (k_ldlt_diag_upd).
-template <bool SC1C>
-__device__ __forceinline__ void gemm_tile_64_k128(const GemmArgs &g, double *lds, long i0, long j0) {
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const int k_ld = tid >> 5, rp = tid & 31;
-    const double *Ap = g.A + i0 + 2 * rp;
-    const double *Bp = g.B + j0 + 2 * rp;
-    double *la = lds, *lb = lds + 128 * SB;                     // [k][row], 128 x 64 each
-    // the C tile is fetched FIRST, beside the operands: nobody else writes it in this launch and earlier launches are
-    // complete, so plain 16-byte loads do; only the stores of an SC1C tile must be write-through (its reader is another CU)
-    const long rowo = i0 + wm * 32 + 2 * l15;
-    v2d cpre[2][4];
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cpre[tj][q] = *(const v2d *)(g.C + rowo + (j0 + wn * 32 + 2 * (l4 + 4 * q) + tj) * g.ldc);
-    {
-        v2d ra[16], rb[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const long k = q * 8 + k_ld;
-            ra[q] = *(const v2d *)(Ap + k * g.lda);
-            rb[q] = *(const v2d *)(Bp + k * g.ldb);
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            *(v2d *)(la + (q * 8 + k_ld) * SB + 2 * rp) = ra[q];
-            *(v2d *)(lb + (q * 8 + k_ld) * SB + 2 * rp) = rb[q];
-        }
-    }
-    __syncthreads();
-    v4d acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
-    const double *pa = la + wm * 32 + 2 * l15, *pb = lb + wn * 32 + 2 * l15;
-#pragma unroll 8
-    for (int ks = 0; ks < 32; ++ks) {
-        const int kk = ks * 4 + l4;
-        const v2d fi = *(const v2d *)(pa + kk * SB);
-        const v2d fj = *(const v2d *)(pb + kk * SB);
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fj.x, fi.x, acc[0][0], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fj.x, fi.y, acc[1][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fj.y, fi.x, acc[0][1], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fj.y, fi.y, acc[1][1], 0, 0, 0);
-    }
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            double *cp = g.C + rowo + (j0 + wn * 32 + 2 * (l4 + 4 * q) + tj) * g.ldc;
-            v2d c = cpre[tj][q];
-            c += g.alpha * (v2d){acc[0][tj][q], acc[1][tj][q]};
-            if (SC1C) {
-                // one 16-byte write-through store (buffer store with the sc1 policy bit = agent scope)
-                typedef int v4i_t __attribute__((ext_vector_type(4)));
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)g.C, 0, 0x7fffffff, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i_t, c), rs, (int)((cp - g.C) * 8), 0, 16);
-            } else {
-                *(v2d *)cp = c;
-            }
-        }
-}
-
-// ---- the same K = 128 tile for a GROUP of four waves that shares its workgroup with another group (diag.hip: k_ldlt_panel,
-// where a TRSM strip or a second tile job lives in the other four waves of the workgroup): no s_barrier -- the hardware
+// ---- a 64x64 tile of C += alpha A B' with K = 128 for a GROUP of four waves that shares its workgroup with another group
+// (diag.hip: k_ldlt_panel, where a TRSM strip or a second tile job lives in the other four waves of the workgroup): no s_barrier -- the hardware
 // barrier counts every live wave of the workgroup -- but a generation-counted LDS word the group's four waves meet on.
 // LDS traffic of one wave is in order, so "my ds_writes have landed (lgkmcnt(0)), then my ds_add" is a release and the
 // spin's ds_read followed by dependent ds_reads an acquire; the asm memory clobbers keep the compiler from moving LDS
 // accesses across.  64 KB of LDS per group: the operands pass through two 32-KB buffers a QUARTER of K at a time (quarter
 // q + 1 is written while quarter q feeds the MFMAs; the wait that publishes it also says everybody is done with the buffer
-// quarter q + 2 goes into): four meetings per tile.  Same k order from a zero accumulator, same C + alpha acc: bit-identical
-// to gemm_tile_64_k128.
+// quarter q + 2 goes into): four meetings per tile.  Same k order from a zero accumulator, same C + alpha acc as the
+// accumulate epilogue of gemm_tile_64: bit-identical results.
 struct GrpBar { unsigned *ctr; unsigned gen; };
 __device__ __forceinline__ void grp_barrier(GrpBar &b) {
     b.gen += 4u;

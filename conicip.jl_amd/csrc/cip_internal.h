@@ -184,7 +184,7 @@ int cip_debug_chain_giveup_set(int n);    // test hook: the next n fused-chain f
 // graph replay with the chain form the graph was recorded with
 int cip_ldlt_debug_giveup(hipStream_t s, double *K, int Npad, long ld, const struct LdltWorkspace &ws, bool fused);
 bool cip_ldlt_last_factor_fused(void);    // did this thread's last cip_ldlt_factor enqueue (or record) a fused panel launch?
-int cip_ldlt_set_fused_chain(int on);     // 1 (default): diag + previous in-block update in one launch; returns the previous setting
+int cip_ldlt_set_fused_chain(int on);     // 3 (default): one launch per panel, 0: three; any other value only queries.  Returns the previous setting
 int cip_solve_block(int Npad);
 int cip_solve_block_max_set(int b);              // 128 | 256 | 512 | 1024 (0: query); returns the previous limit
 int cip_solve_fused_set(int mode);               // 0 (default): two launches per block step; 1: one (pre-multiplied neighbours) for solve blocks <= 512; 2: always; < 0: query.  Returns the previous mode
@@ -313,9 +313,25 @@ int cip_loop_corr(hipStream_t s, int n, int m, int p, const double *r0, const do
 int cip_loop_refine(hipStream_t s, int n, int m, int p, double *rk, const double *dz, const double *r, const double *lam,
                     const double *mb2, const double *mb3, const double *f, double *rIr);
 
+#ifdef __HIPCC__
+// ---- the bounded spin-wait of every in-launch wait (LDL' panel chain, grid barrier of the large S cones): poll done()
+// with s_sleep(SLEEP) between polls; after CIP_WAIT_TICKS of s_memtime (shader clock) give up instead of hanging the GPU --
+// the first give-up of a launch leaves its code in *flag (atomicCAS from 0) -- and return false.
+#define CIP_WAIT_TICKS 2000000000L
+#define CIP_GIVEUP_XWG (-9)          // a wait for other workgroups of the launch (global memory)
+#define CIP_GIVEUP_INWG (-8)         // a wait for other waves of the same workgroup (LDS phase counts)
+template <int SLEEP, class Done>
+__device__ __forceinline__ bool cip_bounded_wait(Done done, int *flag, int code) {
+    const long t0 = __builtin_amdgcn_s_memtime();
+    while (!done()) {
+        __builtin_amdgcn_s_sleep(SLEEP);
+        if (__builtin_amdgcn_s_memtime() - t0 > CIP_WAIT_TICKS) { atomicCAS(flag, 0, code); return false; }
+    }
+    return true;
+}
+
 // ---- wave-level sums without LDS permutes (DPP row operations + v_permlane16/32_swap): every lane ends with the same bits.
 // All lanes of the wave must be active.  (__shfl_xor is a ds_bpermute round trip per step: six dependent ones per 64-lane sum.)
-#ifdef __HIPCC__
 // sum over the 16 lanes of a DPP row, in every lane (xor 1, 2 as quad permutations, then the two mirrors)
 template <int CTRL>
 __device__ __forceinline__ double lz_dpp_add(double x) {

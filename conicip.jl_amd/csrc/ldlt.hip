@@ -30,14 +30,12 @@
 static std::atomic<int> g_nbo{0};         // read by the library's worker threads (batch.hip) while a caller may set it
 static std::atomic<int> g_fuse_diag{-1};
 static std::once_flag g_fuse_once;
-// 0: diag -> TRSM -> in-block update, three launches per panel; 1: the update inside the next diagonal kernel's launch
-// (k_ldlt_diag_upd); 3: one launch per panel, the TRSM pipelined behind the diagonal kernel (k_ldlt_panel)
-#define CIP_FUSE_DEFAULT 3
+// 3 (default; CIP_FUSE_DIAG: any value but 0): one launch per panel, the previous panel's in-block update and this panel's
+// TRSM pipelined behind the diagonal kernel (k_ldlt_panel); 0: diag -> TRSM -> in-block update, three launches per panel
 static void fuse_env(void) {
     std::call_once(g_fuse_once, [] {
         const char *e = getenv("CIP_FUSE_DIAG");
-        const int v = e ? atoi(e) : CIP_FUSE_DEFAULT;
-        g_fuse_diag = (v == 0) ? 0 : (v == 3) ? 3 : 1;
+        g_fuse_diag = (e && atoi(e) == 0) ? 0 : 3;
     });
 }
 int cip_ldlt_outer_block_for(int Npad) {
@@ -264,8 +262,6 @@ void cip_ldlt_ws_carve(void *base, int Npad, LdltWorkspace *ws, int fused) {
 // diag.hip
 int cip_launch_diag_v2(hipStream_t s, double *Kb, long ld, double *xm_out, double *dvec, double *dinv, int *info, int col0,
                        PivotSigns sg);
-int cip_launch_diag_upd(hipStream_t s, double *Kb, long ld, double *xm_out, double *dvec, double *dinv, int *info, int col0,
-                        PivotSigns sg, unsigned *ready, const GemmArgs &g);
 int cip_launch_diag_inverse(hipStream_t s, const double *K, long ld, int nblk, const double *xm_all, double *Linv,
                             double *LinvT, int Bs);
 int cip_launch_panel(hipStream_t s, double *Kb, long ld, double *xm_out, double *dvec, double *dinv, int *info, int col0,
@@ -292,8 +288,9 @@ static int update_rest_of_block(hipStream_t s, double *K, int Npad, long ld, dou
     if (!rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t, g)) return 0;
     return cip_launch_gemm(s, EPI_ACCUM, g);
 }
-// CIP_FUSE_DIAG=0 / cip_set_ldlt_fused_chain(0): the unfused chain (diag -> TRSM -> update per panel), for A/B runs and tests
-int cip_ldlt_set_fused_chain(int on) { fuse_env(); const int prev = g_fuse_diag; if (on == 0 || on == 1 || on == 3) g_fuse_diag = on; return prev; }
+// CIP_FUSE_DIAG=0 / cip_set_ldlt_fused_chain(0): the three-launch chain (diag -> TRSM -> update per panel), the give-up
+// fall-back and the bitwise reference of the fused one; 3 selects the fused chain, any other value only queries
+int cip_ldlt_set_fused_chain(int on) { fuse_env(); const int prev = g_fuse_diag; if (on == 0 || on == 3) g_fuse_diag = on; return prev; }
 
 // did the last factorisation this thread enqueued (or recorded) launch a panel with an in-launch wait? (the give-up hook, below)
 static thread_local bool tl_ran_fused = false;
@@ -308,11 +305,11 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
         const int jb = c0 / CIP_NB;
         const int r = Npad - c0 - CIP_NB;
         // MFMA micro-blocked diagonal kernel + substitution TRSM (the block inverses the solves
-        // need are produced by one batched launch after the factorisation).  From the second panel of the block on, the
-        // diagonal kernel's launch also carries the previous panel's in-block update (diag.hip: k_ldlt_diag_upd).
+        // need are produced by one batched launch after the factorisation).  Fused: one launch per panel, which from the second
+        // panel of the block on also carries the previous panel's in-block update (diag.hip: k_ldlt_panel).
         GemmArgs gu;
         fuse_env();
-        // fused when the chain has the chip to itself -- and in lock-step groups (grid.z = problems) while the group's
+        // fused when the chain has the chip to itself -- and in lock-step groups while the group's
         // long-lived workgroups (diagonal kernel, producers, strips: 10 + Npad / 64 per problem at the first panel) are no more
         // than about four rounds of the chip: order 2048, 8 / 16 / 24 problems 19.9 -> 17.8, 28.0 -> 26.5, 37.6 -> 37.1 ms per
         // pass against the three batched launches per panel, 32 problems equal, 64 problems 83 -> 86 (a big batch is
@@ -327,9 +324,9 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
             if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
             return 4 * cus;
         }();
-        const bool small_group = cip_in_batch() && g_fuse_diag == 3 && cip_tl_bz.B <= lsmax && (long)cip_tl_bz.B * (10 + Npad / 64) <= lscus;
+        const bool small_group = cip_in_batch() && cip_tl_bz.B <= lsmax && (long)cip_tl_bz.B * (10 + Npad / 64) <= lscus;
         const bool fuse = g_fuse_diag && !ws.unfused && (!cip_in_batch() || small_group);
-        if (fuse && g_fuse_diag == 3) {
+        if (fuse) {
             tl_ran_fused = true;
             const bool upd = t > 0 && rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t - 1, gu);
             unsigned *ctr = (unsigned *)(ws.info + 16);
@@ -339,19 +336,14 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
                 return rc;
             continue;
         }
-        if (fuse && t > 0 && rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t - 1, gu)) {
-            tl_ran_fused = true;
-            if ((rc = cip_launch_diag_upd(s, K + c0 + (long)c0 * ld, ld, ws.Xm + (size_t)jb * 2048, ws.dvec + c0, ws.dinv + c0,
-                                          ws.info, c0, ws.signs, (unsigned *)(ws.info + 16) + jb, gu)))
-                return rc;
-        } else if ((rc = cip_launch_diag_v2(s, K + c0 + (long)c0 * ld, ld, ws.Xm + (size_t)jb * 2048, ws.dvec + c0,
-                                            ws.dinv + c0, ws.info, c0, ws.signs)))
+        if ((rc = cip_launch_diag_v2(s, K + c0 + (long)c0 * ld, ld, ws.Xm + (size_t)jb * 2048, ws.dvec + c0,
+                                     ws.dinv + c0, ws.info, c0, ws.signs)))
             return rc;
         if ((rc = cip_launch_trsm_subst(s, K + (c0 + CIP_NB) + (long)c0 * ld, ld, r, K + c0 + (long)c0 * ld,
                                         ws.Xm + (size_t)jb * 2048, ws.dinv + c0,
                                         Wb + (c0 + CIP_NB) + (long)(t * CIP_NB) * Npad, Npad)))
             return rc;
-        if (!fuse && (rc = update_rest_of_block(s, K, Npad, ld, Wb, C0, wblk, t))) return rc;
+        if ((rc = update_rest_of_block(s, K, Npad, ld, Wb, C0, wblk, t))) return rc;
     }
     return 0;
 }
@@ -374,22 +366,6 @@ static int zero_fill(hipStream_t s, void *p, size_t bytes) {
     return 0;
 }
 
-// upper triangle <- (strictly lower triangle)': gives the forward sweep the same coalesced
-// "column-dot" access as the backward sweep (U[k, i] = L[i, k])
-__global__ __launch_bounds__(256) void k_mirror_lower(double *K, long ld, int bj0, CipBatch cb) {
-    CIP_BATCH_GUARD(cb);
-    CIP_BO1(cb, K);
-    __shared__ double t[32][33];
-    const int bi = blockIdx.x + bj0, bj = blockIdx.y + bj0;      // 32x32 tile (row tile bi, column tile bj), bi >= bj; bj0: first column tile of the range
-    if (bi < bj) return;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int q = 0; q < 32; q += 8) t[ty + q][tx] = K[(long)(bi * 32 + tx) + (long)(bj * 32 + ty + q) * ld];
-    __syncthreads();
-    for (int q = 0; q < 32; q += 8) {
-        const int r = bj * 32 + tx, c = bi * 32 + ty + q;          // destination (r, c) = source (c, r)
-        if (c > r) K[(long)r + (long)c * ld] = t[tx][ty + q];
-    }
-}
 // After the factorisation: inverses of the Bs x Bs unit-lower diagonal blocks by doubling,
 //   inv([L11 0; L21 L22]) = [X11 0; -X22 L21 X11  X22],
 // two batched MFMA GEMMs per level (Tt = X11' L21', then X21 = -X22 Tt' together with its transpose), so that a
@@ -461,8 +437,8 @@ static int build_solve_premul(hipStream_t s, double *K, long ld, const LdltWorks
     return 0;
 }
 
-// [J0, J1): the range of Bs-wide diagonal blocks to prepare (their columns are final), all of them by default.  The mirror
-// covers the same columns (every row below them).  Ranges are independent of each other (own slices of X / XT / Tt).
+// [J0, J1): the range of Bs-wide diagonal blocks to prepare (their columns are final), all of them by default.
+// Ranges are independent of each other (own slices of X / XT / Tt).
 static int build_solve_blocks(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws, int J0 = 0, int J1 = -1) {
     const int Bs = ws.Bs;
     if (J1 < 0) J1 = Npad / Bs;
@@ -473,13 +449,7 @@ static int build_solve_blocks(hipStream_t s, double *K, int Npad, long ld, const
     const int nbk = J1 - J0;
     if (nbk <= 0) return 0;
     int rc;
-    // (no mirror pass: L' is written with the factor, diag.hip: diag_store_panel_T / wave_store_T; CIP_LDLT_MIRROR=1 runs the
-    //  old pass on top of it -- it rewrites the same values -- for A/B timing)
-    static const int mirror_pass = [] { const char *e = getenv("CIP_LDLT_MIRROR"); return e ? atoi(e) : 0; }();
-    if (mirror_pass) {
-        const int bj0 = J0 * (Bs / 32), nct = nbk * (Bs / 32);
-        cip_launch_b(k_mirror_lower, dim3(Npad / 32 - bj0, nct), dim3(256), 0, s, K, ld, bj0);
-    }
+    // (no mirror pass: L' is written with the factor, diag.hip: wave_store_T)
     const int per = Bs / CIP_NB;
     const double *xm0 = ws.Xm + (size_t)J0 * per * 2048;
     const double *Kd = K + (long)J0 * Bs * (ld + 1);
@@ -516,7 +486,7 @@ static int build_solve_blocks(hipStream_t s, double *K, int Npad, long ld, const
     return build_solve_premul(s, K, ld, ws, Npad / Bs, J0, J1);
 }
 
-// ---- solve preparation BESIDE the panel chain (round 4).  The block inverses and the mirror image of columns that are
+// ---- solve preparation BESIDE the panel chain (round 4).  The block inverses of the solve blocks whose columns are
 // final do not depend on the rest of the factorisation, and at the bottom of the matrix the panel launches are a latency-
 // bound chain on a mostly idle chip.  When the last outer block is wide (>= 2 solve blocks begin or end in it) the
 // preparation of every solve block whose columns are final is enqueued on a SIDE stream: everything to the left of the
@@ -645,7 +615,7 @@ int cip_ldlt_debug_giveup(hipStream_t s, double *K, int Npad, long ld, const Ldl
     if (kind & 1) {
         cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 0, 1);
     } else {
-        cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 3, -9);
+        cip_launch_b(k_debug_set_word, dim3(1), dim3(64), 0, s, ws.info + 3, CIP_GIVEUP_XWG);
         if (g_debug_redo_pivot.load()) g_debug_redo_armed.store(1);
     }
     CIP_HIP_CHECK(hipGetLastError());

@@ -81,18 +81,15 @@ __device__ __forceinline__ double lg_ld(const double *p) { return __hip_atomic_l
 __device__ __forceinline__ void lg_st(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // grid barrier for the few workgroups of a cooperative launch (all resident: <= 16 workgroups): monotonic counter,
-// every thread drains its stores, one lane arrives and polls (`sc1` loads).  Bounded spin -> *err.
+// every thread drains its stores, one lane arrives and polls (`sc1` loads).  Bounded spin (cip_bounded_wait) -> *err.
 __device__ __forceinline__ void lg_grid_barrier(unsigned *ctr, unsigned nwg, unsigned &phase, int *err) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     ++phase;
     if (threadIdx.x == 0) {
         atomicAdd(ctr, 1u);
-        const long t0 = __builtin_amdgcn_s_memtime();
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nwg * phase) {
-            __builtin_amdgcn_s_sleep(1);
-            if (__builtin_amdgcn_s_memtime() - t0 > 2000000000L) { atomicExch(err, -9); break; }
-        }
+        cip_bounded_wait<1>([&] { return __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nwg * phase; }, err,
+                            CIP_GIVEUP_XWG);
     }
     __syncthreads();
 }

@@ -288,10 +288,10 @@ int cip_set_solve_fused(int mode);
  * cip_set_solve_block_max's value; CIP_LOCKSTEP_SOLVE_BLOCK overrides): a one-problem run with this limit
  * reproduces the call's iterates bit for bit */
 int cip_lockstep_solve_block_for(int B);
-/* panel chain of the serial schedule (also CIP_FUSE_DIAG): 3 (default) = one launch per 128-column panel -- diagonal kernel,
- * the previous panel's in-block update and this panel's TRSM, the TRSM following the diagonal kernel micro-panel by
- * micro-panel through a stage counter; 1 = diagonal kernel + previous panel's update in one launch, TRSM in its own;
- * 0 = three launches per panel.  Same factor bit for bit.  Process-wide; returns the previous setting (other values: query). */
+/* panel chain of the serial schedule (also CIP_FUSE_DIAG, where any value but 0 selects 3): 3 (default) = one launch per
+ * 128-column panel -- diagonal kernel, the previous panel's in-block update and this panel's TRSM, the TRSM following the
+ * diagonal kernel micro-panel by micro-panel through a stage counter; 0 = three launches per panel.  Same factor bit for bit.
+ * Process-wide; accepts 0 and 3, any other value only queries; returns the previous setting. */
 int cip_set_ldlt_fused_chain(int on);
 /* The fused panel chain waits INSIDE a launch for workgroups of the same launch (bounded: 2e9 ticks of the s_memtime counter, which
  * counts shader clock cycles -- about 0.8 s at the 2.4 GHz peak clock, longer at a lower clock -- then the factorisation reports

@@ -1,5 +1,5 @@
-"""The in-launch hand-offs of the blocked LDL's panel chain (diag.hip: k_ldlt_panel, k_ldlt_diag_upd).  Inside those
-launches workgroups hand blocks of K to each other through device-memory counters, write-through stores and agent-scope
+"""The in-launch hand-offs of the blocked LDL's panel chain (diag.hip: k_ldlt_panel).  Inside those launches
+workgroups hand blocks of K to each other through device-memory counters, write-through stores and agent-scope
 loads -- so the test that matters is a BIT-FOR-BIT comparison with the three-launch chain running the same arithmetic: a
 single stale read anywhere changes bits.  Repeated, under a concurrent memory-streaming load, and -- for the default
 schedule -- thousands of times (the opt-in look-ahead schedules of rounds 1-2, whose bit-identity test had to be softened
@@ -40,16 +40,15 @@ def _spd(N, seed, quasi=0):
     return K.contiguous()                       # symmetric: row-major == column-major
 
 
-@pytest.mark.parametrize("mode", [1, 3], ids=["diag+update", "one-launch-panel"])
+@pytest.mark.parametrize("mode", [3], ids=["one-launch-panel"])
 @pytest.mark.parametrize("N,quasi", [(128, 0), (256, 0), (384, 38), (896, 0), (1024, 0), (2048, 0), (4608, 512), (8192, 0)])
 def test_fused_panel_chain_bitwise_equals_unfused(lib, N, quasi, mode):
-    """Mode 1: from the second panel of an outer block on, the diagonal kernel's launch carries the previous panel's in-block
-    update and waits, INSIDE the launch, for the three tiles that are its own block (diag.hip: k_ldlt_diag_upd).  Same
-    arithmetic in the same order as the three-launch chain: identical bits -- also repeated under a concurrent 1-GiB copy
-    load, which is when a missing fence or a stale line would show.  Mode 3: that launch also carries the panel's TRSM,
+    """Mode 3: from the second panel of an outer block on, the diagonal kernel's launch carries the previous panel's in-block
+    update and waits, INSIDE the launch, for the tiles that are its own block; the launch also carries the panel's TRSM,
     which follows the diagonal kernel micro-panel by micro-panel through agent-scope stores, loads and a stage counter
-    (diag.hip: k_ldlt_panel) -- same bar.  The small orders are the launch shapes without strips (one block), without
-    update tiles (last panel of an outer block) and with a single strip."""
+    (diag.hip: k_ldlt_panel).  Same arithmetic in the same order as the three-launch chain: identical bits -- also repeated
+    under a concurrent 1-GiB copy load, which is when a missing fence or a stale line would show.  The small orders are the
+    launch shapes without strips (one block), without update tiles (last panel of an outer block) and with a single strip."""
     from cipkkt import _lib as L
     nbytes = C.c_size_t()
     L.check(lib.cip_ldlt_workspace_bytes(N, C.byref(nbytes)))
@@ -276,8 +275,8 @@ def test_late_helper_stores_of_the_diagonal_kernel_do_not_change_the_factor(tmp_
     stores took a microsecond longer than usual: about one factorisation of order 4096 in 100 000 had a few 64-row strips of one panel
     computed from the previous contents of column block 6 (tests/test_gpu_driver.py::test_dense_qp_2048_properties failed once in a few
     dozen suite runs; profiles/r6/stage_count_defect.txt).  A test build of the library (-DDIAG_DEBUG_SLOW_HELPERS: the helpers' write-back
-    of micro-panel 6 held back) must produce the regular build's bits; the same delay on the old counting (-DDIAG_OLD_STAGE_COUNT)
-    is what tools/stage_mix_demo.sh shows going wrong."""
+    of micro-panel 6 held back) must produce the regular build's bits; the same delay on the old counting turned it over on every
+    factorisation (the stage word)."""
     import shutil
     import subprocess
     import sys
