@@ -70,6 +70,10 @@ SIGNATURES = {
     "cip_solve3x3_dev": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "cip_solve2x2": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4),
     "cip_solve2x2_dev": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4),
+    "cip_solve3x3_many": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "cip_solve3x3_many_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "cip_solve2x2_many": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "cip_solve2x2_many_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "cip_solve4x4_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cip_apply_F_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cip_cone_prod_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -102,6 +106,9 @@ SIGNATURES = {
     "cip_ldlt_workspace_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "cip_ldlt_factor_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_int_p]),
     "cip_ldlt_solve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cip_ldlt_solve_many_scratch_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "cip_ldlt_solve_many_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int]),
     "cip_gemm_nt_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "cip_kkt_order": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),

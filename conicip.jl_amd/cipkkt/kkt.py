@@ -230,6 +230,42 @@ class KKTSystem:
         L.check(self.lib.cip_solve2x2(self.h, _ptr(y), _ptr(w), _ptr(dy), _ptr(dw)))
         return dy, dw
 
+    # ---------------------------------------------------------------- many right-hand sides for one factor
+    def _cols(self, M, rows, k):
+        M = np.asarray(M, dtype=np.float64)
+        if M.ndim == 1:
+            M = M.reshape(rows, -1)
+        if M.shape != (rows, k):
+            raise ValueError("cipkkt: expected a (%d, %d) block, got %s" % (rows, k, M.shape))
+        return np.asfortranarray(M)
+
+    def solve3x3_many(self, X, Y, Z):
+        """solve3x3 for k right-hand sides at once: X (n, k), Y (p, k), Z (m, k) host arrays; returns fresh (n, k), (p, k), (m, k)."""
+        k = np.asarray(X).shape[1] if np.asarray(X).ndim == 2 else 1
+        X, Y, Z = self._cols(X, self.n, k), self._cols(Y, self.p, k), self._cols(Z, self.m, k)
+        A, B, Cm = (np.empty((r, k), order="F") for r in (self.n, self.p, self.m))
+        L.check(self.lib.cip_solve3x3_many(self.h, k, _ptr(X), _ptr(Y), _ptr(Z), _ptr(A), _ptr(B), _ptr(Cm)))
+        return A, B, Cm
+
+    def solve2x2_many(self, Y, W):
+        """solve2x2 for k right-hand sides at once: Y (n, k), W (p, k) host arrays; returns fresh (n, k), (p, k)."""
+        k = np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 1
+        Y, W = self._cols(Y, self.n, k), self._cols(W, self.p, k)
+        DY, DW = np.empty((self.n, k), order="F"), np.empty((self.p, k), order="F")
+        L.check(self.lib.cip_solve2x2_many(self.h, k, _ptr(Y), _ptr(W), _ptr(DY), _ptr(DW)))
+        return DY, DW
+
+    def solve3x3_many_dev(self, X, Y, Z, A, B, Cm):
+        """Device twin of solve3x3_many: contiguous torch tensors holding one right-hand side per ROW -- X (k, n), Y (k, p), Z (k, m)
+        and the outputs A (k, n), B (k, p), Cm (k, m) -- which is the column-major (n, k) ... layout of the C ABI.  Cm may be Z."""
+        k = X.shape[0]
+        L.check(self.lib.cip_solve3x3_many_dev(self.h, k, _ptr(X), _ptr(Y), _ptr(Z), _ptr(A), _ptr(B), _ptr(Cm)))
+
+    def solve2x2_many_dev(self, Y, W, DY, DW):
+        """Device twin of solve2x2_many: Y (k, n), W (k, p), DY (k, n), DW (k, p) contiguous torch tensors, one right-hand side per row."""
+        k = Y.shape[0]
+        L.check(self.lib.cip_solve2x2_many_dev(self.h, k, _ptr(Y), _ptr(W), _ptr(DY), _ptr(DW)))
+
     def solve2x2_dev(self, y, w, dy, dw):
         L.check(self.lib.cip_solve2x2_dev(self.h, _ptr(y), _ptr(w), _ptr(dy), _ptr(dw)))
 

@@ -94,7 +94,7 @@ static void free_all(cip_handle *h) {
     if (h->cs.lg) { cip_sdp_large_destroy(h->cs.lg); h->cs.lg = nullptr; }
     void *ptrs[] = {h->cs.d_bigq, h->cs.d_ritems, h->cs.d_packq, h->cs.d_sidx_small, h->cs.d_sidx, h->cs.d_sdpws, h->cs.d_sdpvec, h->cs.d_sdpflag, h->Q, h->symv_ws, h->A, h->At, h->A_rp, h->A_ci, h->A_v, h->T_rp, h->T_ci, h->T_v, h->kdiag, h->row_cone, h->G, h->Gt,
                     h->cs.d_cones, h->cs.d_items, h->cs.d_scal, h->cs.d_partial, h->cs.d_scalar, h->K, h->Wt, h->syrk_ws, h->Gm, h->AtS, h->WtS,
-                    h->ws_base, h->rhs, h->mt1, h->mt2, h->mt3, h->nt1, h->pt1, h->dot_scratch, h->dot_ptrs, h->stage, h->drv, h->ref, h->c2x2};
+                    h->ws_base, h->rhs, h->mt1, h->mt2, h->mt3, h->nt1, h->pt1, h->dot_scratch, h->dot_ptrs, h->stage, h->drv, h->ref, h->c2x2, h->many, h->many_stage};
     for (void *p : ptrs)
         if (p && !in_arena(h, p)) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -968,6 +968,154 @@ extern "C" int cip_solve2x2(cip_handle *h, const double *y, const double *w, dou
     return 0;
 }
 
+// ------------------------------------------------------------------ many right-hand sides (level 3)
+// X n x nrhs, Y p x nrhs, Z m x nrhs (col-major, ld = rows); the same as nrhs calls of the single entry point, 64 columns at a time:
+// the cone operations and the CSR products per column, the dense A / A' products and the LDL' sweeps over all columns of a chunk
+// (solve_many.hip).  Regularised factor: nrhs refined single solves.
+#define CIP_MANY_CHUNK 64
+static int many_buffers(cip_handle *h) {
+    if (h->many) return 0;
+    DMALLOC(h->many, sizeof(double) * CIP_MANY_CHUNK * ((size_t)h->Npad + 2 * (size_t)h->m + (size_t)h->ws.Bs));
+    return 0;
+}
+// kc <= 64 columns of solve3x3_once (z == NULL: the 2x2 form of the Schur route); c may alias z
+static int solve3x3_chunk(cip_handle *h, int kc, const double *x, const double *y, const double *z, double *a, double *b, double *c) {
+    hipStream_t s = h->stream;
+    const int n = h->n, p = h->p, N = h->N, Npad = h->Npad;
+    const int m = z ? h->m : 0;
+    const long ldr = Npad;
+    double *R = h->many, *T = R + (size_t)CIP_MANY_CHUNK * Npad, *U = T + (size_t)CIP_MANY_CHUNK * h->m;
+    double *S = U + (size_t)CIP_MANY_CHUNK * h->m;
+    int rc;
+    if (h->route == CIP_ROUTE_SCHUR) {
+        // t = (F'F)^-1 z ; [S G'; G 0][a; b] = [x + A't; y] ; c = t - (F'F)^-1 A a
+        for (int j = 0; j < kc && m > 0; ++j)
+            if ((rc = apply_FtF_inv(h, z + (long)j * m, h->mt2, T + (long)j * m))) return rc;
+        if ((rc = cip_block_copy(s, n, kc, 1.0, x, n, nullptr, R, ldr))) return rc;
+        if (m > 0) {
+            if (h->A_sparse) {
+                for (int j = 0; j < kc; ++j)
+                    if ((rc = cip_spmv_csr(s, n, h->T_rp, h->T_ci, h->T_v, 1.0, T + (long)j * m, 1.0, R + j * ldr))) return rc;
+            } else if ((rc = cip_gemm_tn(s, n, kc, m, 1.0, h->A, m, T, m, 1.0, R, ldr))) {
+                return rc;
+            }
+        }
+        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, y, p, nullptr, R + n, ldr))) return rc;
+        if (Npad > N && (rc = cip_block_copy(s, Npad - N, kc, 0.0, nullptr, 0, nullptr, R + N, ldr))) return rc;
+        if ((rc = cip_ldlt_solve_many(s, h->K, Npad, h->ldk, h->ws, S, R, ldr, kc, false))) return rc;
+        if ((rc = cip_block_copy(s, n, kc, 1.0, R, ldr, nullptr, a, n))) return rc;
+        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, R + n, ldr, nullptr, b, p))) return rc;
+        if (m > 0) {
+            if (h->A_sparse) {
+                for (int j = 0; j < kc; ++j)
+                    if ((rc = cip_spmv_csr(s, m, h->A_rp, h->A_ci, h->A_v, 1.0, R + j * ldr, 0.0, U + (long)j * m))) return rc;
+            } else if ((rc = cip_gemm_tn(s, m, kc, n, 1.0, h->At, h->npad, R, ldr, 0.0, U, m))) {
+                return rc;
+            }
+            for (int j = 0; j < kc; ++j)
+                if ((rc = apply_FtF_inv(h, U + (long)j * m, h->mt2, U + (long)j * m))) return rc;
+            if ((rc = cip_axpby(s, m * kc, 1.0, T, 0.0, c))) return rc;
+            if ((rc = cip_axpby(s, m * kc, -1.0, U, 1.0, c))) return rc;
+        }
+    } else {
+        // [-F'F -A 0; -A' Q G'; 0 G 0] [c; a; b] = [-z; x; y]
+        if (m > 0 && (rc = cip_block_copy(s, m, kc, -1.0, z, m, nullptr, R, ldr))) return rc;
+        if ((rc = cip_block_copy(s, n, kc, 1.0, x, n, nullptr, R + m, ldr))) return rc;
+        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, y, p, nullptr, R + m + n, ldr))) return rc;
+        if (Npad > N && (rc = cip_block_copy(s, Npad - N, kc, 0.0, nullptr, 0, nullptr, R + N, ldr))) return rc;
+        if ((rc = cip_ldlt_solve_many(s, h->K, Npad, h->ldk, h->ws, S, R, ldr, kc, false))) return rc;
+        if (m > 0 && (rc = cip_block_copy(s, m, kc, 1.0, R, ldr, nullptr, c, m))) return rc;
+        if ((rc = cip_block_copy(s, n, kc, 1.0, R + m, ldr, nullptr, a, n))) return rc;
+        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, R + m + n, ldr, nullptr, b, p))) return rc;
+    }
+    return 0;
+}
+// two2: the 2x2 form (y, w -> dy, dw; z, c unused).  one_is_single: nrhs == 1 is the single entry point (its bits)
+static int solve_many_impl(cip_handle *h, bool two2, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
+                           double *C, bool one_is_single) {
+    const int n = h->n, m = h->m, p = h->p;
+    if (nrhs == 1 && one_is_single) return two2 ? cip_solve2x2_dev(h, X, Y, A, Bo) : cip_solve3x3_dev(h, X, Y, Z, A, Bo, C);
+    const char *who = two2 ? "cip_solve2x2_many" : "cip_solve3x3_many";
+    if (!h->factored) { cip_set_error("%s: no factorisation (call cip_factor first)", who); return CIP_E_NOTFACTORED; }
+    int rc;
+    if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
+    if (h->reg_rel > 0.0 && (!two2 || m > 0)) {
+        // regularised factor: the refinement against the true operator runs per column, through the single path
+        for (int j = 0; j < nrhs; ++j) {
+            rc = two2 ? cip_solve2x2_dev(h, X + (long)j * n, Y + (long)j * p, A + (long)j * n, Bo + (long)j * p)
+                      : cip_solve3x3_dev(h, X + (long)j * n, Y + (long)j * p, Z + (long)j * m, A + (long)j * n, Bo + (long)j * p,
+                                         C + (long)j * m);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    if (h->info_pending) h->spec_solves += nrhs;
+    h->n_solve += nrhs;
+    if ((rc = many_buffers(h))) return rc;
+    CipRange rg(two2 ? "cip:solve2x2_many" : "cip:solve3x3_many");
+    for (int c0 = 0; c0 < nrhs; c0 += CIP_MANY_CHUNK) {
+        const int kc = nrhs - c0 < CIP_MANY_CHUNK ? nrhs - c0 : CIP_MANY_CHUNK;
+        if ((rc = solve3x3_chunk(h, kc, X + (long)c0 * n, Y + (long)c0 * p, two2 ? nullptr : Z + (long)c0 * m, A + (long)c0 * n,
+                                 Bo + (long)c0 * p, two2 ? nullptr : C + (long)c0 * m)))
+            return rc;
+    }
+    return 0;
+}
+static bool many_args_ok(const cip_handle *h, bool two2, int nrhs, const void *X, const void *Y, const void *Z, const void *A,
+                         const void *Bo, const void *C) {
+    if (!h || nrhs < 0) return false;
+    if (nrhs == 0) return true;
+    return X && A && (h->p == 0 || (Y && Bo)) && (two2 || h->m == 0 || (Z && C));
+}
+// host staging of the host-pointer calls: chunk by chunk through h->many_stage (2 x (n + p + m) x 64 doubles)
+static int solve_many_host(cip_handle *h, bool two2, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
+                           double *C) {
+    hipStream_t s = h->stream;
+    const int n = h->n, p = h->p, m = two2 ? 0 : h->m;
+    const size_t col = (size_t)n + p + h->m;
+    if (!h->many_stage) DMALLOC(h->many_stage, sizeof(double) * 2 * col * CIP_MANY_CHUNK);
+    for (int c0 = 0; c0 < nrhs; c0 += CIP_MANY_CHUNK) {
+        const int kc = nrhs - c0 < CIP_MANY_CHUNK ? nrhs - c0 : CIP_MANY_CHUNK;
+        double *xi = h->many_stage, *yi = xi + (size_t)n * kc, *zi = yi + (size_t)p * kc;
+        double *ao = h->many_stage + col * CIP_MANY_CHUNK, *bo = ao + (size_t)n * kc, *co = bo + (size_t)p * kc;
+        CIP_HIP_CHECK(hipMemcpyAsync(xi, X + (size_t)c0 * n, sizeof(double) * n * kc, hipMemcpyHostToDevice, s));
+        if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(yi, Y + (size_t)c0 * p, sizeof(double) * p * kc, hipMemcpyHostToDevice, s));
+        if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(zi, Z + (size_t)c0 * m, sizeof(double) * m * kc, hipMemcpyHostToDevice, s));
+        int rc;
+        if (h->factored && (rc = factor_resolve(h, true))) return rc;      // this entry point is synchronous anyway
+        if ((rc = solve_many_impl(h, two2, kc, xi, yi, zi, ao, bo, co, nrhs == 1))) return rc;
+        CIP_HIP_CHECK(hipMemcpyAsync(A + (size_t)c0 * n, ao, sizeof(double) * n * kc, hipMemcpyDeviceToHost, s));
+        if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(Bo + (size_t)c0 * p, bo, sizeof(double) * p * kc, hipMemcpyDeviceToHost, s));
+        if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(C + (size_t)c0 * m, co, sizeof(double) * m * kc, hipMemcpyDeviceToHost, s));
+        CIP_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+extern "C" int cip_solve3x3_many_dev(cip_handle *h, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
+                                     double *C) {
+    if (!many_args_ok(h, false, nrhs, X, Y, Z, A, Bo, C)) { cip_set_error("cip_solve3x3_many_dev: bad argument"); return CIP_E_INVALID; }
+    if (nrhs == 0) return 0;
+    return solve_many_impl(h, false, nrhs, X, Y, Z, A, Bo, C, true);
+}
+extern "C" int cip_solve3x3_many(cip_handle *h, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
+                                 double *C) {
+    if (!many_args_ok(h, false, nrhs, X, Y, Z, A, Bo, C)) { cip_set_error("cip_solve3x3_many: bad argument"); return CIP_E_INVALID; }
+    if (nrhs == 0) return 0;
+    return solve_many_host(h, false, nrhs, X, Y, Z, A, Bo, C);
+}
+extern "C" int cip_solve2x2_many_dev(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW) {
+    if (!many_args_ok(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr)) { cip_set_error("cip_solve2x2_many_dev: bad argument"); return CIP_E_INVALID; }
+    if (nrhs == 0) return 0;
+    if (h->route != CIP_ROUTE_SCHUR) { cip_set_error("cip_solve2x2_many: needs the Schur route"); return CIP_E_UNSUPPORTED; }
+    return solve_many_impl(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr, true);
+}
+extern "C" int cip_solve2x2_many(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW) {
+    if (!many_args_ok(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr)) { cip_set_error("cip_solve2x2_many: bad argument"); return CIP_E_INVALID; }
+    if (nrhs == 0) return 0;
+    if (h->route != CIP_ROUTE_SCHUR) { cip_set_error("cip_solve2x2_many: needs the Schur route"); return CIP_E_UNSUPPORTED; }
+    return solve_many_host(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr);
+}
+
 // diag F (the packed scaling) when the cone set is R cones only -- the native loops then fuse the cone operations of their
 // element-wise chains into the vector kernels (vecops.hip: k_loop_*); NULL otherwise (or with CIP_LOOP_FUSED_R=0)
 const double *cip_loop_all_r(cip_handle *h) {
@@ -1125,6 +1273,25 @@ extern "C" int cip_ldlt_solve_dev(void *stream, const double *K, int N, int ld, 
     LdltWorkspace ws{};
     cip_ldlt_ws_carve((void *)workspace, N, &ws, cip_ldlt_fused_for(N));   // same mode as at the factorisation: cip_set_solve_fused must not change between a factor and its solves
     return cip_ldlt_solve((hipStream_t)stream, K, N, ld, ws, rhs);
+}
+// scratch of cip_ldlt_solve_many_dev: the widest solve block any setting of the solve-block limit gives this order x min(nrhs, 64)
+extern "C" int cip_ldlt_solve_many_scratch_bytes(int N, int nrhs, size_t *bytes) {
+    if (N <= 0 || N % CIP_NB || nrhs < 0 || !bytes) { cip_set_error("N must be a positive multiple of 128, nrhs >= 0"); return CIP_E_INVALID; }
+    *bytes = sizeof(double) * (size_t)cip_ldlt_solve_many_scratch_block(N) * (size_t)(nrhs < 64 ? nrhs : 64);
+    return 0;
+}
+extern "C" int cip_ldlt_solve_many_dev(void *stream, const double *K, int N, int ld, const void *workspace, void *scratch, double *B,
+                                       int ldb, int nrhs) {
+    if (!ldlt_dims_ok(K, N, ld, workspace) || nrhs < 0 || ldb < N) {
+        cip_set_error("cip_ldlt_solve_many_dev: bad argument (K, workspace non-NULL; N > 0 and ld >= N multiples of 128; nrhs >= 0; "
+                      "ldb >= N)");
+        return CIP_E_INVALID;
+    }
+    if (nrhs == 0) return 0;
+    if (!B || !scratch) { cip_set_error("cip_ldlt_solve_many_dev: B and scratch must be non-NULL"); return CIP_E_INVALID; }
+    LdltWorkspace ws{};
+    cip_ldlt_ws_carve((void *)workspace, N, &ws, cip_ldlt_fused_for(N));
+    return cip_ldlt_solve_many((hipStream_t)stream, K, N, ld, ws, (double *)scratch, B, ldb, nrhs, true);
 }
 extern "C" int cip_gemm_nt_dev(void *stream, int M, int N, int K, double alpha, const double *A, int lda, const double *B,
                                int ldb, double *C, int ldc, int lower_only) {

@@ -81,6 +81,9 @@ struct cip_handle {
     double *stage = nullptr;        // device staging for the host-pointer entry points: 2*(n+p+m) doubles
     double *ref = nullptr;          // right-hand side / residual / correction of the refinement inside solve3x3 (regularised factor only)
     double *c2x2 = nullptr;         // m-vector: discarded third component of a regularised 2x2 solve
+    // many right-hand sides (cip_solve3x3_many*), allocated on first use, sized for chunks of 64 columns: the Npad x 64 right-hand
+    // side block, two m x 64 blocks (t, u of the Schur route), the Bs x 64 scratch of the sweeps; host staging of the host-pointer calls
+    double *many = nullptr, *many_stage = nullptr;
     double *drv = nullptr;          // vectors of the native interior-point loop (cip_conicip), allocated on first use
 
     // ---- hipGraphs of the two launch-bound inner loops of small systems (opt-in, CIP_GRAPH=1; api.hip: graph_run)

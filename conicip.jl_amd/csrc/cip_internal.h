@@ -194,6 +194,17 @@ size_t cip_ldlt_ws_bytes(int Npad, int fused);     // fused: 1 / 0 = with / with
 void cip_ldlt_ws_carve(void *base, int Npad, LdltWorkspace *ws, int fused);   // fused as passed to cip_ldlt_ws_bytes by the same owner (0 / 1)
 int cip_ldlt_factor(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws);
 int cip_ldlt_solve(hipStream_t s, const double *K, int Npad, long ld, const LdltWorkspace &ws, double *rhs);
+// many right-hand sides (solve_many.hip): B (Npad x k, ld ldb) in place; scratch: cip_ldlt_solve_many_scratch_block(Npad) x min(k, 64)
+// doubles.  k == 1 and one_is_single: cip_ldlt_solve
+int cip_ldlt_solve_many_scratch_block(int Npad);
+int cip_ldlt_solve_many(hipStream_t s, const double *K, int Npad, long ld, const LdltWorkspace &ws, double *scratch, double *B, long ldb,
+                        int k, bool one_is_single);
+// C[M x k] = alpha A' B + beta C  (A: Kr x M, B: Kr x k, C: M x k, col-major; beta == 0: C is not read), fp64 MFMA, deterministic with
+// column-independent bits
+int cip_gemm_tn(hipStream_t s, int M, int k, int Kr, double alpha, const double *A, long lda, const double *B, long ldb,
+                double beta, double *C, long ldc);
+// dst = alpha src .* d (per row; d == NULL: 1; src == NULL: 0), rows x cols blocks
+int cip_block_copy(hipStream_t s, int rows, int cols, double alpha, const double *src, long lds, const double *d, double *dst, long ldd);
 int cip_ldlt_outer_block(void);          // the knob: 0 = automatic
 int cip_ldlt_outer_block_for(int Npad);  // NBO a factorisation of this order uses
 void cip_ldlt_set_outer_block(int nbo);

@@ -149,6 +149,20 @@ int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y, const doub
 int cip_solve2x2(cip_handle *h, const double *y, const double *w, double *dy, double *dw);      /* host pointers */
 int cip_solve2x2_dev(cip_handle *h, const double *y, const double *w, double *dy, double *dw);  /* device pointers */
 
+/* ---- many right-hand sides for one factor: nrhs calls of solve3x3 / solve2x2 in one.  Blocks are column-major with the
+ * leading dimension = their row count: X n x nrhs, Y p x nrhs, Z m x nrhs (A, Bo, C likewise; for solve2x2 Y n x nrhs,
+ * W p x nrhs).  The factor is resolved, the calls are speculative and return CIP_E_RETRY, n_solve grows (by nrhs) and C may
+ * alias Z exactly as for the single calls; nrhs == 1 gives the single call's bits.  The dense A / A' products and the LDL'
+ * sweeps run over 64 columns at a time (L read once per sweep for all of them); a regularised factor is refined per column.
+ * nrhs < 0, or a NULL block the single call needs (X, A; Y, Bo when p > 0; Z, C when m > 0): CIP_E_INVALID before anything
+ * is enqueued; nrhs == 0: no-op.  cip_solve2x2_many*: CIP_E_UNSUPPORTED on the full-3x3 route. */
+int cip_solve3x3_many(cip_handle *h, int nrhs, const double *X, const double *Y, const double *Z,
+                      double *A, double *Bo, double *C);                 /* host pointers */
+int cip_solve3x3_many_dev(cip_handle *h, int nrhs, const double *X, const double *Y, const double *Z,
+                          double *A, double *Bo, double *C);             /* device pointers */
+int cip_solve2x2_many(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW);      /* host */
+int cip_solve2x2_many_dev(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW);  /* device */
+
 /* ---- the 4x4 -> 3x3 reduction of solve4x4 (src/ConicIP.jl:684-692), device pointers.
  * r and dz are 4-block vectors (y[n], w[p], v[m], s[m]) stored contiguously. */
 int cip_solve4x4_dev(cip_handle *h, const double *lambda, const double *r, double *dz);
@@ -259,6 +273,14 @@ int cip_conicip_many(cip_handle *const *handles, int count, const double *const 
 int cip_ldlt_workspace_bytes(int N, size_t *bytes);
 int cip_ldlt_factor_dev(void *hip_stream, double *K, int N, int ld, void *workspace, int *info_host);
 int cip_ldlt_solve_dev(void *hip_stream, const double *K, int N, int ld, const void *workspace, double *rhs);
+/* nrhs right-hand sides at once: B is N x nrhs (leading dimension ldb >= N), solved in place; rows N..ldb-1 are never touched.
+ * scratch: device memory of cip_ldlt_solve_many_scratch_bytes(N, nrhs) bytes (at most 64 columns' worth, whatever nrhs).
+ * Same rules as cip_ldlt_solve_dev, plus nrhs >= 0, ldb >= N, and B, scratch non-NULL when nrhs > 0 -- else CIP_E_INVALID
+ * before anything is enqueued; nrhs == 0: no-op.  nrhs == 1 is cip_ldlt_solve_dev (same bits); otherwise every column gets the
+ * same bits whatever nrhs and the other columns are (fp64 MFMA products, fixed reduction order). */
+int cip_ldlt_solve_many_scratch_bytes(int N, int nrhs, size_t *bytes);
+int cip_ldlt_solve_many_dev(void *hip_stream, const double *K, int N, int ld, const void *workspace,
+                            void *scratch, double *B, int ldb, int nrhs);
 /* C(lower or full) += alpha * A * B'   (A: M x K, B: N x K, all column-major; M,N % 128 == 0, K % 16 == 0, K > 0;
  * lda >= M, ldb >= N, ldc >= M; A, B, C non-NULL; lower_only needs M == N and leaves the 128 x 128 tiles above the diagonal
  * untouched -- else CIP_E_INVALID before anything is enqueued) */

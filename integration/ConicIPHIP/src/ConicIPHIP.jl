@@ -29,7 +29,7 @@ using Libdl
 using LinearAlgebra
 using SparseArrays
 
-export kktsolver_hip, kktsolver_hip_full3x3, kktsolver_2x2_hip, CIP_ROUTE_SCHUR, CIP_ROUTE_FULL3X3
+export kktsolver_hip, kktsolver_hip_full3x3, kktsolver_2x2_hip, solve3x3_many, CIP_ROUTE_SCHUR, CIP_ROUTE_FULL3X3
 export conicIP_hip, conicIP_hip_batch, preprocess_conicIP_hip, CipOptions, CipResult
 
 const _libpath = Ref{String}("")
@@ -112,16 +112,41 @@ function kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_SCHUR)
         packed = _pack_scaling(F, F⁻ᵀ, cone_dims)
         _cipcheck(ccall(_sym(:cip_set_scaling_packed), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, packed))
         _cipcheck(ccall(_sym(:cip_factor), Cint, (Ptr{Cvoid},), h.ptr))   # asynchronous; cip_solve3x3 resolves it
-        function solve3x3(x, y, z)                                            # level 3
-            a, b, c = zeros(n), zeros(p), zeros(m)    # fresh, Julia-owned (they become fields of z / Δz, ConicIP.jl:690)
-            _cipcheck(ccall(_sym(:cip_solve3x3), Cint,
-                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-                h.ptr, Vector{Float64}(x), Vector{Float64}(y), Vector{Float64}(z), a, b, c))
-            return (a, b, c)
-        end
-        return solve3x3
+        return HIPSolve3x3(h, n, m, p)                                       # level 3: callable, solve3x3(x, y, z)
     end
     return solve3x3gen
+end
+
+# what level 2 returns: `L(x, y, z)` is one solve, `solve3x3_many(L, X, Y, Z)` many right-hand sides for the same factor
+struct HIPSolve3x3
+    h::CipHandle
+    n::Int
+    m::Int
+    p::Int
+end
+function (L::HIPSolve3x3)(x, y, z)
+    a, b, c = zeros(L.n), zeros(L.p), zeros(L.m)    # fresh, Julia-owned (they become fields of z / Δz, ConicIP.jl:690)
+    _cipcheck(ccall(_sym(:cip_solve3x3), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        L.h.ptr, Vector{Float64}(x), Vector{Float64}(y), Vector{Float64}(z), a, b, c))
+    return (a, b, c)
+end
+
+"""
+    solve3x3_many(L, X, Y, Z) -> (A, B, C)
+
+Columns of X (n x k), Y (p x k), Z (m x k) are k right-hand sides of the level-3 solve `L` returned by `solve3x3gen(F, F⁻ᵀ)`:
+column j of (A, B, C) is `L(X[:, j], Y[:, j], Z[:, j])` (sensitivity directions, scenarios, blocks of K⁻¹).  One call of
+cip_solve3x3_many: the factor is read once per sweep for up to 64 columns.
+"""
+function solve3x3_many(L::HIPSolve3x3, X::AbstractMatrix, Y::AbstractMatrix, Z::AbstractMatrix)
+    k = size(X, 2)
+    (size(X) == (L.n, k) && size(Y) == (L.p, k) && size(Z) == (L.m, k)) || throw(DimensionMismatch("solve3x3_many: block sizes"))
+    A, B, C = zeros(L.n, k), zeros(L.p, k), zeros(L.m, k)
+    _cipcheck(ccall(_sym(:cip_solve3x3_many), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        L.h.ptr, k, Matrix{Float64}(X), Matrix{Float64}(Y), Matrix{Float64}(Z), A, B, C))
+    return (A, B, C)
 end
 
 # level 1 for whatever the user passed as A (the reference's tests use Matrix, SparseMatrixCSC and Diagonal / Id(n),
