@@ -417,3 +417,48 @@ def test_lockstep_against_the_oracle():
         for f in ("y", "w", "v"):
             a, bb = getattr(got, f), np.asarray(getattr(ref, f)).reshape(-1)
             assert np.linalg.norm(a - bb) <= 1e-6 * (1.0 + np.linalg.norm(bb)), f
+
+
+def _splitk_problem(n, m, seed):
+    """dense-A R-cone QP, strictly feasible at y = 0 (b = -1); n = 1000, m = 4100 reaches the split-K Schur formation
+    (npad 1024, mpad 4112: 9 slices, gemm_f64.hip cip_syrk_split)"""
+    rng = np.random.default_rng(seed)
+    M = rng.standard_normal((n, n))
+    Q = M @ M.T / n + 0.1 * np.eye(n)
+    A = rng.standard_normal((m, n)) / np.sqrt(n)
+    return dict(Q=Q, c=rng.standard_normal(n), A=A, b=-np.ones(m), cone_dims=[("R", m)], G=None, d=None,
+                kwargs=dict(maxIters=5))
+
+
+def test_split_k_schur_formation_in_lockstep():
+    """three problems whose Schur formation takes the split-K form: the per-problem offsets of the split-K images
+    (k_syrk_splitk_64 and k_syrk_reduce: blockIdx.z / bz * stride) against the thread-pool path, bit for bit"""
+    prs = [_splitk_problem(1000, 4100, 900 + i) for i in range(3)]
+    one = _solve(prs, "threads", in_flight=1)
+    lock = _solve(prs, "lockstep")
+    _assert_identical(lock, one)
+    assert all(s.Iter == 5 or s.status == "Optimal" for s in one)
+
+
+def test_csr_group_with_more_than_16_q_cones():
+    """CSR A with 18 Q cones (nqpad = 32: the rank-nq update of the Schur block over two k-tiles) in one group"""
+    n = 60
+    cone_dims = [("R", 20)] + [("Q", 4)] * 18
+    m = sum(k for _, k in cone_dims)
+    rng = np.random.default_rng(950)
+    mask = rng.random((m, n)) < 0.3                # one pattern: the non-zero count is part of a group's shape
+    mask[np.arange(m), rng.integers(0, n, m)] = True
+    prs = []
+    for i in range(3):
+        rng = np.random.default_rng(951 + i)
+        A = np.where(mask, rng.standard_normal((m, n)) + 3.0 * np.sign(rng.standard_normal((m, n))), 0.0)
+        b = np.zeros(m)
+        b[:20] = -1.0
+        b[20::4] = -1.0                            # Q-cone heads: y = 0 is strictly feasible
+        M = rng.standard_normal((n, n))
+        prs.append(dict(Q=M @ M.T / n + 0.1 * np.eye(n), c=rng.standard_normal(n), A=sp.csr_matrix(A), b=b,
+                        cone_dims=cone_dims, G=None, d=None, kwargs={}))
+    one = _solve(prs, "threads", in_flight=1)
+    lock = _solve(prs, "lockstep")
+    assert all(s.status == "Optimal" for s in one), [s.status for s in one]
+    _assert_identical(lock, one)
