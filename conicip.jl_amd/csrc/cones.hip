@@ -351,18 +351,24 @@ __global__ __launch_bounds__(256) void k_maxstep(const ConeDesc *cones, const Wo
     const int tid = threadIdx.x;
     const double INF = __builtin_inf();
     if (cd.type == CIP_CONE_R) {
+        // Julia's min / minimum propagate NaN (:219, :238), fmin drops it: a NaN is flagged beside the fmin reduction, as
+        // in k_min_reduce, so the NaN-free minima keep their bits
         double mn = INF;
+        int nan_seen = 0;
         if (d) {                                                   // maxstep_rp :212-225
             for (int e = it.start + tid; e < it.start + it.len; e += 256) {
                 const double de = d[cd.off + e] * scale;
-                if (de > 0) mn = fmin(mn, x[cd.off + e] / de);
+                if (de > 0) { const double q = x[cd.off + e] / de; if (q != q) nan_seen = 1; else mn = fmin(mn, q); }
             }
-            mn = block_min(mn, sh);
         } else {                                                   // :227-240
-            for (int e = it.start + tid; e < it.start + it.len; e += 256) mn = fmin(mn, x[cd.off + e]);
-            mn = block_min(mn, sh);
-            mn = (mn > 0) ? 0.0 : -1.0 + mn;
+            for (int e = it.start + tid; e < it.start + it.len; e += 256) {
+                const double xe = x[cd.off + e];
+                if (xe != xe) nan_seen = 1; else mn = fmin(mn, xe);
+            }
         }
+        mn = block_min(mn, sh);
+        if (__syncthreads_or(nan_seen)) mn = __builtin_nan("");
+        if (!d) mn = (mn > 0) ? 0.0 : -1.0 + mn;
         if (tid == 0) partial[it.slot] = mn;
     } else if (cd.type == CIP_CONE_Q) {
         const QTeam tm = q_team(cones, it, cd);
