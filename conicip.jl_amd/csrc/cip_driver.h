@@ -1,10 +1,12 @@
-// Host-side pieces shared by the two native interior-point loops (driver.hip: one problem; lockstep.hip: a lock-step
-// batch): the vector layout of the loop inside one device allocation, and the per-iteration scalar logic of
-// src/ConicIP.jl:756-873 (residuals, best-iterate bookkeeping, objective values, stopping tests, certificates).
+// The native interior-point loop (driver.hip), written once for B problems under a batch mask: cip_conicip runs it for one
+// problem, a lock-step group (lockstep.hip) for B.  Here: the vector layout of the loop inside one device allocation, the
+// per-iteration scalar logic of src/ConicIP.jl:756-873 (residuals, best-iterate bookkeeping, objective values, stopping tests,
+// certificates) and the loop itself (Loop).
 #pragma once
 #include "cip_handle.h"
 #include "../../include/cipkkt.h"
 #include <cmath>
+#include <vector>
 
 namespace cipdrv {
 
@@ -50,7 +52,7 @@ inline Norms host_norms(int n, int m, int p, const double *c, const double *b, c
     return nm;
 }
 
-// the 16 dot products one iteration reads back, in this order (driver.hip / lockstep.hip fill the pointer tables alike)
+// the 16 dot products one iteration reads back, in this order (driver.hip: Loop::run fills the pointer tables)
 struct IterDots { double v[16]; };
 
 struct IterOutcome {
@@ -150,5 +152,32 @@ inline double cone_degree(const cip_handle *h) {      // conedim (:547-552)
     for (const ConeDesc &cd : h->h_cones) conedim += cd.type == CIP_CONE_R ? cd.dim : (cd.type == CIP_CONE_Q ? 1 : cd.r);
     return conedim;
 }
+
+inline unsigned long long full_mask(int B) { return B >= 64 ? ~0ull : ((1ull << B) - 1ull); }
+
+// The iteration of src/ConicIP.jl:704-936 -- initial point, predictor, corrector, refinement, step, final status -- for the B problems
+// of the calling thread's batch context, every step one launch for all of them (driver.hip: Loop::run).  Per-problem host state is
+// problem-major, as cip_dots returns it; problem z takes part in a launch while bit z of `active` is set.  What a factorisation's
+// pivot flags lead to is the caller's policy: in-loop regularisation and :Error for one problem (driver.hip: cip_conicip), leaving
+// the group for a lock-step group (lockstep.hip).
+struct Loop {
+    cip_handle *h;                          // problem 0's handle (a group's other problems: the same pointers + z * stride)
+    int B;
+    unsigned long long active;              // problems still iterating
+    std::vector<IterOutcome> outcome;       // final status of every problem, and what its certificate does to the iterate
+    std::vector<int> n_factor, n_solve;
+    int iters = 0;
+    Vectors V;                              // carved out of h->drv; V.z holds every problem's last iterate when run() returns
+    Loop(cip_handle *h_, int B_) : h(h_), B(B_), active(full_mask(B_)), outcome(B_), n_factor(B_, 0), n_solve(B_, 0) {}
+    virtual ~Loop() = default;
+    // c, b, d: problem z's data (host).  Fills res[z] but for wall_s; the caller downloads V.z and applies the certificates.
+    int run(const double *const *c, const double *const *b, const double *const *d, const cip_options &o, cip_result *res,
+            double *trace, int trace_cap);
+
+  protected:
+    virtual int factor() = 0;                  // enqueue assembly + LDL' of the active problems (:737 -> :682)
+    virtual int ride_pivots() = 0;             // enqueue what brings their pivot flags back with the next read-back
+    virtual int take_pivots(bool fresh) = 0;   // act on the flags (fresh: a read-back has just returned); problems that stop leave `active`
+};
 
 }   // namespace cipdrv

@@ -488,8 +488,9 @@ int cip_cones_div(hipStream_t s, const ConeSet &cs, const double *x, const doubl
     return 0;
 }
 // defer_slot >= 0 (lock-step batches only): the minima go to slot `defer_slot` of every problem's row of the gather buffer and
-// the call returns without a read-back -- they ride on the NEXT read-back of that buffer (lockstep.hip pairs the v- and
-// s-side max-steps and the dot products that follow them: one host round trip instead of three); alpha_host is not touched
+// the call returns without a read-back -- they ride on the NEXT read-back of that buffer (the interior-point loop, driver.hip,
+// pairs the v- and s-side max-steps and the dot products that follow them: one host round trip instead of three); alpha_host is
+// not touched
 int cip_cones_maxstep(hipStream_t s, const ConeSet &cs, const double *x, const double *d, double scale, double *alpha_host, int defer_slot) {
     if (cs.nitems == 0) { if (alpha_host) for (int z = 0; z < (cip_tl_bz.B > 1 ? cip_tl_bz.B : 1); ++z) alpha_host[z] = __builtin_inf(); return 0; }
     if (!alpha_host && !(cip_tl_bz.B > 1 && defer_slot >= 0)) { cip_set_error("cip_cones_maxstep: no destination for the minimum"); return CIP_E_INVALID; }

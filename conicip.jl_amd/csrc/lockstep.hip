@@ -13,9 +13,10 @@
 // pointers are problem 0's + z * stride (cip_handle_alloc).  The library's host code then runs ONCE, on problem 0's
 // handle, under a thread-local batch context (cip_internal.h: cip_launch_b appends {stride, mask} to every launch and
 // multiplies grid.z by B; kernels shift their pointer arguments and drop out when their problem's mask bit is clear).
-// The kernels, their grids in x / y and their arithmetic are those of the one-problem path: results are bit-identical
-// to cip_conicip on each problem (tests/test_gpu_lockstep.py).  Per-problem control flow is the mask: problems that have
-// reached a final status stop taking part; the refinement loop runs on the subset that still needs it.  A problem whose
+// The iteration is cip_conicip's own (driver.hip: Loop::run); the kernels, their grids in x / y and their arithmetic are
+// those of the one-problem path: results are bit-identical to cip_conicip on each problem (tests/test_gpu_lockstep.py).
+// Per-problem control flow is the mask: problems that have reached a final status stop taking part; the refinement loop
+// runs on the subset that still needs it.  What differs is the policy on pivot flags (GroupLoop below): a problem whose
 // factorisation meets a bad pivot (it would switch to the regularised factorisation: LPs, singular Q with free
 // variables) is taken out of the lock-step group and solved afterwards by cip_conicip on its own handle.
 //
@@ -53,7 +54,6 @@ struct BatchScope {           // activates the batch context for the calling thr
 #ifndef CIP_LOCKSTEP_SPLIT_DEFAULT
 #define CIP_LOCKSTEP_SPLIT_DEFAULT 2        // (round 6, measured: see cip_conicip_lockstep)
 #endif
-#define STEP_SLOT 40            // deferred max-step minima (cones.hip: cip_cones_maxstep with a defer slot)
 __global__ void k_gather_info(const int *info, double *gather, CipBatch cb) {
     CIP_BATCH_GUARD(cb);
     CIP_BO1(cb, info);
@@ -143,7 +143,48 @@ struct Group {
 };
 
 thread_local int g_last_stats[3] = {0, 0, 0};      // groups, problems, problems that left their group (last call of this thread)
-unsigned long long full_mask(int B) { return B >= 64 ? ~0ull : ((1ull << B) - 1ull); }
+
+// The group's policy on pivot flags: assembly + LDL' of every problem of the mask, the four flag words of each problem copied
+// into its row of the gather buffer (they ride on the next read-back, normally the dots'), and the problems that met a bad
+// pivot or whose fused panel chain gave up an in-launch wait taken out of the group (ejected: solved alone afterwards)
+struct GroupLoop final : Loop {
+    Group &G;
+    std::vector<char> ejected;
+    explicit GroupLoop(Group &g) : Loop(g.h[0], g.B), G(g), ejected(g.B, 0) {}
+    int factor() override {
+        int rc;
+        h->assembled = h->factored = false;
+        h->reg_rel = 0.0;
+        if ((rc = cip_assemble(h, true))) return rc;
+        if ((rc = cip_ldlt_factor(h->stream, h->K, h->Npad, h->ldk, h->ws))) return rc;
+        h->factored = true; h->info_pending = false;
+        return 0;
+    }
+    int ride_pivots() override {       // (under the mask the factorisation ran under)
+        cip_launch_b(k_gather_info, dim3(1), dim3(64), 0, h->stream, (const int *)h->ws.info, G.gather_dev);
+        CIP_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    int take_pivots(bool fresh) override {
+        // (a group of ONE problem is no batch for the kernels: its dot products do not go through the gather buffer)
+        if (!fresh || !cip_in_batch()) {
+            CIP_HIP_CHECK(hipMemcpyAsync(G.gather_host, G.gather_dev, sizeof(double) * (size_t)B * CIP_GATHER, hipMemcpyDeviceToHost, h->stream));
+            const int rcw = cip_wait(h->stream);
+            if (rcw) return rcw;
+        }
+        for (int z = 0; z < B; ++z) {
+            if (!((active >> z) & 1ull)) continue;
+            const double *gi = G.gather_host + (size_t)z * CIP_GATHER + INFO_SLOT;
+            if (gi[1] != 0.0) { cip_set_error("LDL': a triangular sweep bailed out (problem %d)", z); return CIP_E_HIP; }
+            // gi[3]: an in-launch wait of the fused panel launch gave up -- a GPU shared with other processes can keep a launch's
+            // workgroups off the chip for longer than the bound.  The problem leaves the group like one with a bad pivot and is
+            // solved alone afterwards, on the three-launch chain (no in-launch wait, same bits)
+            if (gi[3] != 0.0) { G.h[z]->ws.unfused = 1; G.h[z]->n_chain_fallbacks += 1; h->ws.unfused = 1; }      // (h: the group's launches follow problem 0's workspace -- three launches per panel from here on)
+            if (gi[0] != 0.0 || gi[3] != 0.0) { ejected[z] = 1; active &= ~(1ull << z); }
+        }
+        return 0;
+    }
+};
 
 }   // namespace
 
@@ -230,270 +271,16 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
         }
     }
     t_create = since();
-    cip_handle *h = G.h[0];
     hipStream_t s = G.stream;
-    const int NT = n + p + 2 * m;
-    Vectors V;
-    V.carve(h->drv, n, m, p);
-    double *c_d = V.c_d, *b_d = V.b_d, *d_d = V.d_d;
-    Vec4 &zv = V.z, &r0 = V.r0, &rleft = V.rleft, &r = V.r, &daff = V.daff, &dz = V.dz, &dzr = V.dzr, &rIr = V.rIr, &rkkt = V.rkkt;
-    double *e = V.e, *lam = V.lam, *mb1 = V.mb1, *mb2 = V.mb2, *mb3 = V.mb3;
-    double *Qy = V.Qy, *pinf = V.pinf, *Ays = V.Ays, *Gy = V.Gy;
-    const double conedim = cone_degree(h);
-    const double *f = cip_loop_all_r(h);                   // diag F of problem 0 (the kernels shift it per problem) when every cone is an R cone
-
-    // ---- per-problem host state
-    std::vector<Norms> nm(B);
-    std::vector<double> optBest(B, INFINITY);
-    std::vector<int> n_factor(B, 0), n_solve(B, 0);
-    std::vector<IterOutcome> outcome(B);
-    std::vector<char> ejected(B, 0);
-    for (int z = 0; z < B; ++z) {
-        res[z] = cip_result{};
-        res[z].prFeas = res[z].duFeas = res[z].muFeas = INFINITY; res[z].pobj = INFINITY; res[z].dobj = -INFINITY;
-        nm[z] = host_norms(n, m, p, c[z], m > 0 ? b[z] : nullptr, p > 0 ? d[z] : nullptr);
-    }
-
     CipBatchCtx ctx = {B, (long)G.stride, full_mask(B), G.gather_dev, G.gather_host};
     BatchScope scope(ctx);
-    unsigned long long active = full_mask(B);
-    auto set_mask = [&](unsigned long long mk) { cip_tl_bz.mask = mk; };
-#define CK(x) do { if ((rc = (x)) != 0) return rc; } while (0)
-    auto axpby = [&](int len, double alpha, const double *x, double beta, double *yy) { return len > 0 ? cip_axpby(s, len, alpha, x, beta, yy) : 0; };
-    auto copy = [&](int len, const double *x, double *yy) { return axpby(len, 1.0, x, 0.0, yy); };
-    // assembly + LDL' of every problem of the current mask; the pivot flags come back with the next read-back
-    auto factor = [&]() -> int {
-        int e2;
-        h->reg_rel = 0.0;
-        if ((e2 = cip_assemble(h, true))) return e2;
-        if ((e2 = cip_ldlt_factor(s, h->K, h->Npad, h->ldk, h->ws))) return e2;
-        h->factored = true; h->info_pending = false;
-        for (int z = 0; z < B; ++z) if ((cip_tl_bz.mask >> z) & 1ull) ++n_factor[z];
-        return 0;
-    };
-    // pivot flags of the last factorisation: gather_info enqueues their copy into the gather buffer (launched under the mask
-    // the factorisation ran under; the words then ride on the next read-back of that buffer, normally the dots'), and
-    // eject_bad_pivots takes the problems that met a bad pivot out of the group (read_back: fetch the buffer itself)
-    auto gather_info = [&]() -> int {
-        cip_launch_b(k_gather_info, dim3(1), dim3(64), 0, s, (const int *)h->ws.info, G.gather_dev);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
-    };
-    auto eject_bad_pivots = [&](bool read_back, unsigned long long fmask) -> int {
-        if (read_back) {
-            CIP_HIP_CHECK(hipMemcpyAsync(G.gather_host, G.gather_dev, gather_bytes, hipMemcpyDeviceToHost, s));
-            { const int rcw = cip_wait(s); if (rcw) return rcw; }
-        }
-        for (int z = 0; z < B; ++z) {
-            if (!((fmask >> z) & 1ull)) continue;
-            const double *gi = G.gather_host + (size_t)z * CIP_GATHER + INFO_SLOT;
-            if (gi[1] != 0.0) { cip_set_error("LDL': a triangular sweep bailed out (problem %d)", z); return CIP_E_HIP; }
-            // gi[3]: an in-launch wait of the fused panel launch gave up -- a GPU shared with other processes can keep a launch's
-            // workgroups off the chip for longer than the bound.  The problem leaves the group like one with a bad pivot and is
-            // solved alone afterwards, on the three-launch chain (no in-launch wait, same bits)
-            if (gi[3] != 0.0) { G.h[z]->ws.unfused = 1; G.h[z]->n_chain_fallbacks += 1; h->ws.unfused = 1; }      // (h: the group's launches follow problem 0's workspace -- three launches per panel from here on)
-            if (gi[0] != 0.0 || gi[3] != 0.0) { ejected[z] = 1; active &= ~(1ull << z); }
-        }
-        return 0;
-    };
-    std::vector<double> av(B), as(B), tmpB(B);
-    // A max-step whose minima ride on the next read-back of the gather buffer (slot `slot` of every problem's row).  A group of
-    // ONE problem is not a batch for the kernels (cip_tl_bz.B == 1: no gather buffer behind k_min_reduce), so it takes the
-    // one-problem read-back and `direct[0]` holds the result on return; fetch_step() is then a no-op for that slot.
-    auto maxstep_deferred = [&](const double *x, const double *dd, double scale, int slot, double *direct) -> int {
-        if (B == 1) return cip_cones_maxstep(s, h->cs, x, dd, scale, direct);
-        return cip_cones_maxstep(s, h->cs, x, dd, scale, nullptr, slot);
-    };
-    auto fetch_step = [&](int slot, std::vector<double> &dst) {
-        if (B == 1) return;
-        for (int z = 0; z < B; ++z) dst[z] = G.gather_host[(size_t)z * CIP_GATHER + slot];
-    };
-
-    // ---------------------------------------------------------------- initial point (:704-713)
-    CK(cip_zero(s, (long)driver_doubles(n, m, p), h->drv));
-    // the right-hand sides: problem z's vectors are problem 0's addresses + z * stride
-    for (int z = 0; z < B; ++z) {
-        const size_t off = G.stride * (size_t)z;
-        CIP_HIP_CHECK(hipMemcpyAsync((char *)c_d + off, c[z], sizeof(double) * n, hipMemcpyHostToDevice, s));
-        if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync((char *)b_d + off, b[z], sizeof(double) * m, hipMemcpyHostToDevice, s));
-        if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync((char *)d_d + off, d[z], sizeof(double) * p, hipMemcpyHostToDevice, s));
-    }
-    if (m > 0) CK(cip_cones_identity(s, h->cs, e));
-    set_mask(active);
-    CK(cip_set_scaling_identity(h));
-    CK(factor());
-    CK(copy(n, c_d, r0.y)); CK(copy(p, d_d, r0.w)); CK(copy(m, b_d, r0.v));
-    if (m > 0) CK(cip_zero(s, m, r0.s));
-    CK(gather_info());
-    CK(eject_bad_pivots(true, active));
-    set_mask(active);
-    if (active) {
-        CK(cip_solve4x4_dev(h, e, r0.base, zv.base));
-        for (int z = 0; z < B; ++z) if ((active >> z) & 1ull) ++n_solve[z];
-        if (m > 0) {
-            CK(maxstep_deferred(zv.v, nullptr, 1.0, STEP_SLOT, av.data()));
-            CK(cip_cones_maxstep(s, h->cs, zv.s, nullptr, 1.0, as.data()));
-            fetch_step(STEP_SLOT, av);
-            for (int z = 0; z < B; ++z) { av[z] = -av[z]; as[z] = -as[z]; }
-            CK(cip_axpby_ps(s, m, av.data(), e, 1.0, zv.v));
-            CK(cip_axpby_ps(s, m, as.data(), e, 1.0, zv.s));
-        }
-    }
-
-    std::vector<double> dt((size_t)B * 16), q4((size_t)B * 4), n2((size_t)B * 4), sigma(B), mu(B), mubar(B), alpha(B);
-    int Iter = 1;
-    for (; Iter <= o.maxIters && active; ++Iter) {                                         // :730
-        set_mask(active);
-        if (m > 0) CK(cip_cones_nt_scaling(s, h->cs, zv.v, zv.s, lam));                    // :732-735
-        h->assembled = h->factored = false;
-        CK(factor());                                                                      // :737 -> :682
-        const unsigned long long factored_mask = active;
-        // (round 5: the element-wise chains are the one-problem loop's fused kernels, driver.hip / vecops.hip: k_loop_*)
-        if (m > 0 && !f) CK(cip_cones_prod(s, h->cs, lam, lam, rleft.s));                  // :746
-        CK(cip_gemv_dev(h, CIP_MAT_Q, 0, 1.0, zv.y, 0.0, Qy));
-        CK(copy(n, Qy, rleft.y));                                                          // :747-750
-        if (p > 0) {
-            CK(cip_gemv_dev(h, CIP_MAT_G, 1, 1.0, zv.w, 1.0, rleft.y));
-            CK(cip_gemv_dev(h, CIP_MAT_G, 0, 1.0, zv.y, 0.0, rleft.w));
-            CK(cip_gemv_dev(h, CIP_MAT_G, 1, 1.0, zv.w, 0.0, pinf));
-        }
-        if (m > 0) {
-            CK(cip_gemv_dev(h, CIP_MAT_A, 1, -1.0, zv.v, 1.0, rleft.y));
-            CK(cip_gemv_dev(h, CIP_MAT_A, 0, 1.0, zv.y, 0.0, rleft.v));
-            CK(cip_gemv_dev(h, CIP_MAT_A, 1, -1.0, zv.v, p > 0 ? 1.0 : 0.0, pinf));
-        } else if (p == 0) CK(cip_zero(s, n, pinf));
-        CK(cip_loop_resid(s, n, m, p, rleft.base, zv.s, c_d, d_d, b_d, lam, f, r0.base, Gy, Ays));       // :753
-        const double *px[16] = {zv.v, c_d, r0.y, r0.v, r0.s, zv.y, zv.w, zv.v, d_d, b_d, pinf, zv.y, zv.v, Ays, Gy, Qy};
-        const double *py[16] = {zv.s, zv.y, r0.y, r0.v, r0.s, Qy, r0.w, r0.v, zv.w, zv.v, pinf, zv.y, zv.v, Ays, Gy, Qy};
-        const int ln[16] = {m, n, n, m, m, n, p, m, p, m, n, n, m, m, p, n};
-        CK(gather_info());                    // same mask as the factorisation; rides on the dots' read-back
-        CK(cip_dots(s, 16, px, py, ln, h->dot_scratch, h->dot_ptrs, dt.data()));
-        if (B == 1) CK(eject_bad_pivots(true, factored_mask));      // a group of one takes the one-problem read-back path
-        else CK(eject_bad_pivots(false, factored_mask));
-        for (int z = 0; z < B; ++z) {
-            if (!((active >> z) & 1ull)) continue;
-            IterDots dd;
-            for (int i = 0; i < 16; ++i) dd.v[i] = dt[(size_t)z * 16 + i];
-            outcome[z] = evaluate_iteration(dd, nm[z], conedim, m, p, o, Iter, &res[z], optBest[z], nullptr);
-            mu[z] = outcome[z].mu; mubar[z] = outcome[z].mubar;
-            if (outcome[z].status != CIP_STATUS_NONE) { res[z].status = outcome[z].status; active &= ~(1ull << z); }
-        }
-        if (!active) break;
-        set_mask(active);
-
-        // ------------------------------------------------------------ predictor (:879-887)
-        CK(cip_solve4x4_dev(h, lam, r0.base, daff.base));
-        for (int z = 0; z < B; ++z) if ((active >> z) & 1ull) ++n_solve[z];
-        for (int z = 0; z < B; ++z) sigma[z] = 0.0;
-        if (m > 0) {
-            // one host round trip for the three results (round 4; it was three): the two max-steps leave their minima in slots
-            // STEP_SLOT, STEP_SLOT + 1 of the gather buffer, which comes back with the dot products
-            CK(maxstep_deferred(zv.v, daff.v, 1.0, STEP_SLOT, av.data()));
-            CK(maxstep_deferred(zv.s, daff.s, 1.0, STEP_SLOT + 1, as.data()));
-            const double *qx[4] = {zv.v, zv.v, daff.v, daff.v};
-            const double *qy[4] = {zv.s, daff.s, zv.s, daff.s};
-            const int ql[4] = {m, m, m, m};
-            CK(cip_dots(s, 4, qx, qy, ql, h->dot_scratch, h->dot_ptrs, q4.data()));
-            fetch_step(STEP_SLOT, av);
-            fetch_step(STEP_SLOT + 1, as);
-            for (int z = 0; z < B; ++z) {
-                if (!((active >> z) & 1ull)) continue;
-                const double a_aff = std::fmin(std::fmin(av[z], 1.0), as[z]);
-                const double *q = &q4[(size_t)z * 4];
-                const double rho = (q[0] - a_aff * q[1] - a_aff * q[2] + a_aff * a_aff * q[3]) / mubar[z];   // fts :162-163, :886
-                const double cl = std::fmax(0.0, std::fmin(1.0, rho));
-                sigma[z] = std::pow(cl, 3.0);
-            }
-        }
-
-        // ------------------------------------------------------------ corrector (:893-901)
-        if (m > 0 && !f) {
-            CK(cip_cones_apply(s, h->cs, CIP_OP_FINVT, daff.s, mb1));
-            CK(cip_cones_apply(s, h->cs, CIP_OP_F, daff.v, mb2));
-            CK(cip_cones_prod(s, h->cs, mb1, mb2, mb3));
-        }
-        if (m > 0) {
-            for (int z = 0; z < B; ++z) tmpB[z] = sigma[z] * mu[z];
-            CK(cip_loop_corr(s, n, m, p, r0.base, daff.base, mb3, e, f, tmpB.data(), r.base));
-        } else CK(copy(NT, r0.base, r.base));
-
-        // ------------------------------------------------------------ Newton step + refinement (:907-921)
-        CK(cip_solve4x4_dev(h, lam, r.base, dz.base));
-        for (int z = 0; z < B; ++z) if ((active >> z) & 1ull) ++n_solve[z];
-        unsigned long long refine = active;
-        bool step_known = false;
-        for (int it = 0; it < o.maxRefinementSteps && refine; ++it) {
-            set_mask(refine);
-            CK(cip_gemv_dev(h, CIP_MAT_Q, 0, 1.0, dz.y, 0.0, rkkt.y));
-            if (p > 0) {
-                CK(cip_gemv_dev(h, CIP_MAT_G, 1, 1.0, dz.w, 1.0, rkkt.y));
-                CK(cip_gemv_dev(h, CIP_MAT_G, 0, 1.0, dz.y, 0.0, rkkt.w));
-            }
-            if (m > 0) {
-                CK(cip_gemv_dev(h, CIP_MAT_A, 1, -1.0, dz.v, 1.0, rkkt.y));
-                CK(cip_gemv_dev(h, CIP_MAT_A, 0, 1.0, dz.y, 0.0, rkkt.v));
-                if (!f) {
-                    CK(cip_cones_apply(s, h->cs, CIP_OP_F, dz.v, mb1));
-                    CK(cip_cones_prod(s, h->cs, lam, mb1, mb2));
-                    CK(cip_cones_apply(s, h->cs, CIP_OP_FINVT, dz.s, mb1));
-                    CK(cip_cones_prod(s, h->cs, lam, mb1, mb3));
-                }
-            }
-            CK(cip_loop_refine(s, n, m, p, rkkt.base, dz.base, r.base, lam, mb2, mb3, f, rIr.base));
-            const double *nx[4] = {rIr.y, rIr.w, rIr.v, rIr.s};
-            const int nl[4] = {n, p, m, m};
-            // the step's two max-steps ride on this read-back (first pass only): when no problem asks for refinement -- the usual
-            // case -- dz is final and the iteration has saved a host round trip; otherwise they are taken again behind the loop
-            static const int spec_on = [] { const char *e = getenv("CIP_LOCKSTEP_SPEC_STEP"); return e ? atoi(e) : 1; }();
-            const bool spec = spec_on && it == 0 && m > 0 && B > 1;
-            if (spec) {
-                CK(cip_cones_maxstep(s, h->cs, zv.v, dz.v, 1.0 / (1.0 - o.DTB), nullptr, STEP_SLOT));
-                CK(cip_cones_maxstep(s, h->cs, zv.s, dz.s, 1.0 / (1.0 - o.DTB), nullptr, STEP_SLOT + 1));
-            }
-            CK(cip_dots(s, 4, nx, nx, nl, h->dot_scratch, h->dot_ptrs, n2.data()));
-            for (int z = 0; z < B; ++z) {
-                if (!((refine >> z) & 1ull)) continue;
-                const double *q = &n2[(size_t)z * 4];
-                const double rnorm = (nrm(q[0]) + (p > 0 ? nrm(q[1]) : 0.0) + (m > 0 ? nrm(q[2]) + nrm(q[3]) : 0.0)) / (n + 2 * m);   // :917
-                if (rnorm < o.refinementThreshold) refine &= ~(1ull << z);
-            }
-            if (spec && !refine) {
-                for (int z = 0; z < B; ++z) {
-                    av[z] = G.gather_host[(size_t)z * CIP_GATHER + STEP_SLOT];
-                    as[z] = G.gather_host[(size_t)z * CIP_GATHER + STEP_SLOT + 1];
-                }
-                step_known = true;
-            }
-            if (!refine) break;
-            set_mask(refine);
-            CK(cip_solve4x4_dev(h, lam, rIr.base, dzr.base));
-            for (int z = 0; z < B; ++z) if ((refine >> z) & 1ull) ++n_solve[z];
-            CK(axpby(NT, 1.0, dzr.base, 1.0, dz.base));                                    // :920
-        }
-        set_mask(active);
-
-        // ------------------------------------------------------------ step (:927-932)
-        for (int z = 0; z < B; ++z) alpha[z] = 1.0;
-        if (m > 0) {
-            if (!step_known) {
-                // (one round trip for the pair: the v side rides on the s side's read-back)
-                CK(maxstep_deferred(zv.v, dz.v, 1.0 / (1.0 - o.DTB), STEP_SLOT, av.data()));
-                CK(cip_cones_maxstep(s, h->cs, zv.s, dz.s, 1.0 / (1.0 - o.DTB), as.data()));
-                fetch_step(STEP_SLOT, av);
-            }
-            for (int z = 0; z < B; ++z) alpha[z] = std::fmin(std::fmin(av[z], 1.0), std::fmin(as[z], 1.0));
-        }
-        for (int z = 0; z < B; ++z) tmpB[z] = -alpha[z];
-        CK(cip_axpby_ps(s, NT, tmpB.data(), dz.base, 1.0, zv.base));
-    }
-    // problems still active ran out of iterations (:936)
-    for (int z = 0; z < B; ++z)
-        if ((active >> z) & 1ull) { res[z].status = CIP_STATUS_ABANDONED; outcome[z] = IterOutcome{}; outcome[z].status = CIP_STATUS_ABANDONED; }
-
+    GroupLoop L(G);
+    if ((rc = L.run(c, b, d, o, res, nullptr, 0))) return rc;
     if (timing) { (void)hipStreamSynchronize(s); t_loop = since(); }
     // ---- results of the lock-step problems
+    const Vec4 &zv = L.V.z;
     for (int z = 0; z < B; ++z) {
-        if (ejected[z]) continue;
+        if (L.ejected[z]) continue;
         const size_t off = G.stride * (size_t)z;
         CIP_HIP_CHECK(hipMemcpyAsync(y[z], (char *)zv.y + off, sizeof(double) * n, hipMemcpyDeviceToHost, s));
         if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(w[z], (char *)zv.w + off, sizeof(double) * p, hipMemcpyDeviceToHost, s));
@@ -503,22 +290,20 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     if (timing)
         fprintf(stderr, "lockstep group B=%d n=%d: probe %.2f ms, arena %.2f, create %.2f, loop %.2f (%d iterations), download %.2f; slab %.1f MB\n",
-                B, n, t_probe, t_arena - t_probe, t_create - t_arena, t_loop - t_create, Iter, 1e3 * wall - t_loop, G.stride / 1048576.0);
+                B, n, t_probe, t_arena - t_probe, t_create - t_arena, t_loop - t_create, L.iters, 1e3 * wall - t_loop, G.stride / 1048576.0);
     for (int z = 0; z < B; ++z) {
-        if (ejected[z]) continue;
-        apply_certificate(outcome[z], n, m, p, y[z], p > 0 ? w[z] : nullptr, m > 0 ? v[z] : nullptr);
-        res[z].n_factor = n_factor[z]; res[z].n_solve = n_solve[z];
+        if (L.ejected[z]) continue;
+        apply_certificate(L.outcome[z], n, m, p, y[z], p > 0 ? w[z] : nullptr, m > 0 ? v[z] : nullptr);
         res[z].wall_s = wall;            // the group's wall time: the problems finished together
     }
-#undef CK
     g_last_stats[0] += 1; g_last_stats[1] += B;
-    for (int z = 0; z < B; ++z) g_last_stats[2] += ejected[z] ? 1 : 0;
+    for (int z = 0; z < B; ++z) g_last_stats[2] += L.ejected[z] ? 1 : 0;
     exit_timer.on = timing; exit_timer.t0 = std::chrono::steady_clock::now();
     // ---- problems that left the group: the one-problem loop on their own handle (regularised factorisation and all)
     {
         BatchScope single(CipBatchCtx{1, 0, 1ull, nullptr, nullptr});
         for (int z = 0; z < B; ++z) {
-            if (!ejected[z]) continue;
+            if (!L.ejected[z]) continue;
             cip_handle *hz = G.h[z];
             hz->assembled = hz->factored = false; hz->info_pending = false; hz->reg_rel = 0.0; hz->n_regularized = 0;
             if ((rc = cip_conicip(hz, c[z], m > 0 ? b[z] : nullptr, p > 0 ? d[z] : nullptr, opt_in, y[z], p > 0 ? w[z] : nullptr,

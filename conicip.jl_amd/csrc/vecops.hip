@@ -368,6 +368,7 @@ __global__ __launch_bounds__(256) void k_axpby_ps(int len, CipScal64 alpha, cons
         y[i] = axpby_op(a, x[i], beta, y[i]);
 }
 int cip_axpby_ps(hipStream_t s, int len, const double *alpha_host, const double *x, double beta, double *y) {
+    if (!cip_in_batch()) return cip_axpby(s, len, alpha_host[0], x, beta, y);     // one problem: the scalar launch
     if (len <= 0) return 0;
     CipScal64 a;
     for (int z = 0; z < CIP_BATCH_MAX; ++z) a.v[z] = z < cip_tl_bz.B ? alpha_host[z] : 0.0;
