@@ -302,8 +302,11 @@ int cip_set_solve_block_max(int b);
  * update of everything below / above); 1 = ONE launch per block step for solve blocks of at most 512 columns -- the neighbour
  * blocks X_J L_{J,J-1} / L_{J+1,J} X_J are formed with the block inverses at factorisation time, so a step depends on the
  * previous step's result only (sweeps 20 % faster, factorisation dearer: pays from about six solves per factorisation on);
- * 2 = for every block width.  Applies to handles created afterwards; the two forms differ in rounding.  Returns the
- * previous mode (other values: query). */
+ * 2 = for every block width.  Applies to handles created afterwards; the two forms differ in rounding.  On graded factors
+ * (|L| up to 1e6) the one-launch form is the less accurate one: the pre-multiplied neighbours put |L_JJ||inv L_JJ| in front of
+ * L_{J,J-1}, and the residual against the factor was measured at 30 to 1.4e4 times the substitution bound u |L||D||L'||x| and
+ * 1.1e-14 to 1.4e-14 norm-wise, where the two-launch form stays at 1 to 3 times and below 3e-15 (DESIGN_LOG.md, "The LDL'
+ * and its solves on graded matrices").  Returns the previous mode (other values: query). */
 int cip_set_solve_fused(int mode);
 /* the solve-block limit cip_conicip_lockstep gives the handles of a call of B problems in all (512 for B <= 8, else 256 -- chosen
  * from the size of the whole call, so the groups of 64 it is cut into all use the same one; never more than
