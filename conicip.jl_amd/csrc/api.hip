@@ -19,6 +19,12 @@ void cip_set_error(const char *fmt, ...) {
 }
 extern "C" const char *cip_last_error(void) { return g_err; }
 
+// ------------------------------------------------------------------ environment switches (cip_internal.h)
+int cip_env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+long cip_env_long(const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; }
+double cip_env_double(const char *name, double dflt) { const char *e = getenv(name); return e ? atof(e) : dflt; }
+bool cip_env_set(const char *name) { return getenv(name) != nullptr; }
+
 // ------------------------------------------------------------------ profiler ranges (roctx)
 // "cip:scaling", "cip:assemble", "cip:ldlt", "cip:solve3x3", "cip:iteration" ranges for rocprofv3 --marker-trace.  The
 // marker library is looked up at run time (no link-time dependency: the library links libamdhip64 only); absent or
@@ -29,8 +35,7 @@ static int (*g_roctx_push)(const char *) = nullptr;
 static int (*g_roctx_pop)(void) = nullptr;
 static std::once_flag g_roctx_once;
 static void roctx_init(void) {
-    const char *e = getenv("CIP_ROCTX");
-    if (e && atoi(e) == 0) return;
+    if (cip_env_int("CIP_ROCTX", 1) == 0) return;
     for (const char *name : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
         if (void *lib = dlopen(name, RTLD_LAZY | RTLD_LOCAL)) {
             g_roctx_push = (int (*)(const char *))dlsym(lib, "roctxRangePushA");
@@ -53,7 +58,7 @@ static int rup(int x, int q) { return ((x + q - 1) / q) * q; }
 // 4.8e-4 and huge ints) instead of whatever the allocator hands out -- fresh memory of a fresh process is zero, recycled memory of a long
 // one is not, and nothing may depend on either.  tests/test_gpu_poison.py runs trajectories under it and compares the bits.
 static int debug_poison(void *p, size_t bytes) {
-    static const int v = [] { const char *e = getenv("CIP_DEBUG_POISON"); return e ? atoi(e) & 255 : 0; }();
+    static const int v = cip_env_int("CIP_DEBUG_POISON", 0) & 255;
     if (!v) return 0;
     CIP_HIP_CHECK(hipDeviceSynchronize());
     CIP_HIP_CHECK(hipMemset(p, v, bytes));
@@ -94,7 +99,7 @@ static void free_all(cip_handle *h) {
     if (h->cs.lg) { cip_sdp_large_destroy(h->cs.lg); h->cs.lg = nullptr; }
     void *ptrs[] = {h->cs.d_bigq, h->cs.d_ritems, h->cs.d_packq, h->cs.d_sidx_small, h->cs.d_sidx, h->cs.d_sdpws, h->cs.d_sdpvec, h->cs.d_sdpflag, h->Q, h->symv_ws, h->A, h->At, h->A_rp, h->A_ci, h->A_v, h->T_rp, h->T_ci, h->T_v, h->kdiag, h->row_cone, h->G, h->Gt,
                     h->cs.d_cones, h->cs.d_items, h->cs.d_scal, h->cs.d_partial, h->cs.d_scalar, h->K, h->Wt, h->syrk_ws, h->Gm, h->AtS, h->WtS,
-                    h->ws_base, h->rhs, h->mt1, h->mt2, h->mt3, h->nt1, h->pt1, h->dot_scratch, h->dot_ptrs, h->stage, h->drv, h->ref, h->c2x2, h->many, h->many_stage};
+                    h->ws_base, h->rhs, h->mt1, h->mt2, h->mt3, h->nt1, h->pt1, h->dot_scratch, h->stage, h->drv, h->ref, h->c2x2, h->many, h->many_stage};
     for (void *p : ptrs)
         if (p && !in_arena(h, p)) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -416,9 +421,7 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
     DMALLOC(h->rhs, sizeof(double) * h->Npad);
     DMALLOC(h->mt1, sizeof(double) * m); DMALLOC(h->mt2, sizeof(double) * m); DMALLOC(h->mt3, sizeof(double) * m);
     DMALLOC(h->nt1, sizeof(double) * n); DMALLOC(h->pt1, sizeof(double) * p);
-    DMALLOC(h->dot_scratch, sizeof(double) * (32 * 32 + 64));
-    CIP_HIP_CHECK(hipMemsetAsync(h->dot_scratch + 32 * 32 + 32, 0, sizeof(double) * 32, s));      // the completion counters of vecops.hip: k_dots
-    DMALLOC(h->dot_ptrs, 32 * 32);
+    DMALLOC(h->dot_scratch, sizeof(double) * (32 * 32 + 32));
     DMALLOC(h->stage, sizeof(double) * 2 * (size_t)(n + p + m));
     CIP_HIP_CHECK(hipEventCreate(&h->ev0)); CIP_HIP_CHECK(hipEventCreate(&h->ev1)); CIP_HIP_CHECK(hipEventCreate(&h->ev2));
     // (the pinned pivot-flag words are allocated by the first factorisation: pinned allocations cost ~0.1 ms each, and the
@@ -552,9 +555,8 @@ extern "C" int cip_assemble_only(cip_handle *h) {
 // (rocprofv3 also crashed on the graph path with several host threads).
 static bool graph_wanted(cip_handle *h) {
     if (h->graph_state == 0) {
-        const char *e = getenv("CIP_GRAPH");
-        const int npmax = getenv("CIP_GRAPH_NMAX") ? atoi(getenv("CIP_GRAPH_NMAX")) : 4096;
-        h->graph_state = (h->Npad <= npmax && e && atoi(e) == 1 && !h->timing && !h->ws.prof) ? 1 : -1;
+        const int npmax = cip_env_int("CIP_GRAPH_NMAX", 4096);
+        h->graph_state = (h->Npad <= npmax && cip_env_int("CIP_GRAPH", 0) == 1 && !h->timing && !h->ws.prof) ? 1 : -1;
     }
     return h->graph_state == 1;
 }
@@ -718,7 +720,7 @@ static int factor_resolve(cip_handle *h, bool wait) {
     if (h->reg_rel > 0.0) {
         info = h->info_host[2];
     } else if (h->auto_reg) {
-        h->reg_rel = getenv("CIP_AUTO_REG") ? atof(getenv("CIP_AUTO_REG")) : CIP_AUTO_REG;
+        h->reg_rel = cip_env_double("CIP_AUTO_REG", CIP_AUTO_REG);
         h->n_regularized += 1;
         int rc;
         if ((rc = refactor_and_wait(h))) return rc;
@@ -902,7 +904,7 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
         const double *px[6] = {rx, ry, rz, xs, ys, zs};
         const int ln[6] = {n, p, m, n, p, m};
         double d6[6];
-        if ((rc = cip_dots(s, 6, px, px, ln, h->dot_scratch, h->dot_ptrs, d6))) return rc;
+        if ((rc = cip_dots(s, 6, px, px, ln, h->dot_scratch, d6))) return rc;
         const double rn = sqrt(d6[0] + d6[1] + d6[2]), bn = sqrt(d6[3] + d6[4] + d6[5]);
         if (!(rn > 1e-14 * bn) || !(rn < prev)) break;           // converged, stagnating, or not finite
         prev = rn;
@@ -1117,10 +1119,9 @@ extern "C" int cip_solve2x2_many(cip_handle *h, int nrhs, const double *Y, const
 }
 
 // diag F (the packed scaling) when the cone set is R cones only -- the native loops then fuse the cone operations of their
-// element-wise chains into the vector kernels (vecops.hip: k_loop_*); NULL otherwise (or with CIP_LOOP_FUSED_R=0)
+// element-wise chains into the vector kernels (vecops.hip: k_loop_*); NULL otherwise
 const double *cip_loop_all_r(cip_handle *h) {
-    static const int on = [] { const char *e = getenv("CIP_LOOP_FUSED_R"); return e ? atoi(e) : 1; }();
-    if (!on || h->m <= 0) return nullptr;
+    if (h->m <= 0) return nullptr;
     for (int q = 0; q < h->cs.ncones; ++q) if (h->h_cones[q].type != CIP_CONE_R) return nullptr;
     return h->cs.d_scal;
 }
@@ -1136,8 +1137,7 @@ extern "C" int cip_solve4x4_dev(cip_handle *h, const double *lambda, const doubl
     if (h->all_r < 0) {
         h->all_r = m > 0 ? 1 : 0;
         for (int q = 0; q < h->cs.ncones; ++q) if (h->cs.h_cones[q].type != CIP_CONE_R) h->all_r = 0;
-        const char *e = getenv("CIP_S4_FUSED");
-        if (e && atoi(e) == 0) h->all_r = 0;
+        if (cip_env_int("CIP_S4_FUSED", 1) == 0) h->all_r = 0;
     }
     // the fused kernels read r across threads (CSR gathers) while writing dz: an in-place call (dz overlapping r) takes the
     // element-wise generic path, which tolerates it
@@ -1227,7 +1227,7 @@ extern "C" int cip_gemv_dev(cip_handle *h, int which, int trans, double alpha, c
 extern "C" int cip_dots_dev(cip_handle *h, int count, const double *const *x, const double *const *y, const int *len,
                             double *out_host) {
     if (!h) return CIP_E_INVALID;
-    return cip_dots(h->stream, count, x, y, len, h->dot_scratch, h->dot_ptrs, out_host);
+    return cip_dots(h->stream, count, x, y, len, h->dot_scratch, out_host);
 }
 extern "C" int cip_axpby_dev(cip_handle *h, int len, double alpha, const double *x, double beta, double *y) {
     if (!h) return CIP_E_INVALID;

@@ -289,8 +289,7 @@ static std::atomic<int> g_lazy_copy{-1};  // CIP_LAZY_COPY / cip_set_lazy_copy: 
 int cip_lazy_copy_set(int on) {
     int prev = g_lazy_copy.load(std::memory_order_relaxed);
     if (prev < 0) {                                                  // first use: the environment decides (racing threads agree)
-        const char *e = getenv("CIP_LAZY_COPY");
-        const int env = e ? (atoi(e) != 0) : 1;
+        const int env = cip_env_int("CIP_LAZY_COPY", 1) != 0;
         int expect = -1;
         g_lazy_copy.compare_exchange_strong(expect, env);
         prev = g_lazy_copy.load(std::memory_order_relaxed);

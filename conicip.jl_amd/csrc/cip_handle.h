@@ -77,7 +77,7 @@ struct cip_handle {
     double *mt1 = nullptr, *mt2 = nullptr, *mt3 = nullptr;   // m-vectors
     double *nt1 = nullptr;          // n-vector
     double *pt1 = nullptr;          // p-vector
-    double *dot_scratch = nullptr; void *dot_ptrs = nullptr;
+    double *dot_scratch = nullptr;
     double *stage = nullptr;        // device staging for the host-pointer entry points: 2*(n+p+m) doubles
     double *ref = nullptr;          // right-hand side / residual / correction of the refinement inside solve3x3 (regularised factor only)
     double *c2x2 = nullptr;         // m-vector: discarded third component of a regularised 2x2 solve

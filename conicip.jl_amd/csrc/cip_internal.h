@@ -22,6 +22,14 @@ void cip_set_error(const char *fmt, ...);
         }                                                                         \
     } while (0)
 
+// ---------------------------------------------------------------- environment switches (api.hip; INTEGRATION.md section 6 lists them)
+// The value of a CIP_* variable through atoi / atol / atof (garbage reads as 0), `dflt` when it is unset.  Range checks and
+// "read once" (a function-local static) are the call site's; cip_env_set: set to anything at all, "0" included.
+int cip_env_int(const char *name, int dflt);
+long cip_env_long(const char *name, long dflt);
+double cip_env_double(const char *name, double dflt);
+bool cip_env_set(const char *name);
+
 // ---------------------------------------------------------------- launches that can be recorded into a hipGraph
 // The LDL' factorisation and the triangular solves of a handle are fixed launch sequences (same pointers, same sizes
 // every time).  For small systems they are recorded ONCE as an explicit graph -- kernel nodes added one after the other
@@ -303,7 +311,7 @@ int cip_gemv_t(hipStream_t s, int rows, int cols, double alpha, const double *A,
 int cip_spmv_csr(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val,
                  double alpha, const double *x, double beta, double *y);
 int cip_dots(hipStream_t s, int count, const double *const *x_host, const double *const *y_host,
-             const int *len_host, double *scratch_dev, void *ptrs_dev, double *out_host);
+             const int *len_host, double *scratch_dev, double *out_host);
 int cip_axpby(hipStream_t s, int len, double alpha, const double *x, double beta, double *y);
 // solve4x4 around the sweeps for all-R cone sets (vecops.hip): the element-wise launches fused, same arithmetic
 int cip_s4_pre_r(hipStream_t s, int m, int n, int p, int Npad, const double *f, const double *rs, const double *lam, const double *rv,
@@ -315,7 +323,7 @@ int cip_axpby_ps(hipStream_t s, int len, const double *alpha_host, const double 
 int cip_zero(hipStream_t s, long len, double *y);                     // batch-aware memset(0) of doubles
 int cip_copy(hipStream_t s, long len, const double *x, double *y);    // batch-aware device-to-device copy
 struct cip_handle;
-const double *cip_loop_all_r(cip_handle *h);     // api.hip: the packed scaling = diag F when every cone is an R cone (and CIP_LOOP_FUSED_R != 0), else NULL
+const double *cip_loop_all_r(cip_handle *h);     // api.hip: the packed scaling = diag F when every cone is an R cone, else NULL
 // the element-wise chains of the interior-point loop, one kernel each (vecops.hip; f != NULL: all cones R, cone operations fused in)
 int cip_loop_resid(hipStream_t s, int n, int m, int p, double *rl, const double *zs, const double *c, const double *d, const double *b,
                    const double *lam, const double *f, double *r0, double *Gy, double *Ays);

@@ -327,14 +327,14 @@ __global__ __launch_bounds__(256) void k_syrk_reduce(GemmArgs g, CipBatch cb) {
 }
 // 128-tile form of the split: few tiles and a K so long that the 64-tile form is bound by re-streaming its operands
 static bool syrk_split_128(int M, int K) {
-    static const int force = [] { const char *e = getenv("CIP_SYRK_TILE"); return e ? atoi(e) : 0; }();
+    static const int force = cip_env_int("CIP_SYRK_TILE", 0);
     if (force == 64) return false;
     const long tm = M / CIP_NB, t128 = tm * (tm + 1) / 2;
     if (force == 128) return t128 <= 256;
     return t128 <= 64 && K >= 16384;
 }
 int cip_syrk_split(int M, int K, int *len) {
-    static const int on = [] { const char *e = getenv("CIP_SYRK_SPLITK"); return e ? atoi(e) : 1; }();
+    static const int on = cip_env_int("CIP_SYRK_SPLITK", 1);
     const long tm = M / CIP_NB, wgs = 4 * (tm * (tm + 1) / 2);
     int n = 1;
     if (on && wgs < 640 && K >= 4096) {
@@ -345,27 +345,6 @@ int cip_syrk_split(int M, int K, int *len) {
     n = (K + l - 1) / l;
     if (len) *len = l;
     return n;
-}
-
-// XCD-aware order (optional, CIP_TRAIL_PATCH): workgroups are dealt round-robin to the 8 XCDs, so XCD x is handed whole
-// p x p patches of quarter tiles (patches x, x+8, ...): the 2p half-panels of a patch are then fetched into that
-// XCD's L2 once for p^2 tiles instead of once per tile.
-__global__ __launch_bounds__(256, 4) void k_ldlt_trailing_64p(GemmArgs g, int psz, int npatch, int P, CipBatch cb) {
-    __shared__ __attribute__((aligned(16))) double lds[2 * 2 * CIP_KT * SB];   // 32 KB
-    bool live;
-    (void)gemm_batch_prologue(g, cb, live);
-    if (!live) return;
-    __builtin_amdgcn_s_setprio(3);
-    const int b = blockIdx.x, x = b & 7, sq = b >> 3, per = psz * psz;
-    const int patch = x + 8 * (sq / per), w = sq % per;
-    if (patch >= npatch) return;
-    int pi, pj;
-    tile_coords(patch, 1, P, pi, pj);
-    const int nq = g.M / SB;
-    const int qi = pi * psz + w % psz, qj = pj * psz + w / psz;
-    if (qi >= nq || qj >= nq) return;
-    if ((qi >> 1) < (qj >> 1) || ((qi >> 1) == (qj >> 1) && qi < qj)) return;      // above the (128-tile) diagonal
-    gemm_tile_64(g, lds, (long)qi * SB, (long)qj * SB);
 }
 
 int cip_launch_gemm(hipStream_t s, int epi, const GemmArgs &g) {
@@ -399,34 +378,20 @@ int cip_launch_gemm(hipStream_t s, int epi, const GemmArgs &g) {
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    // CIP_GEMM_TILE=128: the lower-triangular update on the 128x128 kernel (kept for A/B runs of tools/gemm_bench.hip)
-    static const int g_tile = [] { const char *e = getenv("CIP_GEMM_TILE"); return (e && atoi(e) == 128) ? 128 : 64; }();
     if (epi == EPI_LAZYC) {
         if (!g.lower || !g.Qin || !g.Cdiag || (g.ldq & 1) || (((uintptr_t)g.Qin) & 15)) { cip_set_error("gemm: bad lazy-C arguments"); return -1; }
         cip_launch_b(k_ldlt_trailing_64<EPI_LAZYC>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (epi == EPI_ACCUM && g.lower && g_tile == 64) {
-        // the LDL' trailing update: every 128-tile of the lower triangle as four 64x64 quarter tiles
-        // Optional XCD-aware patch order (CIP_TRAIL_PATCH=4 or 8).  PMC at r = 8192, K = 512: 1.52 GB of L2-miss
-        // fetches per launch in plain tile order, 0.94 GB with 4x4 patches, 0.75 GB with 8x8 -- but the launch is not
-        // faster (standalone +1.5 % at r = 8192, -1 % at r = 2048) and the factorisation is 1-2 % SLOWER (same-session
-        // A/B: 52.6 / 51.9 vs 51.0 / 50.4 TFLOP/s): the misses are served by the Infinity Cache and hidden by the 20
-        // waves per CU, while a patch granularity costs load balance over the 8 XCDs.  Off by default.
-        static const int psz = [] { const char *e = getenv("CIP_TRAIL_PATCH"); return e ? atoi(e) : 0; }();
-        if (psz > 0) {
-            const int nq = g.M / SB, P = (nq + psz - 1) / psz, npatch = P * (P + 1) / 2;
-            const long grid = (long)((npatch + 7) / 8) * 8 * psz * psz;
-            cip_launch_b(k_ldlt_trailing_64p, dim3((unsigned)grid), dim3(256), 0, s, g, psz, npatch, P);
-            CIP_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
+    if (epi == EPI_ACCUM && g.lower) {
+        // the LDL' trailing update: every 128-tile of the lower triangle as four 64x64 quarter tiles (in plain tile order: an
+        // XCD-aware patch order fetched less and ran slower, DESIGN_LOG.md "Experiments removed from the library")
         cip_launch_b(k_ldlt_trailing_64<EPI_ACCUM>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (epi == EPI_SYRKQ && g.lower && g_tile == 64 && g.ksplit_ws && g.ksplit_n > 1) {
+    if (epi == EPI_SYRKQ && g.lower && g.ksplit_ws && g.ksplit_n > 1) {
         GemmArgs gs = g;
         gs.alpha = 1.0;                                          // (the images hold the plain products; alpha is applied by the reduction)
         if (syrk_split_128(g.M, g.K)) cip_launch_b(k_syrk_splitk_128, dim3((unsigned)tiles, (unsigned)g.ksplit_n), dim3(256), 0, s, gs);
@@ -436,11 +401,11 @@ int cip_launch_gemm(hipStream_t s, int epi, const GemmArgs &g) {
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (epi == EPI_SYRKQ && g.lower && g_tile == 64) {
+    if (epi == EPI_SYRKQ && g.lower) {
         // operands global -> LDS directly + raised wave priority, as the trailing update (round 4, config 3: 1.35 -> 1.28 ms per
-        // Schur formation, same-session A/B 4.17 -> 4.10 ms per iteration, same bits); CIP_SYRK_GLDS=0: register staging
-        static const int glds = [] { const char *e = getenv("CIP_SYRK_GLDS"); return e ? atoi(e) : 1; }();
-        if (glds && !(g.lda & 1) && !(g.ldb & 1) && !(((uintptr_t)g.A | (uintptr_t)g.B) & 15)) cip_launch_b(k_syrkq_64<true>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+        // Schur formation, same-session A/B 4.17 -> 4.10 ms per iteration, same bits); register staging for odd leading
+        // dimensions and misaligned operands
+        if (!(g.lda & 1) && !(g.ldb & 1) && !(((uintptr_t)g.A | (uintptr_t)g.B) & 15)) cip_launch_b(k_syrkq_64<true>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
         else cip_launch_b(k_syrkq_64<false>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
@@ -452,12 +417,8 @@ int cip_launch_gemm(hipStream_t s, int epi, const GemmArgs &g) {
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    dim3 grid((unsigned)tiles), block(256);
-    switch (epi) {
-        case EPI_ACCUM: cip_launch_b(k_gemm_nt_128<EPI_ACCUM>, grid, block, 0, s, g); break;
-        case EPI_SYRKQ: cip_launch_b(k_gemm_nt_128<EPI_SYRKQ>, grid, block, 0, s, g); break;
-        default: cip_set_error("gemm: bad epilogue"); return -1;
-    }
+    if (epi != EPI_ACCUM) { cip_set_error("gemm: bad epilogue"); return -1; }      // (EPI_SYRKQ: lower tiles only, above)
+    cip_launch_b(k_gemm_nt_128<EPI_ACCUM>, dim3((unsigned)tiles), dim3(256), 0, s, g);
     CIP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -34,8 +34,7 @@ static std::once_flag g_fuse_once;
 // TRSM pipelined behind the diagonal kernel (k_ldlt_panel); 0: diag -> TRSM -> in-block update, three launches per panel
 static void fuse_env(void) {
     std::call_once(g_fuse_once, [] {
-        const char *e = getenv("CIP_FUSE_DIAG");
-        g_fuse_diag = (e && atoi(e) == 0) ? 0 : 3;
+        g_fuse_diag = cip_env_int("CIP_FUSE_DIAG", 3) == 0 ? 0 : 3;
     });
 }
 int cip_ldlt_outer_block_for(int Npad) {
@@ -44,7 +43,7 @@ int cip_ldlt_outer_block_for(int Npad) {
     // Round 4 re-tuned the width on the current chain (same-session A/B, wide last block in force; CIP_LDLT_NBO_AUTO overrides):
     // 640 / 768 / 896 / 1024 -> 185.4 / 189.1 / 191.3 / 188.7 KKT solves/s at n = 8192 (6 x 896 + 2816: one trailing update
     // fewer, 60.1 TFLOP/s), config 3 (order 4608) 31.3 -> 30.0 ms, the literal 3x3 route at N = 16384 35.7 -> 35.8.
-    static const int nbo_auto = [] { const char *e = getenv("CIP_LDLT_NBO_AUTO"); const int v = e ? atoi(e) : 896; return (v >= 256 && v <= 1024 && v % CIP_NB == 0) ? v : 896; }();
+    static const int nbo_auto = [] { const int v = cip_env_int("CIP_LDLT_NBO_AUTO", 896); return (v >= 256 && v <= 1024 && v % CIP_NB == 0) ? v : 896; }();
     return (Npad >= 4096 && g_fuse_diag) ? nbo_auto : 512;    // not a function of the batch: lock-step groups reproduce the one-problem loop bit for bit
 }
 #define CIP_NBO_MAX 1024
@@ -58,7 +57,7 @@ static size_t wbuf_cols(int Npad) { return Npad >= 4096 ? (Npad < CIP_TAIL_MAX ?
 // 182.5 KKT solves/s (beyond 2816 the block's first panel launches are bound by their ~900 tiles: 57 / 52 / 51 us).
 // A function of the order and the column only, like the width itself.
 static int ldlt_tail_cols(void) {
-    static const int v = [] { const char *e = getenv("CIP_LDLT_TAIL"); const int t = e ? atoi(e) : 2816; return t > CIP_TAIL_MAX ? CIP_TAIL_MAX : t; }();
+    static const int v = [] { const int t = cip_env_int("CIP_LDLT_TAIL", 2816); return t > CIP_TAIL_MAX ? CIP_TAIL_MAX : t; }();
     return v;
 }
 static int outer_block_width(int Npad, int C0) {
@@ -167,7 +166,7 @@ static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static std::atomic<int> g_solve_block_max{-1};
 thread_local int cip_tl_solve_block_max = 0;
 int cip_solve_block_max_set(int b) {
-    if (g_solve_block_max.load() < 0) { const char *e = getenv("CIP_SOLVE_BLOCK"); int v = -1; g_solve_block_max.compare_exchange_strong(v, e ? atoi(e) : 1024); }
+    if (g_solve_block_max.load() < 0) { int v = -1; g_solve_block_max.compare_exchange_strong(v, cip_env_int("CIP_SOLVE_BLOCK", 1024)); }
     const int prev = g_solve_block_max.load();
     if (b == 128 || b == 256 || b == 512 || b == 1024) g_solve_block_max.store(b);
     return prev;
@@ -193,7 +192,7 @@ int cip_solve_block(int Npad) {
 // solves per factorisation on: off by default, kept for callers that solve many right-hand sides with one factor.
 static std::atomic<int> g_solve_fused{-1};
 int cip_solve_fused_set(int mode) {
-    if (g_solve_fused.load() < 0) { const char *e = getenv("CIP_SOLVE_FUSED"); int v = -1; g_solve_fused.compare_exchange_strong(v, e ? atoi(e) : 0); }
+    if (g_solve_fused.load() < 0) { int v = -1; g_solve_fused.compare_exchange_strong(v, cip_env_int("CIP_SOLVE_FUSED", 0)); }
     const int prev = g_solve_fused.load();
     if (mode == 0 || mode == 1 || mode == 2) g_solve_fused.store(mode);
     return prev;
@@ -317,9 +316,9 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
         // for its own problem's workgroup 0 only, which was dispatched before it; a workgroup 0 waits for its producers, which
         // follow it in dispatch order and find a CU as soon as any earlier problem's workgroups retire -- and the first
         // problem's always can.
-        static const int lsmax = [] { const char *e = getenv("CIP_LOCKSTEP_PANEL_MAX"); return e ? atoi(e) : 32; }();
+        static const int lsmax = cip_env_int("CIP_LOCKSTEP_PANEL_MAX", 32);
         static const int lscus = [] {
-            if (const char *e = getenv("CIP_LOCKSTEP_PANEL_CUS")) return atoi(e);
+            if (cip_env_set("CIP_LOCKSTEP_PANEL_CUS")) return cip_env_int("CIP_LOCKSTEP_PANEL_CUS", 0);
             int dev = 0, cus = 256;
             if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
             return 4 * cus;
@@ -412,8 +411,8 @@ __global__ __launch_bounds__(256, 4) void k_solve_premul(const double *K, long l
     }
     gemm_tile_64<EPI_STORE>(g, lds, i0, j0);
 }
-// The doubling products of the LAST solve block of a 1024-wide blocking on 16x16 tiles (k_gemm_nt_16_batched; CIP_DOUBLING_TINY=0:
-// never).  That block's preparation is the one piece of a factorisation nothing hides: with the side stream it runs under the first
+// The doubling products of the LAST solve block of a 1024-wide blocking on 16x16 tiles (k_gemm_nt_16_batched).
+// That block's preparation is the one piece of a factorisation nothing hides: with the side stream it runs under the first
 // solve's forward sweep, which reaches the block after ~90 us, and its seven dependent launches took 135 us -- a 64x64 tile walks its
 // whole K = h on one CU (512 dependent MFMAs per wave at h = 512: 19 us per launch on an idle chip), the 16x16 form spreads the same
 // product over (h / 16)^2 workgroups.  Same-session, n = 8192: the first solve after a factorisation 0.282 -> 0.244 ms (the second:
@@ -421,8 +420,7 @@ __global__ __launch_bounds__(256, 4) void k_solve_premul(const double *K, long l
 // 8 problems of order 2048: 15.2 -> 15.8 ms per pass).  A function of the block's position and the blocking only -- a side-stream
 // group, a whole-matrix preparation (which splits the last block off) and a lock-step batch all produce the same bits.
 static int doubling_tiny(int Bs, int J0, int nbk_all) {
-    static const int on = [] { const char *e = getenv("CIP_DOUBLING_TINY"); return e ? atoi(e) : 1; }();
-    return on && Bs == 1024 && J0 == nbk_all - 1;
+    return Bs == 1024 && J0 == nbk_all - 1;
 }
 static int build_solve_premul(hipStream_t s, double *K, long ld, const LdltWorkspace &ws, int nbk_all, int J0, int J1) {
     if (!ws.fused) return 0;
@@ -511,7 +509,7 @@ void cip_ldlt_side_destroy(LdltSide *sd) {
 }
 static std::atomic<int> g_side_prep{-1};
 static int side_prep_mode(void) {
-    if (g_side_prep.load() < 0) { const char *e = getenv("CIP_SIDE_PREP"); int v = -1; g_side_prep.compare_exchange_strong(v, e ? (atoi(e) != 0) : 1); }
+    if (g_side_prep.load() < 0) { int v = -1; g_side_prep.compare_exchange_strong(v, cip_env_int("CIP_SIDE_PREP", 1) != 0); }
     return g_side_prep.load();
 }
 int cip_ldlt_set_side_prep(int on) { const int prev = side_prep_mode(); if (on == 0 || on == 1) g_side_prep.store(on); return prev; }
@@ -545,7 +543,7 @@ static int side_fork(LdltSide *sd, hipStream_t s, double *K, int Npad, long ld, 
     hipStream_t t = sd->s2;
     CIP_HIP_CHECK(hipEventRecord(sd->fork[g], s));
     CIP_HIP_CHECK(hipStreamWaitEvent(t, sd->fork[g], 0));
-    static const long delay_us = [] { const char *e = getenv("CIP_DEBUG_SIDE_DELAY_US"); return e ? atol(e) : 0L; }();
+    static const long delay_us = cip_env_long("CIP_DEBUG_SIDE_DELAY_US", 0L);
     if (delay_us > 0) { hipLaunchKernelGGL(k_debug_spin, dim3(1), dim3(64), 0, t, delay_us * 100); CIP_HIP_CHECK(hipGetLastError()); }
     const int rc = build_solve_blocks(t, K, Npad, ld, ws, J0, J1);
     CIP_HIP_CHECK(hipEventRecord(sd->done[g], t));
@@ -662,7 +660,7 @@ static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const L
             // are final (the first fork takes everything to its left).  The wide block's FIRST panel launches carry ~900
             // update tiles each and fill the chip: side work beside them costs the chain what it saves (same-session A/B,
             // forking from the block's start: 187.5 against 188.7 KKT solves/s); the last ones are a chain on an idle chip.
-            static const int side_from = [] { const char *e = getenv("CIP_SIDE_PREP_FROM"); return e ? atoi(e) : 2048; }();
+            static const int side_from = cip_env_int("CIP_SIDE_PREP_FROM", 2048);
             for (int c = C0; c < Npad; ) {
                 // (forks no finer than 1024 columns: with a 512-wide solve block -- order 4608, config 3 -- a fork per block was five
                 //  groups of tiny launches per factorisation, 0.2 ms of side work more than the serial preparation)
@@ -704,11 +702,8 @@ static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const L
     }
     if (sd && sd->nfork > 0) {
         // The LAST group -- the solve blocks whose columns the last panels produced -- runs under the first solve's forward sweep,
-        // which waits for it at the last block (cip_ldlt_side_join).  Round 5 measured it on the factorisation's own stream instead
-        // (CIP_SIDE_LAST_MAIN=1: no fork, no join, the group's seven launches alone on the chip: 63 us with the 16x16-tile doubling
-        // products): the first solve 0.245 -> 0.223 ms, the step 0.03 ms SLOWER.  On the side stream by default.
-        static const int last_main = [] { const char *e = getenv("CIP_SIDE_LAST_MAIN"); return e ? atoi(e) : 0; }();
-        if (last_main && Npad / Bs - Jdone == 1) return build_solve_blocks(s, K, Npad, ld, ws, Jdone, Npad / Bs);
+        // which waits for it at the last block (cip_ldlt_side_join).  (On the factorisation's own stream it lost: DESIGN_LOG.md,
+        // "Experiments removed from the library".)
         return side_fork(sd, s, K, Npad, ld, ws, Jdone, Npad / Bs);      // joined by the solves (cip_ldlt_side_join)
     }
     if (ws.no_prep) return 0;

@@ -195,8 +195,7 @@ extern "C" int cip_lockstep_solve_block_for(int B) {
     // groups of up to 8 problems: 512 (the sweeps are launch chains on a mostly idle chip: half the block steps; 8 problems of
     // order 2048, 256 / 512 / 1024: 16.75 / 16.55 / 17.8 ms per pass); larger groups: 256 (the doubling GEMMs of a wider
     // block are real work for 64 problems).  CIP_LOCKSTEP_SOLVE_BLOCK overrides both.
-    const char *e = getenv("CIP_LOCKSTEP_SOLVE_BLOCK");
-    const int want = e ? atoi(e) : (B <= 8 ? 512 : 256), glob = cip_solve_block_max_set(0);
+    const int want = cip_env_int("CIP_LOCKSTEP_SOLVE_BLOCK", B <= 8 ? 512 : 256), glob = cip_solve_block_max_set(0);
     return want < glob ? want : glob;
 }
 // One lock-step group (B <= CIP_BATCH_MAX problems of the same shape).  Returns 0 and fills res / y / w / v of every
@@ -205,7 +204,7 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
                           const double *const *d, const cip_options *opt_in, double *const *y, double *const *w,
                           double *const *v, cip_result *res) {
     const auto t_start = std::chrono::steady_clock::now();
-    static const bool timing = getenv("CIP_LOCKSTEP_TIMING") != nullptr;
+    static const bool timing = cip_env_set("CIP_LOCKSTEP_TIMING");
     auto since = [&]() { return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
     double t_probe = 0, t_arena = 0, t_create = 0, t_loop = 0;
     const cip_options o = resolve_options(opt_in);
@@ -318,8 +317,7 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
 static std::atomic<int> g_lockstep_split{-1};
 int cip_lockstep_split_set(int k) {
     if (g_lockstep_split.load() < 0) {
-        const char *e = getenv("CIP_LOCKSTEP_SPLIT");
-        int v = -1, want = e ? atoi(e) : CIP_LOCKSTEP_SPLIT_DEFAULT;
+        int v = -1, want = cip_env_int("CIP_LOCKSTEP_SPLIT", CIP_LOCKSTEP_SPLIT_DEFAULT);
         want = want < 1 ? 1 : (want > 8 ? 8 : want);
         g_lockstep_split.compare_exchange_strong(v, want);
     }
@@ -366,7 +364,7 @@ extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const d
     // 2 x 4 LOSE (15.3 -> 15.5-16.9: each panel launch owns whole CUs -- 160 KB of LDS per workgroup -- and two latency-bound chains only
     // get in each other's way), as do three or four groups (64 as 4 x 16: 77.2-78.8).  Hence: two groups, none smaller than 8.
     int nsplit = cip_lockstep_split_set(0);
-    static const int split_min = [] { const char *e = getenv("CIP_LOCKSTEP_SPLIT_MIN"); const int k = e ? atoi(e) : CIP_LOCKSTEP_SPLIT_MIN_DEFAULT; return k < 1 ? 1 : k; }();
+    static const int split_min = [] { const int k = cip_env_int("CIP_LOCKSTEP_SPLIT_MIN", CIP_LOCKSTEP_SPLIT_MIN_DEFAULT); return k < 1 ? 1 : k; }();
     while (nsplit > 1 && count / nsplit < split_min) --nsplit;
     if (nsplit <= 1) return range(0, count);
     int device = 0;

@@ -37,14 +37,6 @@
 #define LG_SQRT1_2 0.7071067811865476
 
 __device__ int g_lz_hist[40];           // k_lg_lanczos1: histogram of step counts (bins of 8)
-#ifdef LZ_TIMING
-__device__ long g_lz_t[8];              // development: clocks per phase, summed over all calls (thread 0)
-#define LZ_T0() long lz_t = __builtin_amdgcn_s_memtime()
-#define LZ_T(i) do { if (threadIdx.x == 0) { const long t_ = __builtin_amdgcn_s_memtime(); g_lz_t[i] += t_ - lz_t; lz_t = t_; } } while (0)
-#else
-#define LZ_T0() do { } while (0)
-#define LZ_T(i) do { } while (0)
-#endif
 #define LG_NPAD 4
 struct LargeWs {
     int rp = 0;                    // padded order (256 or 512)
@@ -591,11 +583,11 @@ int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out) {
         int c = ncols > 0 ? ncols : 64;
         if ((size_t)c > cap) c = (int)cap;
         if (c < 16) c = 16;
-        if (const char *e = getenv("CIP_LG_CHUNK")) if (atoi(e) >= 1) c = atoi(e);
+        if (const int e = cip_env_int("CIP_LG_CHUNK", 0); e >= 1) c = e;
         w->chunk = c;
     }
     w->ncols = ncols;
-    const bool cache_mat = ncols > 0 && w->chunk >= ncols && (size_t)nlarge * ncols * m2 <= ((size_t)4 << 30) && !(getenv("CIP_LG_AMAT") && atoi(getenv("CIP_LG_AMAT")) == 0);
+    const bool cache_mat = ncols > 0 && w->chunk >= ncols && (size_t)nlarge * ncols * m2 <= ((size_t)4 << 30);
     size_t bytes = (cache_mat ? (size_t)nlarge * ncols * m2 : 0) + 8 * m2 + (3 + (size_t)nlarge) * m2 + LG_NPAD * (size_t)nlarge * m2 + al256(12 * (size_t)rp * 8) + 2 * (size_t)w->chunk * m2 + al256(1024) +
                    al256(16 * (size_t)nlarge);
     // the two LDL' workspaces: solve block = the whole padded matrix (X = inv(L_unit) in one piece: the "triangular solves" here are
@@ -639,27 +631,18 @@ int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out) {
     *out = w;
     return 0;
 }
-void cip_lg_cks_dump(void);
 void cip_sdp_large_destroy(LargeWs *w) {
     if (!w) return;
-    cip_lg_cks_dump();
     if (w->hflag) (void)hipHostFree(w->hflag);
     if (w->s2) (void)hipStreamDestroy(w->s2);
     if (w->efork) (void)hipEventDestroy(w->efork);
     if (w->ejoin) (void)hipEventDestroy(w->ejoin);
-    if (const char *e = getenv("CIP_LG_LANCZOS_STATS")) {
-        if (atoi(e)) {
-            int st[40];
-            if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_lz_hist), sizeof(st)) == hipSuccess) {
-                fprintf(stderr, "lanczos max-step, steps per call (bins of 8):");
-                for (int q = 0; q <= 32; ++q) if (st[q]) fprintf(stderr, " [%d-%d]: %d", 8 * q, 8 * q + 7, st[q]);
-                fprintf(stderr, "\n");
-            }
-#ifdef LZ_TIMING
-            long tt[8];
-            if (hipMemcpyFromSymbol(tt, HIP_SYMBOL(g_lz_t), sizeof(tt)) == hipSuccess)
-                fprintf(stderr, "lanczos clocks: load+v1 %ld | A v %ld | alpha %ld | dots %ld | update %ld | beta %ld | multisection %ld | rest of check %ld\n", tt[0], tt[1], tt[2], tt[3], tt[4], tt[5], tt[7], tt[6]);
-#endif
+    if (cip_env_int("CIP_LG_LANCZOS_STATS", 0)) {
+        int st[40];
+        if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_lz_hist), sizeof(st)) == hipSuccess) {
+            fprintf(stderr, "lanczos max-step, steps per call (bins of 8):");
+            for (int q = 0; q <= 32; ++q) if (st[q]) fprintf(stderr, " [%d-%d]: %d", 8 * q, 8 * q + 7, st[q]);
+            fprintf(stderr, "\n");
         }
     }
     if (w->base) (void)hipFree(w->base);
@@ -729,12 +712,8 @@ __global__ __launch_bounds__(256) void k_gemm_nt_small(const double *A, long lda
     }
 }
 // part 2: only the 64-tiles that touch i <= j are computed (the others keep what C held); 3: only those that touch i >= j
-static int lg_small_gemm(void) {
-    static const int small = [] { const char *e = getenv("CIP_LG_SMALLGEMM"); return e ? atoi(e) : 1; }();
-    return small;
-}
 static int lg_gemm(hipStream_t s, double *C, long sC, const double *A, long sA, const double *B, long sB, int rp, int batch, int part = 0) {
-    if (batch == 1 && part == 0 && rp <= 256 && lg_small_gemm()) {
+    if (batch == 1 && part == 0 && rp <= 256) {
         hipLaunchKernelGGL((k_gemm_nt_small<false, false>), dim3(rp / 16, rp / 16), dim3(256), 0, s, A, (long)rp, B, (long)rp, C, (long)rp, rp, rp);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
@@ -965,7 +944,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
         if (tid == 0) { partial[item] = INF; if (stat) stat[0] = 0; if (cert) { cert[0] = 0.0; cert[1] = 1.0; } }
         return;
     }
-    LZ_T0();
     double a[8][16];                                           // blocks bj <= 2 ai + 1 only (k_lg_tridiag1's layout)
 #pragma unroll
     for (int ai = 0; ai < 8; ++ai)
@@ -994,7 +972,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
     }
     if (tid < 256) { vs[tid] = vi; vput(0, tid, vi); }
     __syncthreads();
-    LZ_T(0);
     int m = 0;
     double th_lo = 0.0, th_hi = 0.0, ascale = 0.0, prev_lo = 0.0;
     bool done = false, have_prev = false;
@@ -1033,7 +1010,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
             for (int q = 0; q < 8; ++q) s1 += colp[q * 256 + tid];
             wi = rowp[tid] + s1;
         }
-        LZ_T(1);
         // ---- the recurrence's own terms first: w -= beta_{j-1} v_{j-1}, alpha_j = v_j'w, w -= alpha_j v_j.  (Taking them out
         // in the Gram-Schmidt sweep with everything else needs its second pass at EVERY step: they are the large components,
         // and with a basis orthogonal to delta the sweep then puts delta |alpha| / beta of them back along the old vectors.)
@@ -1045,7 +1021,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
         double alpha = lz_sum256(tid < 256 ? wi * vs[tid] : 0.0, red, 2);
         if (tid < 256) { wi = fma(-alpha, vs[tid], wi); wsv[tid] = wi; }
         __syncthreads();
-        LZ_T(2);
         // ---- then w orthogonal to v_0 .. v_j by classical Gram-Schmidt: what it finds is rounding noise while the basis is
         // orthogonal; a second sweep when the first one took out a sizeable part of w ("twice is enough")
         double nrm2 = 0.0;
@@ -1075,7 +1050,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
                 if (k <= j && l8 == 0) hb[k] = h;
             }
             __syncthreads();
-            LZ_T(3);
             alpha += hb[j];
             double h2 = 0.0;                                   // |h|^2: what this sweep takes out of w
             {
@@ -1110,7 +1084,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
                 }
             }
             nrm2 = lz_sum256(tid < 256 ? wi * wi : 0.0, red, pass);        // (its barrier also publishes wsv)
-            LZ_T(4);
             // (Daniel, Gragg, Kaufman, Stewart.)  h2 is the same in every thread below 256; thread 0 decides
             if (pass == 0) {
                 if (tid == 0) s_first = (nrm2 >= 0.5 * (nrm2 + h2)) ? 1 : 0;
@@ -1123,7 +1096,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
         const double beta = sqrt(nrm2);
         if (tid == 0) { al[j] = alpha; be[j] = beta; }
         m = j + 1;
-        LZ_T(5);
         // ---- convergence test
         ascale = fmax(ascale, fabs(alpha) + beta);
         const bool check = m == r || !(beta > 1e-13 * ascale) || (m >= 24 && ((m <= 64 && (m & 7) == 0) || (m & 15) == 0));
@@ -1203,7 +1175,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
             }
             th_lo = lo; th_hi = hi;
             prev_lo = want_max ? lo : hi; have_prev = true;
-            LZ_T(7);
             if (tid == 0) {
                 // the Ritz vector's last component: (T - theta I) s = 0 solved from the BOTTOM with s_m = 1 --
                 //   s_{i-1} = ((theta - a_i) s_i - b_i s_{i+1}) / b_{i-1}
@@ -1227,7 +1198,6 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
             __syncthreads();
             done = (s_res[0] <= 1e-11 * s_res[1]) || !(beta > 1e-14 * s_res[1]) || m == r;
         }
-        LZ_T(6);
         if (!done) {
             const double vn = wi / beta;
             if (tid < 256) { vs[tid] = vn; vput(j + 1, tid, vn); }
@@ -1345,9 +1315,7 @@ static int lg_tridiag(hipStream_t s, LargeWs *w, const double *M, const double *
         if (!work) { cip_set_error("large S cone: the tridiagonalisation above order 1024 needs a work matrix"); return CIP_E_INVALID; }
         return lg_tridiag_stepped(s, w, M, dscale, r, work);
     }
-    // CIP_LG_TRIDIAG1=0: the cooperative kernel at every order (A/B runs)
-    static const int one_wg = [] { const char *e = getenv("CIP_LG_TRIDIAG1"); return (e && atoi(e) == 0) ? 0 : 1; }();
-    if (one_wg && r <= 256) {
+    if (r <= 256) {
         const size_t shm1 = T1_LDS_DOUBLES * sizeof(double);
         if ((rc = lg_set_attr((const void *)k_lg_tridiag1, shm1))) return rc;
         hipLaunchKernelGGL(k_lg_tridiag1, dim3(1), dim3(512), shm1, s, M, w->rp, dscale, r, w->vec + 1 * w->rp, w->vec + 2 * w->rp, (const int *)nullptr);
@@ -1424,49 +1392,6 @@ __global__ void k_lg_pubflag(const unsigned *sweepflag, const int *info_a, const
         __hip_atomic_store(host + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-static int lg_warm(void) {
-    static const int on = [] { const char *e = getenv("CIP_LG_WARM"); return e ? atoi(e) : 1; }();
-    return on;
-}
-// ---- development aid (CIP_LG_CHECKSUM=1): order-independent checksums (integer sums of the bit patterns) of the NT scaling's
-// intermediates, per call and stage, printed when the workspace is destroyed -- two runs of one program must print the same table
-// (tools/sdp640_repeat.py: a difference names the first racy stage)
-__global__ __launch_bounds__(256) void k_lg_checksum(const double *x, long n, unsigned long long *out) {
-    unsigned long long acc = 0;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) acc += (unsigned long long)__double_as_longlong(x[e]);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) atomicAdd(out, acc);
-}
-__global__ __launch_bounds__(256) void k_lg_sumsq(const double *x, long n, unsigned long long *out) {     // sum of squares as a double in a 64-bit slot (atomic adds: good to rounding)
-    double acc = 0.0;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) acc += x[e] * x[e];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) atomicAdd((double *)out, acc);
-}
-static unsigned long long *g_lg_cks = nullptr;      // LG_CKS_CALLS calls x 16 stages
-#define LG_CKS_CALLS 4096
-static int g_lg_cks_call = 0;
-static int lg_cks_on(void) { static const int on = [] { const char *e = getenv("CIP_LG_CHECKSUM"); return e ? atoi(e) : 0; }(); return on; }
-static void lg_cks(hipStream_t s, int stage, const double *x, long n) {
-    if (!lg_cks_on() || g_lg_cks_call >= LG_CKS_CALLS) return;
-    if (!g_lg_cks) { (void)hipMalloc((void **)&g_lg_cks, LG_CKS_CALLS * 16 * 8); (void)hipMemset(g_lg_cks, 0, LG_CKS_CALLS * 16 * 8); }
-    if (stage >= 12) hipLaunchKernelGGL(k_lg_sumsq, dim3(256), dim3(256), 0, s, x, n, g_lg_cks + g_lg_cks_call * 16 + stage);
-    else hipLaunchKernelGGL(k_lg_checksum, dim3(256), dim3(256), 0, s, x, n, g_lg_cks + g_lg_cks_call * 16 + stage);
-}
-void cip_lg_cks_dump(void) {
-    if (!g_lg_cks) return;
-    static unsigned long long h[LG_CKS_CALLS * 16];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpy(h, g_lg_cks, sizeof(h), hipMemcpyDeviceToHost);
-    for (int c = 0; c < g_lg_cks_call && c < LG_CKS_CALLS; ++c) {
-        fprintf(stderr, "cks call %d:", c);
-        for (int q = 0; q < 12; ++q) fprintf(stderr, " %016llx", h[c * 16 + q]);
-        { double a, b; __builtin_memcpy(&a, &h[c * 16 + 12], 8); __builtin_memcpy(&b, &h[c * 16 + 13], 8); fprintf(stderr, " | |G_in|^2 %.17g |G_out|^2 %.17g rel %.3e", a, b, (b - a) / a); }
-        fprintf(stderr, "\n");
-    }
-    (void)hipMemset(g_lg_cks, 0, LG_CKS_CALLS * 16 * 8);
-    g_lg_cks_call = 0;
-}
 // nestod_sdc for one large cone (index li among the large cones)
 int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, const double *v, const double *sv, double *scal,
                      double *lambda, int *flag) {
@@ -1477,12 +1402,10 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
     hipLaunchKernelGGL(k_lg_mat, lg_grid(n2), dim3(256), 0, s, sv + cd.off, 1L, 0L, w->Ks, r, rp, 1.0);
     if ((rc = cip_ldlt_factor(s, w->Kz, rp, rp, w->wz))) return rc;                 // Lz (unit) and d_z  (:202-203)
     if ((rc = cip_ldlt_factor(s, w->Ks, rp, rp, w->ws))) return rc;
-    lg_cks(s, 0, w->Kz, n2); lg_cks(s, 1, w->Ks, n2);
     hipLaunchKernelGGL(k_lg_flag, dim3(1), dim3(64), 0, s, w->wz.info, w->ws.info, flag);
     hipLaunchKernelGGL(k_lg_tfac, lg_grid(n2), dim3(256), 0, s, w->Kz, w->wz.dvec, w->Tz, rp);
     hipLaunchKernelGGL(k_lg_tfac, lg_grid(n2), dim3(256), 0, s, w->Ks, w->ws.dvec, w->Ts, rp);
     if ((rc = lg_gemm(s, w->G, 0, w->Tz, 0, w->Ts, 0, rp, 1))) return rc;           // G = Lz' Ls          (:204)
-    lg_cks(s, 2, w->G, n2);
     // Round 5: WARM START of the one-sided Jacobi.  svd(G) = U Sigma V' is needed for U and Sigma only (:204-208), and the
     // Jacobi below may start from G W for ANY orthogonal W: the left singular vectors and the singular values are those of G.
     // Between two interior-point iterations the NT scaling moves little, so with W = the right singular vectors V of the previous
@@ -1493,23 +1416,20 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
     // only to cond(G) eps, and a W that is not orthogonal would change the answer by that much).  Four extra 256^3 products per
     // scaling (~5 us each).  The first scaling after the packed scaling was replaced from outside (cip_set_scaling_identity at the
     // start of every interior-point solve, cip_set_scaling_packed) starts cold: a solve's results do not depend on what the handle
-    // did before.  CIP_LG_WARM=0 switches it off.
+    // did before.
     const dim3 tg(rp / 32, rp / 32);
     double *Vw = w->Vw + (size_t)li * n2;
     unsigned long long *vst = w->vstate + 2 * (size_t)li;
-    const bool keep_v = lg_warm() != 0;
-    const bool jacobi_warm = keep_v && w->have_v[li];
-    if (keep_v) CIP_HIP_CHECK(hipMemcpyAsync(w->G0, w->G, sizeof(double) * n2, hipMemcpyDeviceToDevice, s));
+    const bool jacobi_warm = w->have_v[li] != 0;
+    CIP_HIP_CHECK(hipMemcpyAsync(w->G0, w->G, sizeof(double) * n2, hipMemcpyDeviceToDevice, s));
     if (jacobi_warm) {
         hipLaunchKernelGGL(k_lg_transpose, tg, dim3(256), 0, s, (const double *)Vw, w->W1, rp, (const double *)nullptr);      // V'
         if ((rc = lg_gemm(s, w->W2, 0, w->W1, 0, w->W1, 0, rp, 1))) return rc;                                              // V'V
         hipLaunchKernelGGL(k_lg_ns, lg_grid(n2), dim3(256), 0, s, w->W2, rp, vst);                                          // 1.5 I - 0.5 V'V (symmetric); max |V'V - I|
         if ((rc = lg_gemm(s, w->W1, 0, Vw, 0, w->W2, 0, rp, 1))) return rc;                                                 // Vn = V (1.5 I - 0.5 V'V)
         hipLaunchKernelGGL(k_lg_transpose, tg, dim3(256), 0, s, (const double *)w->W1, w->W2, rp, (const double *)nullptr);  // Vn'
-        lg_cks(s, 3, w->W2, n2);
         if ((rc = lg_gemm(s, w->G, 0, w->G0, 0, w->W2, 0, rp, 1))) return rc;                                               // G <- G Vn
         hipLaunchKernelGGL(k_lg_warm_gate, lg_grid(n2), dim3(256), 0, s, w->G, (const double *)w->G0, n2, (const unsigned long long *)vst);   // ... unless V is not fit for it: G <- G0 (cold)
-        lg_cks(s, 4, w->G, n2);
     }
     bool left_cone = false;                                 // either Cholesky met a non-positive pivot (read back with the sweep flags)
     {
@@ -1517,13 +1437,9 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
         // 3.95 / 3.11 / 3.25 / 4.48 ms per NT scaling -- a rotation round is bound by the hand-over between the wave's lane groups
         // (LDS + workgroup barrier: fewer waves per workgroup, shorter rounds), an outer round costs ~3 us (block exchange through
         // L2 + launch boundary) and their number doubles as the blocks halve), 16 at order 512 (16 workgroups), 8 at order 1024.
-        // CIP_LG_JACOBI_B = 4 / 8 / 16 / 32 overrides at order 256.
-        static const int bforce = [] { const char *e = getenv("CIP_LG_JACOBI_B"); return e ? atoi(e) : 0; }();
-        const int b = rp > 1024 ? 4 : rp > 512 ? 8 : (rp <= 256 ? ((bforce == 32 || bforce == 16 || bforce == 4) ? bforce : 8) : 16);       // order 2048: two blocks of 4 columns are a CU's LDS
-        const int nt = rp > 512 ? b * 64 : b * (rp / 8);           // 512 (order 256, b = 16), 256 (b = 8), 1024 (order 512) or 512 (order 1024: 64 lanes x 16 elements per column)
+        const int b = rp > 1024 ? 4 : rp > 512 ? 8 : rp > 256 ? 16 : 8;       // order 2048: two blocks of 4 columns are a CU's LDS
         const size_t shm = (size_t)2 * b * lg_pitch(rp) * sizeof(double);
         CIP_HIP_CHECK(hipMemsetAsync(w->ctr, 0, 1024, s));
-        lg_cks(s, 12, w->G, n2);
         if ((rc = cip_prof_slot_begin(CIP_PROF_JACOBI, s, 0.0))) return rc;
         // ONE LAUNCH PER PHASE (round 5, second session; the only form since round 6): the pairs inside the blocks, then each round of
         // the tournament over blocks, the launch boundary in place of a grid barrier.  0 differing results in 11 500 repeated scalings
@@ -1557,15 +1473,13 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
             }
             return 0;
         };
-        if (rp == 256 && bforce == 116) {                  // A/B form (round 5): 16-column blocks, 16 lanes x 16 elements per column, 4 waves, 8 workgroups -- half the
-                                                           // outer rounds, shorter lane sums, and SLOWER: config 4 8.41 against 8.03 ms per iteration
-            rc = run(k_lg_jacobi<256, 16>, 256, 16, (size_t)2 * 16 * lg_pitch(rp) * sizeof(double));
-        } else if (rp > 1024) rc = run(k_lg_jacobi<256, 32>, 256, b, shm);
-        else if (rp > 512) rc = run(k_lg_jacobi<512, 16>, 512, b, shm);
-        else if (nt == 128) rc = run(k_lg_jacobi<128>, 128, b, shm);
-        else if (nt == 256) rc = run(k_lg_jacobi<256>, 256, b, shm);
-        else if (nt == 512) rc = run(k_lg_jacobi<512>, 512, b, shm);
-        else rc = run(k_lg_jacobi<1024>, 1024, b, shm);
+        // one form per padded order; lanes per column x elements per lane: 32 x 8, 64 x 8, 64 x 16, 64 x 32
+        switch (rp) {
+            case 256: rc = run(k_lg_jacobi<256>, 256, b, shm); break;
+            case 512: rc = run(k_lg_jacobi<1024>, 1024, b, shm); break;
+            case 1024: rc = run(k_lg_jacobi<512, 16>, 512, b, shm); break;
+            default: rc = run(k_lg_jacobi<256, 32>, 256, b, shm); break;      // 2048
+        }
         const int rce = cip_prof_slot_end(CIP_PROF_JACOBI, s);      // (also on the error paths: an unpaired event would mis-pair every later collect)
         if (rc) return rc;
         if (rce) return rce;
@@ -1576,7 +1490,7 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
             return CIP_E_SINGULAR;
         }
     }
-    if (getenv("CIP_LG_DEBUG")) {
+    if (cip_env_set("CIP_LG_DEBUG")) {
         unsigned hc[64];
         CIP_HIP_CHECK(hipMemcpyAsync(hc, w->ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
         CIP_HIP_CHECK(hipStreamSynchronize(s));
@@ -1585,14 +1499,11 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
         fprintf(stderr, "[lg] jacobi: %d sweeps with a rotation above cos^2 = 1e-16%s\n", sweeps, left_cone ? " (iterate outside the cone)" : "");
     }
     double *lam = w->vec;
-    lg_cks(s, 5, w->G, n2); lg_cks(s, 13, w->G, n2);
     hipLaunchKernelGGL(k_lg_colnorm, dim3((rp + 3) / 4), dim3(256), 0, s, w->G, lam, rp);
-    lg_cks(s, 6, lam, rp);
-    if (keep_v) {                                                                                                           // V = G0' (A_f Sigma^-2) for the next call
+    {                                                                                                                       // V = G0' (A_f Sigma^-2) for the next call
         hipLaunchKernelGGL(k_lg_transpose, tg, dim3(256), 0, s, (const double *)w->G, w->W1, rp, (const double *)lam);        // (A_f Sigma^-2)'
         hipLaunchKernelGGL(k_lg_transpose, tg, dim3(256), 0, s, (const double *)w->G0, w->W2, rp, (const double *)nullptr);   // G0'
         if ((rc = lg_gemm(s, Vw, 0, w->W2, 0, w->W1, 0, rp, 1))) return rc;
-        lg_cks(s, 7, Vw, n2);
         // fit for the next call's warm start?  The host knows the Cholesky flags from the sweep read-back (an iterate outside the
         // cone leaves NaN in G, lam and V: round 5 kept such a V, and the next scaling of a perfectly interior iterate came out NaN
         // with a clean flag); the device-side word also covers non-finite / non-positive singular values (k_lg_warm_gate reads it)
@@ -1607,8 +1518,6 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
     hipLaunchKernelGGL(k_lg_store, lg_grid(n2 > cd.dim ? n2 : cd.dim), dim3(256), 0, s, w->Tz, w->Ts, R, Ri, w->Rip + LG_NPAD * (size_t)li * n2,
                        lam, lambda ? lambda + cd.off : nullptr, r, rp, cd.dim);
     if (lambda) hipLaunchKernelGGL(k_lg_lambda_diag, lg_grid(r), dim3(256), 0, s, lam, lambda + cd.off, r);
-    lg_cks(s, 8, w->Tz, n2); lg_cks(s, 9, w->Ts, n2);
-    if (lg_cks_on()) g_lg_cks_call += 1;
     CIP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1631,7 +1540,7 @@ int cip_sdp_large_refresh(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li,
 // Measured: config 4 8.17-8.22 -> 7.88-8.00 ms per iteration; tests/test_gpu_sdp.py (LAPACK on hard spectra, the certificate's
 // self-test, five trajectories) green in both modes.
 static int lz_reorth(void) {
-    static const int on = [] { const char *e = getenv("CIP_LG_LANCZOS_REORTH"); return e ? atoi(e) : 0; }();
+    static const int on = cip_env_int("CIP_LG_LANCZOS_REORTH", 0);
     return on;
 }
 // 2 (default; CIP_LG_LANCZOS changes it): the max-step's extreme eigenvalue by k_lg_lanczos1 at orders <= 256 + the inertia certificate
@@ -1639,7 +1548,7 @@ static int lz_reorth(void) {
 // tridiagonalisation + Sturm multisection at every order (A/B runs, tests).  on < 0 only reads; returns the previous setting
 #include <atomic>
 int cip_sdp_large_lanczos(int on) {
-    static std::atomic<int> mode{[] { const char *e = getenv("CIP_LG_LANCZOS"); const int v = e ? atoi(e) : 2; return (v >= 0 && v <= 3) ? v : 2; }()};
+    static std::atomic<int> mode{[] { const int v = cip_env_int("CIP_LG_LANCZOS", 2); return (v >= 0 && v <= 3) ? v : 2; }()};
     const int prev = mode.load();
     if (on >= 0 && on <= 3) mode.store(on);
     return prev;
@@ -1756,7 +1665,7 @@ int cip_sdp_large_maxstep(hipStream_t s, LargeWs *w, const ConeDesc &cd, const d
     hipLaunchKernelGGL(k_lg_mat, lg_grid(n2), dim3(256), 0, s, x + cd.off, 1L, 0L, Kx, r, rp, 1.0);
     if ((rc = cip_ldlt_factor(s, Kx, rp, rp, wx))) return rc;                 // X = L D L'
     const double *Xi = (wx.Bs == CIP_NB) ? wx.Linv : wx.X;                // inv(L_unit)
-    if (rp <= 256 && lg_small_gemm()) {                                             // inv(L) D, D = mat(d) read from the vector
+    if (rp <= 256) {                                             // inv(L) D, D = mat(d) read from the vector
         hipLaunchKernelGGL((k_gemm_nt_small<true, false>), dim3(rp / 16, rp / 16), dim3(256), 0, s, Xi, (long)rp, d + cd.off, 0L, M2, (long)rp, rp, r);
     } else {
         hipLaunchKernelGGL(k_lg_mat, lg_grid(n2), dim3(256), 0, s, d + cd.off, 1L, 0L, M1, r, rp, 0.0);
@@ -1822,7 +1731,7 @@ int cip_sdp_large_apply(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, i
     const int which = (mode == CIP_OP_F) ? 3 : (mode == CIP_OP_FT) ? 2 : (mode == CIP_OP_FINV) ? 1 : 0;
     const double *Q = w->Rip + (LG_NPAD * (size_t)li + which) * n2;
     int rc;
-    if (rp <= 256 && lg_small_gemm()) {
+    if (rp <= 256) {
         // two launches: mat(x) is read from the vector by the first product, the second writes vecm (k_gemm_nt_small<BVEC / CVEC>)
         hipLaunchKernelGGL((k_gemm_nt_small<true, false>), dim3(rp / 16, rp / 16), dim3(256), 0, s, Q, (long)rp, x + cd.off, 0L, w->M2, (long)rp, rp, r);
         hipLaunchKernelGGL((k_gemm_nt_small<false, true>), dim3(rp / 16, rp / 16), dim3(256), 0, s, (const double *)w->M2, (long)rp, Q, (long)rp, out + cd.off, 0L, rp, r);

@@ -221,52 +221,12 @@ __global__ __launch_bounds__(64) void k_dots2(const double *partial, double *out
     }
 }
 
-// Round 5: both stages in ONE launch.  The block that completes a dot's DOT_NB partial sums (a counter per dot, left at zero again
-// for the next call) adds them up exactly as k_dots2 does -- the partials read with agent-scope loads: they were written by other
-// CUs, and this CU's vector cache may still hold the previous call's values at the same addresses.  Same bits, one dependent
-// launch (~4 us) less per dot-product group, three or four groups per interior-point iteration -- and NOT faster: the in-launch
-// hand-off (write-through store, wait, atomic, coherent re-load) costs what the launch boundary does (8 / 64 problems of order 2048
-// in lock-step: 16.7 / 79.8 ms per pass against 15.9 / 78.3 with two launches).  Off by default; CIP_DOTS_FUSED=1 selects it.
-__global__ __launch_bounds__(256) void k_dots(const DotTable tab, double *partial, unsigned *cnt, double *out, double *gather, CipBatch cb) {
-    CIP_BATCH_GUARD(cb);
-    __shared__ double sh[4];
-    __shared__ unsigned last;
-    DotPtrs d = tab.p[blockIdx.y];
-    CIP_BO3(cb, d.x, d.y, partial);
-    CIP_BO2(cb, cnt, out);
-    double s = 0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < d.len; i += (long)DOT_NB * 256) s += d.x[i] * d.y[i];
-    s = wsum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // written through (agent-scope store), waited for, then counted: NO release / acquire fences -- on this chip an agent-scope
-        // release is an L2 write-back, and tens of thousands of blocks doing one each made a 64-problem lock-step pass 8 % slower
-        // than the two-launch form (the library's other in-launch hand-offs are built the same way: diag.hip st_pub / ld_pub)
-        __hip_atomic_store(&partial[blockIdx.y * DOT_NB + blockIdx.x], (sh[0] + sh[1]) + (sh[2] + sh[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last = __hip_atomic_fetch_add(&cnt[blockIdx.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == DOT_NB - 1;
-    }
-    __syncthreads();
-    if (last && threadIdx.x < 64) {
-        asm volatile("" ::: "memory");
-        double t = (threadIdx.x < DOT_NB) ? __hip_atomic_load(&partial[blockIdx.y * DOT_NB + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-        t = wsum(t);
-        if (threadIdx.x == 0) {
-            out[blockIdx.y] = t;
-            if (gather) gather[blockIdx.z * CIP_GATHER + blockIdx.y] = t;
-            __hip_atomic_store(&cnt[blockIdx.y], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 int cip_dots(hipStream_t s, int count, const double *const *x_host, const double *const *y_host, const int *len_host,
-             double *scratch_dev, void *ptrs_dev, double *out_host) {
+             double *scratch_dev, double *out_host) {
     if (count <= 0) return 0;
     if (count > DOT_MAX) { cip_set_error("dots: count > %d", DOT_MAX); return -1; }
     DotTable tab = {};
     for (int i = 0; i < count; ++i) { tab.p[i].x = x_host[i]; tab.p[i].y = y_host[i]; tab.p[i].len = len_host[i]; tab.p[i].pad = 0; }
-    (void)ptrs_dev;                                  // (the device copy of the table: unused since the table is a kernel argument)
     double *partial = scratch_dev;
     double *out = scratch_dev + DOT_MAX * DOT_NB;
     const CipBatchCtx &bc = cip_tl_bz;
@@ -274,15 +234,8 @@ int cip_dots(hipStream_t s, int count, const double *const *x_host, const double
     int rc;
     if ((rc = cip_host_scratch(&hs))) return rc;
     const bool direct = bc.B <= 1 && count <= 512;                 // one problem: the sums go straight to the host
-    static const int fused = [] { const char *e = getenv("CIP_DOTS_FUSED"); return e ? atoi(e) : 0; }();
-    if (fused) {
-        unsigned *cnt = (unsigned *)(scratch_dev + DOT_MAX * DOT_NB + DOT_MAX);         // zeroed when the scratch was allocated; every call leaves it zero
-        cip_launch_b(k_dots, dim3(DOT_NB, count), dim3(256), 0, s, tab, partial, cnt, direct ? hs.dev : out,
-                     bc.B > 1 ? bc.gather_dev : (double *)nullptr);
-    } else {
-        cip_launch_b(k_dots1, dim3(DOT_NB, count), dim3(256), 0, s, tab, partial);
-        cip_launch_b(k_dots2, dim3(count), dim3(64), 0, s, (const double *)partial, direct ? hs.dev : out, bc.B > 1 ? bc.gather_dev : (double *)nullptr);
-    }
+    cip_launch_b(k_dots1, dim3(DOT_NB, count), dim3(256), 0, s, tab, partial);
+    cip_launch_b(k_dots2, dim3(count), dim3(64), 0, s, (const double *)partial, direct ? hs.dev : out, bc.B > 1 ? bc.gather_dev : (double *)nullptr);
     CIP_HIP_CHECK(hipGetLastError());
     if (bc.B > 1) {
         // out_host: B x count, problem-major; masked-off problems keep whatever the gather buffer held (callers ignore them)
@@ -323,7 +276,7 @@ int cip_host_scratch(CipHostScratch *out) {
     return 0;
 }
 int cip_wait(hipStream_t s) {
-    static const int spin = [] { const char *e = getenv("CIP_SPIN_WAIT"); return (e && atoi(e) == 0) ? 0 : 1; }();
+    static const int spin = cip_env_int("CIP_SPIN_WAIT", 1) != 0;
     if (!spin) { CIP_HIP_CHECK(hipStreamSynchronize(s)); return 0; }
     const int rc = scratch_init();
     if (rc) return rc;

@@ -5,6 +5,7 @@
 #include <vector>
 #include <cstdlib>
 void cip_set_error(const char *fmt, ...) {}
+int cip_env_int(const char *, int dflt) { return dflt; }      // (stand-alone build: every switch at its default)
 thread_local CipGraphBuilder *cip_tl_builder = nullptr;
 thread_local CipBatchCtx cip_tl_bz = {1, 0, 1ull, nullptr, nullptr};
 int main(int argc, char **argv) {
