@@ -111,6 +111,12 @@ SIGNATURES = {
                                           C.c_int]),
     "cip_gemm_nt_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "cip_qrcp_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "cip_imcols_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "cip_qrcp_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_int_p,
+                               c_double_p, c_int_p]),
+    "cip_imcols_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, c_int_p,
+                                 c_int_p, c_int_p, c_double_p]),
     "cip_kkt_order": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "cip_get_kkt_matrix": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cip_assemble_only": (C.c_int, [C.c_void_p]),

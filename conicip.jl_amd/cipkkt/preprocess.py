@@ -14,6 +14,10 @@ of level-2 BLAS.  scipy has no sparse rank-revealing QR, so the full-row-rank ca
 case in which nothing is changed -- is CERTIFIED first on the n x n Gram matrix (`_full_row_rank`: sigma_min from `eigvalsh`,
 sparse blocks enter through sparse products, nothing wider than n x n is ever dense); only when the certificate does not hold
 does the pivoted QR run, and above `DENSE_QR_LIMIT` entries it refuses with a message instead of allocating.
+
+Device QR.  `preprocess_conicIP(..., rank_solver="device")` hands the uncertified cases to `qrcp.imcols_hip` instead: the same
+algorithm as a column-pivoted Householder QR in HIP (csrc/qrcp.hip), no size limit, the wide matrix concatenated on the device.
+The host path is the default and is unchanged.
 """
 import numpy as np
 import scipy.linalg as sla
@@ -86,8 +90,15 @@ def imcols(A, b, eps=1e-8):
     return [], False
 
 
-def preprocess_conicIP(Q, c, A, b, cone_dims, G=None, d=None, **options):
-    """`conicIP` behind the reference's rank pre-solve (src/preprocessor.jl:43-96); same keywords as `conicIP`."""
+def preprocess_conicIP(Q, c, A, b, cone_dims, G=None, d=None, rank_solver="host", **options):
+    """`conicIP` behind the reference's rank pre-solve (src/preprocessor.jl:43-96); same keywords as `conicIP`.
+    rank_solver: where the rank-revealing QR runs when the full-row-rank certificate does not hold -- "host" (LAPACK geqp3, refused
+    above `DENSE_QR_LIMIT` entries) or "device" (`imcols_hip`: no size limit, [Q A' G'] is put together on the device)."""
+    if rank_solver not in ("host", "device"):
+        raise ValueError("preprocess_conicIP: rank_solver must be \"host\" or \"device\", not %r" % (rank_solver,))
+    on_device = rank_solver == "device"
+    if on_device:
+        from .qrcp import imcols_hip
     c = np.asarray(c, dtype=np.float64).reshape(-1)
     n, m = c.size, A.shape[0]
     G = np.zeros((0, n)) if G is None else G
@@ -96,12 +107,16 @@ def preprocess_conicIP(Q, c, A, b, cone_dims, G=None, d=None, **options):
     Gd = _dense(G)
     if p > 0 and _full_row_rank([G if sp.issparse(G) else Gd], 1e-8):
         keep_p, primal_ok = list(range(p)), True                    # G has full row rank: G y = d is consistent, nothing to drop
+    elif on_device:
+        keep_p, primal_ok = imcols_hip(G if sp.issparse(G) else Gd, d)
     else:
         keep_p, primal_ok = imcols(Gd, d)
     At = (A.T.tocsr() if sp.issparse(A) else np.asarray(A, dtype=np.float64).T) if m > 0 else np.zeros((n, 0))
     dual_blocks = [Q, At, Gd[keep_p, :].T]
     if _full_row_rank(dual_blocks, 1e-8):
         keep_d, dual_ok = list(range(n)), True                      # [Q A' G'] has full row rank: every dual equation is determined
+    elif on_device:
+        keep_d, dual_ok = imcols_hip(dual_blocks, c)
     else:
         wide = n * (n + m + len(keep_p))
         if wide > DENSE_QR_LIMIT:

@@ -287,6 +287,33 @@ int cip_ldlt_solve_many_dev(void *hip_stream, const double *K, int N, int ld, co
 int cip_gemm_nt_dev(void *hip_stream, int M, int N, int K, double alpha,
                     const double *A, int lda, const double *B, int ldb, double *C, int ldc, int lower_only);
 
+/* ---- rank-revealing (column-pivoted) Householder QR and the pre-solve's `imcols` on top of it (device pointers), usable on
+ * their own.  M is len x cnt column-major with leading dimension ld.  Argument rules: len, cnt >= 0; ld >= max(len, 1); stop, eps
+ * >= 0 and finite; M, workspace (and b, rows_host for cip_imcols_dev) non-NULL when len * cnt > 0; k_host / nrows_host /
+ * consistent_host non-NULL -- else CIP_E_INVALID before anything is enqueued; len * cnt == 0: no-op with k = 0 (no rows,
+ * consistent).  A NaN or Inf entry (or one whose square overflows): CIP_E_INVALID "non-finite entry".  Both calls wait for their
+ * result.  The same input gives the same bits on every run.
+ * workspace for cip_qrcp_dev / cip_imcols_dev (the latter includes a working copy of M) */
+int cip_qrcp_workspace_bytes(int len, int cnt, size_t *bytes);
+int cip_imcols_workspace_bytes(int len, int cnt, size_t *bytes);
+/* M is overwritten with LAPACK geqp3's result layout: columns physically permuted, R on and above the diagonal, the reflector
+ * tails (leading 1 implicit) below it in the first k columns; rows len..ld-1 are never read or written.  Column j of the result
+ * is column piv_host[j] of the input (0-based).  The factorisation stops at the first step whose largest remaining column norm
+ * is <= stop (every later |R_jj| would be): *k_host = steps done, columns k.. then hold the updated, unfactored remainder.
+ * piv_host[cnt], rdiag_host[min(len,cnt)] (the diagonal of R, first *k_host entries valid), tau_dev[min(len,cnt)] (device) may
+ * be NULL.  16-byte accesses when ld is even and M 16-byte aligned; same bits either way. */
+int cip_qrcp_dev(void *hip_stream, double *M, int len, int cnt, int ld, double stop, void *workspace,
+                 double *tau_dev, int *piv_host, double *rdiag_host, int *k_host);
+/* imcols of the reference (src/preprocessor.jl:10-28) for the rows of A (cnt rows of length len), handed over as
+ * M = A' column-major -- i.e. A in row-major order; M and b (device, cnt entries) are NOT modified.  A is scaled by 1 / ||A||_F,
+ * the QR runs with stop = eps on a working copy, the rows whose |R_jj| > eps are kept, x = A[R,:] \ b[R] is the minimum-norm
+ * solution Q1 R1^-T b_R with one refinement step, and the system counts as consistent when ||A x - b||_inf < eps over all rows.
+ * rows_host[cnt]: sorted 0-based kept rows, *nrows_host of them (also when inconsistent); *consistent_host 0/1; *resid_host =
+ * ||A x - b||_inf of the scaled system (may be NULL).  An empty or all-zero A: no rows, consistent (the reference's empty-R
+ * branch). */
+int cip_imcols_dev(void *hip_stream, const double *M, int len, int cnt, int ld, const double *b, double eps,
+                   void *workspace, int *rows_host, int *nrows_host, int *consistent_host, double *resid_host);
+
 /* ---- introspection (tests, bench) */
 int cip_kkt_order(const cip_handle *h, int *N, int *N_padded);
 int cip_get_kkt_matrix(cip_handle *h, double *K_host /* N_padded^2 */); /* assembled (before cip_factor) or factored */
