@@ -1301,10 +1301,8 @@ extern "C" int cip_gemm_nt_dev(void *stream, int M, int N, int K, double alpha, 
                       "lda >= M, ldb >= N, ldc >= M; M == N with lower_only)");
         return CIP_E_INVALID;
     }
-    GemmArgs g = {};
-    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.alpha = alpha;
-    g.lower = lower_only ? 1 : 0;
-    return cip_launch_gemm((hipStream_t)stream, EPI_ACCUM, g);
+    if (lower_only) return cip_gemm_lower((hipStream_t)stream, M, K, alpha, A, lda, B, ldb, C, ldc);
+    return cip_gemm_rect((hipStream_t)stream, M, N, K, alpha, A, lda, B, ldb, C, ldc);
 }
 
 // ------------------------------------------------------------------ introspection

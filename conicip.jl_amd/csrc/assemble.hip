@@ -304,14 +304,9 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
     h->ws.lazyC = nullptr;
     if (!h->A_sparse) {
         if ((rc = cip_cones_scale_At(s, h->cs, n, h->At, h->npad, h->Wt, h->npad))) return rc;
-        GemmArgs g = {};
-        g.A = h->Wt; g.lda = h->npad; g.B = h->Wt; g.ldb = h->npad;
-        g.C = h->K; g.ldc = h->ldk; g.M = h->npad; g.N = h->npad; g.K = h->mpad;
-        g.alpha = 1.0; g.lower = 1; g.Qin = h->Q; g.ldq = n; g.nvalid = n;
-        g.ksplit_ws = h->syrk_ws; g.ksplit_n = h->syrk_n; g.ksplit_len = h->syrk_len;
         // (algorithmic work of the Schur formation: m n^2 flop on the lower half)
         if ((rc = cip_prof_slot_begin(CIP_PROF_SYRK, s, (double)h->m * (double)n * (double)n * (cip_in_batch() ? (double)__builtin_popcountll(cip_tl_bz.mask) : 1.0)))) return rc;
-        if ((rc = cip_launch_gemm(s, EPI_SYRKQ, g))) return rc;
+        if ((rc = cip_syrk_schur(s, h->npad, h->mpad, n, 1.0, h->Wt, h->npad, h->Q, n, h->K, h->ldk, h->syrk_ws, h->syrk_n, h->syrk_len))) return rc;
         if ((rc = cip_prof_slot_end(CIP_PROF_SYRK, s))) return rc;
     } else {
         const int lazy_now = g_lazy_copy.load(std::memory_order_relaxed);
@@ -347,17 +342,11 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
     if (h->A_sparse && h->AtS) {
         // the S cones' part of A'(F'F)^-1 A: W = A_S' F^-1 by congruences on the dense block of their rows, then K += W W'
         if ((rc = cip_sdp_scale_At(s, h->cs, n, h->AtS, (long)h->npad, h->WtS, (long)h->npad))) return rc;
-        GemmArgs g = {};
-        g.A = h->WtS; g.lda = h->npad; g.B = h->WtS; g.ldb = h->npad;
-        g.C = h->K; g.ldc = h->ldk; g.M = h->npad; g.N = h->npad; g.K = h->mSpad; g.alpha = 1.0; g.lower = 1;
-        if ((rc = cip_launch_gemm(s, EPI_ACCUM, g))) return rc;
+        if ((rc = cip_gemm_lower(s, h->npad, h->mSpad, 1.0, h->WtS, h->npad, h->WtS, h->npad, h->K, h->ldk))) return rc;
     }
     if (h->A_sparse && h->nq > 0 && h->m > 0) {
         // after k_fill_rest: the rank-nq update touches whole 128-tiles (adds exact zeros outside [0,n)^2)
-        GemmArgs g = {};
-        g.A = h->Gm; g.lda = h->npad; g.B = h->Gm; g.ldb = h->npad;
-        g.C = h->K; g.ldc = h->ldk; g.M = h->npad; g.N = h->npad; g.K = h->nqpad; g.alpha = 1.0; g.lower = 1;
-        if ((rc = cip_launch_gemm(s, EPI_ACCUM, g))) return rc;
+        if ((rc = cip_gemm_lower(s, h->npad, h->nqpad, 1.0, h->Gm, h->npad, h->Gm, h->npad, h->K, h->ldk))) return rc;
     }
     CIP_HIP_CHECK(hipGetLastError());
     return 0;

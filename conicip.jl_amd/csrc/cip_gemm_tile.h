@@ -1,7 +1,31 @@
-// Device pieces of the fp64 MFMA GEMM shared by gemm_f64.hip and the fused diagonal + in-block-update kernel of diag.hip:
-// the 64x64 tile computation (gemm_tile_64) and the lock-step batch prologue of GEMM kernels.
+// Device pieces of the fp64 MFMA GEMM shared by gemm_f64.hip, the fused diagonal + in-block-update kernel of diag.hip, the
+// pre-multiplied solve neighbours of ldlt.hip and the single products of sdp_large.hip: the kernels' parameter block, the 64x64
+// tile computation (gemm_tile_64), the 16x16 split-k tile (gemm_tile_16_splitk) and the lock-step batch prologue of GEMM kernels.
 #pragma once
 #include "cip_internal.h"
+
+// epilogue of a tile body.  EPI_LAZYC: C = Cin + alpha acc with Cin = Qin (ldq), Cdiag[i] on its diagonal
+enum { EPI_ACCUM = 0, EPI_SYRKQ = 2, EPI_STORE = 3, EPI_LAZYC = 4 };
+
+// The GEMM kernels' parameter block, filled by the launchers of gemm_f64.hip (and, on the device, by the kernels that run a tile
+// body on operands of their own: diag.hip, ldlt.hip: k_solve_premul).  A kernel reads the fields of its form only.
+struct GemmArgs {
+    const double *A; long lda;   // M x K, element (i,k) at A[i + k*lda]
+    const double *B; long ldb;   // N x K, element (j,k) at B[j + k*ldb]
+    double *C; long ldc;         // M x N
+    int M, N, K;                 // M, N multiples of 128; K multiple of 16
+    double alpha;
+    int tiles;                   // batched 64-tile form: GEMM_TILES_*
+    // EPI_SYRKQ: C = Qin + alpha acc for i,j < nvalid (lower tiles); EPI_LAZYC: Cin
+    const double *Qin; long ldq; int nvalid;
+    const double *Cdiag;         // EPI_LAZYC: the diagonal of Cin
+    // batched forms: grid.y x bz independent problems (bz == 0 reads as 1), pointer strides in doubles
+    int bz;
+    long sAy, sAz, sBy, sBz, sCy, sCz;
+    double *Ct; long ldct, sCty, sCtz;   // EPI_STORE and the 16-tile form, optional: the result is also stored transposed, Ct[j + i*ldct]
+    // split-K Schur formation (cip_syrk_schur): `ksplit_n` slices of `ksplit_len` columns, one M x M image each in `ksplit_ws`
+    double *ksplit_ws; int ksplit_n, ksplit_len;
+};
 
 // Lock-step batches (cip_internal.h): grid.z = (own batch count, >= 1) x (problems); returns the launch's own z index
 // after shifting every operand pointer by the problem's slab offset; live = false: the problem is masked off.
@@ -27,10 +51,7 @@ __device__ __forceinline__ void gemm_own_batch(GemmArgs &g, unsigned oz) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Small-tile variant (64x64 C tile, wave = 32x32 = 2x2 MFMA tiles) for the latency-critical skinny
-// updates on the factorisation's critical path (in-block strip update):
-// 4x the workgroups and a quarter of the per-tile latency of the 128x128 kernel, at twice the LDS
-// traffic per flop -- these launches carry < 10 % of the flops.  Accumulate epilogue only.
+// The 64x64 tile of C (wave = 32x32 = 2x2 MFMA tiles), one epilogue per EPI_*; against the 128x128 tile: gemm_f64.hip's header
 #define SB 64
 // GLDS: operands go global -> LDS directly (`global_load_lds_dwordx4`: no staging registers, no ds_write pass).  The
 // [k][64 rows] LDS image is lane-linear for the staging pattern below -- a wave's 64 x 16 bytes are two consecutive k columns --
@@ -136,6 +157,44 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
                 }
             }
         }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ONE 16x16 tile of C = A B' per 256-thread workgroup, the k range [0, K) split over its four waves (K a multiple of 128), operands
+// from global memory (L2) straight into the MFMA lanes -- lane l supplies row l % 16, k = l / 16 of its operand tile -- no LDS
+// staging; the partial accumulators of waves 1..3 are added to wave 0's in wave order.  The operand order of gemm_tile_64: B's
+// rows first.  a: this lane's first element of A, A[i0 + l % 16, wave K/4 + l / 16]; fetch_b(kk): this lane's element of B kk
+// columns further on, B[j0 + l % 16, wave K/4 + l / 16 + kk]; store(q, c), called by wave 0 only: c = (A B')[i0 + l % 16, j0 + l / 16 + 4 q].
+// Every caller runs the same MFMAs on the same operands in the same order: same bits.
+template <class FetchB, class Store>
+__device__ __forceinline__ void gemm_tile_16_splitk(const double *a, long lda, int K, FetchB fetch_b, Store store) {
+    __shared__ double red[3][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int kq = K >> 2;
+    v4d acc0 = (v4d){0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
+    for (int k = 0; k < kq; k += 32) {
+        double av[8], bv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            av[u] = a[(long)(k + 4 * u) * lda];
+            bv[u] = fetch_b(k + 4 * u);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u += 2) {
+            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[u], av[u], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[u + 1], av[u + 1], acc1, 0, 0, 0);
+        }
+    }
+    acc0 += acc1;
+    if (wave > 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[wave - 1][q][lane] = acc0[q];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) store(q, ((acc0[q] + red[0][q][lane]) + red[1][q][lane]) + red[2][q][lane]);
+    }
 }
 
 // ---- a 64x64 tile of C += alpha A B' with K = 128 for a GROUP of four waves that shares its workgroup with another group

@@ -92,32 +92,32 @@ inline void cip_launch_b(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t
 }
 
 // ---------------------------------------------------------------- GEMM (gemm_f64.hip)
-enum { EPI_ACCUM = 0, EPI_SYRKQ = 2, EPI_STORE = 3, EPI_LAZYC = 4 };     // EPI_LAZYC: C = Cin + alpha acc with Cin = Qin (ldq), Cdiag[i] on its diagonal
-
-struct GemmArgs {
-    const double *A; long lda;   // M x K, element (i,k) at A[i + k*lda]
-    const double *B; long ldb;   // N x K, element (j,k) at B[j + k*ldb]
-    double *C; long ldc;         // M x N
-    int M, N, K;                 // M, N multiples of 128; K multiple of 16
-    double alpha;
-    int lower;                   // 1: only tiles with bi >= bj (M == N); 2 / 3 (batched overwrite form): only 64-tiles with bi <= bj / bi >= bj
-    // EPI_SYRKQ: C = Qin + acc for i,j < nvalid (lower tiles)
-    const double *Qin; long ldq; int nvalid;
-    // batching (EPI_ACCUM only): grid.y x grid.z independent problems, pointer strides in doubles
-    int by, bz;
-    long sAy, sAz, sBy, sBz, sCy, sCz;
-    int overwrite;               // EPI_ACCUM: C = alpha*acc instead of C += alpha*acc
-    double *Ct; long ldct, sCty, sCtz;   // 128-tile EPI_ACCUM only, optional: the result is also stored transposed, Ct[j + i*ldct]
-    const double *Cdiag;         // EPI_LAZYC: the diagonal of Cin
-    int force64;                 // plain accumulate form: quarter tiles (k_gemm_nt_64) whatever the tile count
-    int tiny16;                  // batched overwrite form: one 16x16 tile per workgroup, k split over its waves (k_gemm_nt_16_batched; K % 128 == 0)
-    // EPI_SYRKQ with few output tiles and a long K (round 4): the k range is cut into `ksplit_n` slices of `ksplit_len` columns, every
-    // slice's product goes to its own M x M image in `ksplit_ws`, a second launch adds them up in slice order together with Qin
-    double *ksplit_ws; int ksplit_n, ksplit_len;
-};
-// how cip_launch_gemm(EPI_SYRKQ) would split an (M x M, K) Schur formation: number of slices (1: no split) and their length
+// One launcher per form of C (+)= alpha A B' (all column-major): A is M x K with element (i, k) at A[i + k*lda], B is N x K with
+// (j, k) at B[j + k*ldb]; M, N multiples of 128, K of 16.  Which kernel and tile serve a form, and why: gemm_f64.hip.
+// C -= / += alpha A B' on the 128-tiles of the lower triangle (M == N), in 64x64 quarter tiles; the tiles above stay as they were
+int cip_gemm_lower(hipStream_t s, int M, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc);
+// the same with the C operand read from Qin (leading dimension ldq, even; 16-byte aligned) with Cdiag[i] on its diagonal: C = Cin + alpha A B'
+int cip_gemm_lower_lazyc(hipStream_t s, int M, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc,
+                         const double *Qin, long ldq, const double *Cdiag);
+// C += alpha A B' on the whole M x N rectangle
+int cip_gemm_rect(hipStream_t s, int M, int N, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc);
+// Schur formation C = Qin + alpha W W' for i, j < nvalid on the lower 128-tiles (W: M x K).  split_n > 1 with a workspace: the k range
+// is cut into split_n slices of split_len columns (cip_syrk_split), every slice's product goes to its own M x M image in
+// split_ws, a second launch adds them up in slice order together with Qin
+int cip_syrk_schur(hipStream_t s, int M, int K, int nvalid, double alpha, const double *W, long ldw, const double *Qin, long ldq, double *C, long ldc,
+                   double *split_ws, int split_n, int split_len);
+// how cip_syrk_schur wants an (M x M, K) Schur formation split: number of slices (1: no split) and their length
 int cip_syrk_split(int M, int K, int *len);
-int cip_launch_gemm(hipStream_t s, int epi, const GemmArgs &g);
+// Batched overwrite C_b = alpha A_b B_b', by x bz independent problems: problem (y, z) of an operand starts at p + y*sy + z*sz (doubles).
+// Ct.p != NULL: the result is also stored transposed, Ct[j + i*ld].  `tiles`: which 64-tiles are computed (the others keep what C held)
+struct GemmBatchIn { const double *p; long ld, sy, sz; };
+struct GemmBatchOut { double *p; long ld, sy, sz; };
+enum { GEMM_TILES_ALL = 0, GEMM_TILES_TOUCH_UPPER = 1, GEMM_TILES_TOUCH_LOWER = 2 };     // all / those touching i <= j / those touching i >= j
+int cip_gemm_batched_64(hipStream_t s, int M, int N, int K, double alpha, const GemmBatchIn &A, const GemmBatchIn &B, const GemmBatchOut &C,
+                        const GemmBatchOut &Ct, int by, int bz, int tiles);
+// the same on 16x16 tiles with k split over the four waves of a workgroup (every tile; K a multiple of 128)
+int cip_gemm_batched_16(hipStream_t s, int M, int N, int K, double alpha, const GemmBatchIn &A, const GemmBatchIn &B, const GemmBatchOut &C,
+                        const GemmBatchOut &Ct, int by, int bz);
 
 // ---------------------------------------------------------------- small results back to the host (vecops.hip)
 // The loop's scalars (max-step minima, dot products, the lock-step gather) are a few doubles the host must SEE before it can go

@@ -1,26 +1,31 @@
-// fp64 MFMA "NT" GEMM for gfx950:  C (+)= alpha * A * B'   (all column-major).
-//
-// This one kernel carries every O(N^3) term of the KKT path:
-//   * LDL' trailing update   C -= (L21 D) L21'      (lower tiles only, K = outer block)
-//   * Schur formation        S  = Q + (A'F^-1)(A'F^-1)'   (EPI_SYRKQ)
-// i.e. the work the reference does in src/kktsolvers.jl:32-35 (dense GEMMs + QR)
-// and :289-295 (Schur + LU), re-designed for CDNA4.
-//
-// Design (MI355X):
-//   * 128x128 C tile per 256-thread workgroup = 4 wave64s in a 2x2 grid, each wave
-//     a 64x64 sub-tile = 4x4 v_mfma_f64_16x16x4_f64 accumulators (128 acc VGPRs).
-//   * Both operands are "row-contiguous, k-strided" in memory (a panel column is
-//     a contiguous run of rows), so a k-tile of 16 columns is staged as
-//     lds[k][row]: global_load_dwordx4 (one wave reads 1 KB contiguous per k) ->
-//     ds_write_b128, double-buffered, one barrier per k-tile.
-//   * Fragments are read with ds_read_b128: lane c takes rows (2c, 2c+1) of a
-//     32-row group, feeding two MFMA tiles per read; the row pitch is 1024 B
-//     (== 0 mod 256 B), which is conflict-free for the b128 lane groups.
-//   * The MFMA is issued "transposed" (A-operand = B rows, B-operand = A rows)
-//     so that an accumulator's lane index runs along C's rows: the epilogue then
-//     moves 16-byte double2 per lane, 256 B contiguous per 16 lanes.
-//   * blockIdx is remapped so that each XCD (own L2) walks a contiguous run of
-//     tiles (bijective variant of the xcd swizzle).
+// fp64 MFMA "NT" GEMM for gfx950:  C (+)= alpha * A * B'   (all column-major): every O(N^3) term of the KKT path, i.e. the work
+// the reference does in src/kktsolvers.jl:32-35 (dense GEMMs + QR) and :289-295 (Schur + LU), re-designed for CDNA4.
+// One launcher per form (declared in cip_internal.h, defined at the end of this file); DESIGN.md section 5 has the kernel
+// table, the tile design and the measurements behind each choice.
+//   cip_gemm_lower        k_ldlt_trailing_64<EPI_ACCUM>: the LDL' trailing update C -= (L21 D) L21' (K = outer block) and the rank
+//                         updates of the assembly, on 64x64 quarter tiles of the lower triangle, operands global -> LDS directly
+//   cip_gemm_lower_lazyc  k_ldlt_trailing_64<EPI_LAZYC>: the same with C read from Q (assemble.hip: lazy copy)
+//   cip_gemm_rect         k_gemm_nt_64 (64x64, register staging, raised priority) below 256 128-tiles: the wide and short in-block
+//                         update of the three-launch panel chain (K = 128); k_gemm_nt_128 (128x128) from there on
+//   cip_syrk_schur        S = Q + (A'F^-1)(A'F^-1)', K = m: k_syrkq_64<GLDS> on quarter tiles; with few tiles and K >= 4096 the k range
+//                         in slices, k_syrk_splitk_64 (or, <= 64 tiles and K >= 16384, k_syrk_splitk_128) + k_syrk_reduce
+//   cip_gemm_batched_64   k_gemm_nt_64_batched (64x64, optional transposed copy / tile selection): block-inverse doubling
+//                         (ldlt.hip), congruences of the large S cones (sdp_large.hip)
+//   cip_gemm_batched_16   k_gemm_nt_16_batched (16x16, k split over the four waves, no LDS staging): the doubling of the last
+//                         1024-wide solve block, the one preparation nothing hides
+// The 64x64 tile (cip_gemm_tile.h: gemm_tile_64) is the workhorse: 4 wave64s in a 2x2 grid, each a 32x32 sub-tile = 2x2
+// v_mfma_f64_16x16x4_f64 accumulators, 32 KB of LDS, five workgroups per CU.  It beats the 128x128 tile at two workgroups per CU
+// on the trailing update (55.0 vs 52.4 TFLOP/s at r = 8192, K = 512) and has a quarter of its per-tile latency on the skinny
+// updates.  The 128x128 tile (gemm_tile_128, below: each wave a 64x64 sub-tile = 4x4 accumulators, 64 KB of LDS) moves half the LDS
+// and operand traffic per flop and is kept where that decides: big rectangles and the long-K split Schur formation.  Both tiles:
+//   * Both operands are "row-contiguous, k-strided" in memory (a panel column is a contiguous run of rows), so a k-tile of
+//     16 columns is staged as lds[k][row], double-buffered, one barrier per k-tile.
+//   * Fragments are read with ds_read_b128: lane c takes rows (2c, 2c+1) of a 32-row group, feeding two MFMA tiles per read;
+//     the row pitch is a multiple of 256 B, which is conflict-free for the b128 lane groups.
+//   * The MFMA is issued "transposed" (A-operand = B rows, B-operand = A rows) so that an accumulator's lane index runs
+//     along C's rows: the epilogue then moves 16-byte double2 per lane, 256 B contiguous per 16 lanes.
+//   * blockIdx of the rectangular kernels is remapped so that each XCD (own L2) walks a contiguous run of tiles (bijective
+//     variant of the xcd swizzle).
 #include "cip_internal.h"
 #include "cip_gemm_tile.h"
 #include <stdlib.h>
@@ -33,21 +38,17 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
-// linear tile index -> (block row, block column): row-major over the lower triangle, or column-major rectangle
-__device__ __forceinline__ void tile_coords(int t, int lower, int tm, int &bi, int &bj) {
-    if (lower) {
-        bi = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((long)bi * (bi + 1) / 2 > t) --bi;
-        while ((long)(bi + 1) * (bi + 2) / 2 <= t) ++bi;
-        bj = t - (int)((long)bi * (bi + 1) / 2);
-    } else {
-        bi = t % tm;
-        bj = t / tm;
-    }
+// linear tile index -> (block row, block column), row-major over the lower triangle
+__device__ __forceinline__ void lower_tile_coords(int t, int &bi, int &bj) {
+    bi = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((long)bi * (bi + 1) / 2 > t) --bi;
+    while ((long)(bi + 1) * (bi + 2) / 2 <= t) ++bi;
+    bj = t - (int)((long)bi * (bi + 1) / 2);
 }
 
-template <int EPI>
-__device__ __forceinline__ void gemm_tile_128(GemmArgs &g, double *lds, int bi, int bj) {
+// 128x128 tile of C: STORE ? C = alpha acc : C += alpha acc
+template <bool STORE>
+__device__ __forceinline__ void gemm_tile_128(const GemmArgs &g, double *lds, int bi, int bj) {
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -124,39 +125,23 @@ __device__ __forceinline__ void gemm_tile_128(GemmArgs &g, double *lds, int bi, 
             for (int gi = 0; gi < 2; ++gi) {
                 const long row = i0 + wm * 64 + gi * 32 + 2 * l15;
                 v2d val = (v2d){acc[2 * gi][tj][q], acc[2 * gi + 1][tj][q]};
-                if (EPI == EPI_ACCUM) {
-                    double *cp = g.C + row + col * g.ldc;
-                    v2d c = g.overwrite ? (v2d){0.0, 0.0} : *(v2d *)cp;
-                    c += g.alpha * val;
-                    *(v2d *)cp = c;
-                    if (g.Ct) { g.Ct[col + row * g.ldct] = c.x; g.Ct[col + (row + 1) * g.ldct] = c.y; }
-                } else {   // EPI_SYRKQ
-                    if (col < g.nvalid) {
-                        if (row + 1 < g.nvalid) {
-                            // Q keeps the caller's (possibly odd) leading dimension: scalar loads
-                            const double *qp = g.Qin + row + col * g.ldq;
-                            const v2d qv = (v2d){qp[0], qp[1]};
-                            *(v2d *)(g.C + row + col * g.ldc) = qv + g.alpha * val;
-                        } else if (row < g.nvalid) {
-                            g.C[row + col * g.ldc] = g.Qin[row + col * g.ldq] + g.alpha * val.x;
-                        }
-                    }
-                }
+                double *cp = g.C + row + col * g.ldc;
+                v2d c = STORE ? (v2d){0.0, 0.0} : *(v2d *)cp;
+                c += g.alpha * val;
+                *(v2d *)cp = c;
             }
         }
     }
 }
 
-template <int EPI>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_128(GemmArgs g, CipBatch cb) {
     __shared__ __attribute__((aligned(16))) double lds[2 * 2 * LDS_TILE];   // 64 KB
     bool live;
-    const unsigned oz = gemm_batch_prologue(g, cb, live);
+    (void)gemm_batch_prologue(g, cb, live);
     if (!live) return;
-    if (EPI == EPI_ACCUM) gemm_own_batch(g, oz);       // batched problems: grid.y x grid.z
-    int bi, bj;
-    tile_coords(xcd_remap(blockIdx.x, gridDim.x), g.lower, g.M / CIP_NB, bi, bj);   // grid may cover only the first tiles
-    gemm_tile_128<EPI>(g, lds, bi, bj);
+    const int tm = g.M / CIP_NB;
+    const int t = xcd_remap(blockIdx.x, gridDim.x);
+    gemm_tile_128<false>(g, lds, t % tm, t / tm);
 }
 
 __global__ __launch_bounds__(256, 4) void k_gemm_nt_64(GemmArgs g, CipBatch cb) {
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(256, 4) void k_ldlt_trailing_64(GemmArgs g, CipBatc
     if (!live) return;
     __builtin_amdgcn_s_setprio(3);                     // measured: 58.0 vs 56.6 TFLOP/s without
     int bi, bj;
-    tile_coords((int)(blockIdx.x >> 2), 1, g.M / CIP_NB, bi, bj);
+    lower_tile_coords((int)(blockIdx.x >> 2), bi, bj);
     const int sub = blockIdx.x & 3;
     if (bi == bj && sub == 2) return;            // strictly-upper quadrant of a diagonal tile: never referenced
     gemm_tile_64<EPI, true>(g, lds, (long)bi * CIP_NB + (sub & 1) * SB, (long)bj * CIP_NB + (sub >> 1) * SB);
@@ -196,18 +181,17 @@ __global__ __launch_bounds__(256, 4) void k_gemm_nt_64_batched(GemmArgs g, CipBa
     if (!live) return;
     gemm_own_batch(g, oz);
     const int tm = g.M / SB;
-    if (g.lower == 2 && (blockIdx.x % tm) > (blockIdx.x / tm)) return;          // "upper only": tiles strictly below the diagonal are not wanted
-    if (g.lower == 3 && (blockIdx.x % tm) < (blockIdx.x / tm)) return;          // "lower only"
+    if (g.tiles == GEMM_TILES_TOUCH_UPPER && (blockIdx.x % tm) > (blockIdx.x / tm)) return;     // tiles strictly below the diagonal are not wanted
+    if (g.tiles == GEMM_TILES_TOUCH_LOWER && (blockIdx.x % tm) < (blockIdx.x / tm)) return;     // tiles strictly above
     gemm_tile_64<EPI_STORE>(g, lds, (long)(blockIdx.x % tm) * SB, (long)(blockIdx.x / tm) * SB);
 }
 
-// The same batched overwrite form with ONE 16x16 tile of C per workgroup, the k range split over its four waves, operands from
-// global memory (L2) straight into the MFMA lanes -- lane l supplies row l % 16, k = l / 16 of its operand tile -- no LDS
-// staging; the partial accumulators of waves 1..3 are added to wave 0's in a fixed order (the form of sdp_large.hip's
-// k_gemm_nt_small).  For the block-inverse doubling (ldlt.hip): a level is a handful of h x h x h products, and a 64x64 tile walks
-// its whole K = h on one CU -- 512 dependent MFMAs per wave at h = 512, 14 us of one CU's MFMA pipe behind a latency-bound
-// k-loop, 19 us per launch on an idle chip -- while here the same product is (h / 16)^2 workgroups with 8 h / 128 MFMAs per
-// wave.  K a multiple of 128, M and N of 16.  Register q of lane l holds C[i0 + l % 16, j0 + l / 16 + 4 q].
+// The same batched overwrite form with ONE 16x16 tile of C per workgroup, the k range split over its four waves: the tile of
+// cip_gemm_tile.h's gemm_tile_16_splitk (same MFMAs, same reduction order), written out here with alpha and the transposed copy in
+// its epilogue.  For the block-inverse doubling (ldlt.hip): a level is a handful of h x h x h products, and a 64x64 tile walks its
+// whole K = h on one CU -- 512 dependent MFMAs per wave at h = 512, 14 us of one CU's MFMA pipe behind a latency-bound k-loop, 19 us
+// per launch on an idle chip -- while here the same product is (h / 16)^2 workgroups with 8 h / 128 MFMAs per wave.  K a multiple
+// of 128, M and N of 16.  Register q of lane l holds C[i0 + l % 16, j0 + l / 16 + 4 q].
 __global__ __launch_bounds__(256) void k_gemm_nt_16_batched(GemmArgs g, CipBatch cb) {
     __shared__ double red[3][4][64];
     bool live;
@@ -261,7 +245,7 @@ __global__ __launch_bounds__(256, 4) void k_syrkq_64(GemmArgs g, CipBatch cb) {
     if (!live) return;
     if (GLDS) __builtin_amdgcn_s_setprio(3);
     int bi, bj;
-    tile_coords((int)(blockIdx.x >> 2), 1, g.M / CIP_NB, bi, bj);
+    lower_tile_coords((int)(blockIdx.x >> 2), bi, bj);
     const int sub = blockIdx.x & 3;
     if (bi == bj && sub == 2) return;
     gemm_tile_64<EPI_SYRKQ, GLDS>(g, lds, (long)bi * CIP_NB + (sub & 1) * SB, (long)bj * CIP_NB + (sub >> 1) * SB);
@@ -276,7 +260,7 @@ __global__ __launch_bounds__(256, 4) void k_syrk_splitk_64(GemmArgs g, CipBatch 
     (void)gemm_batch_prologue(g, cb, live);
     if (!live) return;
     int bi, bj;
-    tile_coords((int)(blockIdx.x >> 2), 1, g.M / CIP_NB, bi, bj);
+    lower_tile_coords((int)(blockIdx.x >> 2), bi, bj);
     const int sub = blockIdx.x & 3;
     if (bi == bj && sub == 2) return;
     const long k0 = (long)blockIdx.y * g.ksplit_len;
@@ -295,13 +279,13 @@ __global__ __launch_bounds__(256, 2) void k_syrk_splitk_128(GemmArgs g, CipBatch
     (void)gemm_batch_prologue(g, cb, live);
     if (!live) return;
     int bi, bj;
-    tile_coords((int)blockIdx.x, 1, g.M / CIP_NB, bi, bj);
+    lower_tile_coords((int)blockIdx.x, bi, bj);
     const long k0 = (long)blockIdx.y * g.ksplit_len;
     g.A += k0 * g.lda; g.B += k0 * g.ldb;
     g.K = (g.K - k0 < g.ksplit_len) ? (int)(g.K - k0) : g.ksplit_len;
     g.C = (double *)((char *)g.ksplit_ws + (long)(blockIdx.z / (g.bz > 0 ? g.bz : 1)) * cb.stride) + (long)blockIdx.y * g.M * g.M;
-    g.ldc = g.M; g.Ct = nullptr; g.overwrite = 1;
-    gemm_tile_128<EPI_ACCUM>(g, lds, bi, bj);
+    g.ldc = g.M;
+    gemm_tile_128<true>(g, lds, bi, bj);
 }
 // C[i, j] = Qin[i, j] + sum_b image_b[i, j] for i >= j (by 64-tiles), i, j < nvalid; one thread per row pair of a 64 x 64 tile column
 __global__ __launch_bounds__(256) void k_syrk_reduce(GemmArgs g, CipBatch cb) {
@@ -310,7 +294,7 @@ __global__ __launch_bounds__(256) void k_syrk_reduce(GemmArgs g, CipBatch cb) {
     if (!live) return;
     const double *ws = (const double *)((const char *)g.ksplit_ws + (long)(blockIdx.z / (g.bz > 0 ? g.bz : 1)) * cb.stride);
     int bi, bj;
-    tile_coords((int)blockIdx.x, 1, g.M / SB, bi, bj);                 // 64-tiles of the lower triangle
+    lower_tile_coords((int)blockIdx.x, bi, bj);                 // 64-tiles of the lower triangle
     const int r2 = threadIdx.x & 31, c0 = threadIdx.x >> 5;             // row pair, first column (8 columns per pass)
     const long row = (long)bi * SB + 2 * r2;
     const long img = (long)g.M * g.M;
@@ -347,78 +331,113 @@ int cip_syrk_split(int M, int K, int *len) {
     return n;
 }
 
-int cip_launch_gemm(hipStream_t s, int epi, const GemmArgs &g) {
-    if (g.M <= 0 || g.N <= 0) return 0;
-    if (g.M % CIP_NB || g.N % CIP_NB || g.K % CIP_KT || g.K <= 0) {
-        cip_set_error("gemm: bad dims M=%d N=%d K=%d", g.M, g.N, g.K);
-        return -1;
+// ---------------------------------------------------------------------------------------------------------------- launchers
+// false: nothing to launch, *rc is what the launcher returns (0 for an empty product, -1 with the error set)
+static bool gemm_dims_ok(int M, int N, int K, int *rc) {
+    *rc = 0;
+    if (M <= 0 || N <= 0) return false;
+    if (M % CIP_NB || N % CIP_NB || K % CIP_KT || K <= 0) {
+        cip_set_error("gemm: bad dims M=%d N=%d K=%d", M, N, K);
+        *rc = -1;
+        return false;
     }
-    const int tm = g.M / CIP_NB, tn = g.N / CIP_NB;
-    long tiles;
-    if (g.lower == 1) {
-        if (g.M != g.N) { cip_set_error("gemm: lower needs M == N"); return -1; }
-        tiles = (long)tm * (tm + 1) / 2;
-    } else {
-        tiles = (long)tm * tn;
-    }
-    const int by = g.by > 0 ? g.by : 1, bz = g.bz > 0 ? g.bz : 1;
-    if (by * bz > 1 || (g.overwrite && epi == EPI_ACCUM && g.lower != 1)) {
-        if (epi != EPI_ACCUM || g.lower == 1 || (g.lower >= 2 && !g.overwrite)) { cip_set_error("gemm: batching needs the plain accumulate form"); return -1; }
-        if (g.overwrite && g.tiny16 && !g.lower && g.K % 128 == 0) {
-            cip_launch_b(k_gemm_nt_16_batched, dim3((unsigned)((g.M / 16) * (g.N / 16)), by, bz), dim3(256), 0, s, g);
-            CIP_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-        if (g.overwrite) {
-            cip_launch_b(k_gemm_nt_64_batched, dim3((unsigned)(4 * tiles), by, bz), dim3(256), 0, s, g);
-            CIP_HIP_CHECK(hipGetLastError());
-            return 0;
-        }
-        cip_launch_b(k_gemm_nt_128<EPI_ACCUM>, dim3((unsigned)tiles, by, bz), dim3(256), 0, s, g);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (epi == EPI_LAZYC) {
-        if (!g.lower || !g.Qin || !g.Cdiag || (g.ldq & 1) || (((uintptr_t)g.Qin) & 15)) { cip_set_error("gemm: bad lazy-C arguments"); return -1; }
-        cip_launch_b(k_ldlt_trailing_64<EPI_LAZYC>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (epi == EPI_ACCUM && g.lower) {
-        // the LDL' trailing update: every 128-tile of the lower triangle as four 64x64 quarter tiles (in plain tile order: an
-        // XCD-aware patch order fetched less and ran slower, DESIGN_LOG.md "Experiments removed from the library")
-        cip_launch_b(k_ldlt_trailing_64<EPI_ACCUM>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (epi == EPI_SYRKQ && g.lower && g.ksplit_ws && g.ksplit_n > 1) {
+    return true;
+}
+static long lower_tiles_128(int M) { const long tm = M / CIP_NB; return tm * (tm + 1) / 2; }
+static GemmArgs gemm_args(int M, int N, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc) {
+    GemmArgs g = {};
+    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.alpha = alpha;
+    return g;
+}
+
+int cip_gemm_lower(hipStream_t s, int M, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc) {
+    int rc; if (!gemm_dims_ok(M, M, K, &rc)) return rc;
+    GemmArgs g = gemm_args(M, M, K, alpha, A, lda, B, ldb, C, ldc);
+    // every 128-tile of the lower triangle as four 64x64 quarter tiles (in plain tile order: an XCD-aware patch order fetched
+    // less and ran slower, DESIGN_LOG.md "Experiments removed from the library")
+    cip_launch_b(k_ldlt_trailing_64<EPI_ACCUM>, dim3((unsigned)(4 * lower_tiles_128(M))), dim3(256), 0, s, g);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int cip_gemm_lower_lazyc(hipStream_t s, int M, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc,
+                         const double *Qin, long ldq, const double *Cdiag) {
+    int rc; if (!gemm_dims_ok(M, M, K, &rc)) return rc;
+    if (!Qin || !Cdiag || (ldq & 1) || (((uintptr_t)Qin) & 15)) { cip_set_error("gemm: bad lazy-C arguments"); return -1; }
+    GemmArgs g = gemm_args(M, M, K, alpha, A, lda, B, ldb, C, ldc);
+    g.Qin = Qin; g.ldq = ldq; g.Cdiag = Cdiag;
+    cip_launch_b(k_ldlt_trailing_64<EPI_LAZYC>, dim3((unsigned)(4 * lower_tiles_128(M))), dim3(256), 0, s, g);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// skinny, latency-critical: quarter-size tiles
+static bool rect_on_quarter_tiles(long tiles128) { return tiles128 < 256; }
+
+int cip_gemm_rect(hipStream_t s, int M, int N, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc) {
+    int rc; if (!gemm_dims_ok(M, N, K, &rc)) return rc;
+    const GemmArgs g = gemm_args(M, N, K, alpha, A, lda, B, ldb, C, ldc);
+    const long tiles = (long)(M / CIP_NB) * (N / CIP_NB);
+    if (rect_on_quarter_tiles(tiles)) cip_launch_b(k_gemm_nt_64, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+    else cip_launch_b(k_gemm_nt_128, dim3((unsigned)tiles), dim3(256), 0, s, g);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// operands global -> LDS directly + raised wave priority, as the trailing update (round 4, config 3: 1.35 -> 1.28 ms per
+// Schur formation, same-session A/B 4.17 -> 4.10 ms per iteration, same bits); register staging for odd leading
+// dimensions and misaligned operands
+static bool syrkq_glds(const double *W, long ldw) { return !(ldw & 1) && !(((uintptr_t)W) & 15); }
+
+int cip_syrk_schur(hipStream_t s, int M, int K, int nvalid, double alpha, const double *W, long ldw, const double *Qin, long ldq, double *C, long ldc,
+                   double *split_ws, int split_n, int split_len) {
+    int rc; if (!gemm_dims_ok(M, M, K, &rc)) return rc;
+    GemmArgs g = gemm_args(M, M, K, alpha, W, ldw, W, ldw, C, ldc);
+    g.Qin = Qin; g.ldq = ldq; g.nvalid = nvalid;
+    const long tiles = lower_tiles_128(M);
+    if (split_ws && split_n > 1) {
+        g.ksplit_ws = split_ws; g.ksplit_n = split_n; g.ksplit_len = split_len;
         GemmArgs gs = g;
         gs.alpha = 1.0;                                          // (the images hold the plain products; alpha is applied by the reduction)
-        if (syrk_split_128(g.M, g.K)) cip_launch_b(k_syrk_splitk_128, dim3((unsigned)tiles, (unsigned)g.ksplit_n), dim3(256), 0, s, gs);
-        else cip_launch_b(k_syrk_splitk_64, dim3((unsigned)(4 * tiles), (unsigned)g.ksplit_n), dim3(256), 0, s, gs);
-        const long t64 = (long)(g.M / SB) * (g.M / SB + 1) / 2;
+        if (syrk_split_128(M, K)) cip_launch_b(k_syrk_splitk_128, dim3((unsigned)tiles, (unsigned)split_n), dim3(256), 0, s, gs);
+        else cip_launch_b(k_syrk_splitk_64, dim3((unsigned)(4 * tiles), (unsigned)split_n), dim3(256), 0, s, gs);
+        const long t64 = (long)(M / SB) * (M / SB + 1) / 2;
         cip_launch_b(k_syrk_reduce, dim3((unsigned)t64), dim3(256), 0, s, g);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
+    } else if (syrkq_glds(W, ldw)) {
+        cip_launch_b(k_syrkq_64<true>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+    } else {
+        cip_launch_b(k_syrkq_64<false>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
     }
-    if (epi == EPI_SYRKQ && g.lower) {
-        // operands global -> LDS directly + raised wave priority, as the trailing update (round 4, config 3: 1.35 -> 1.28 ms per
-        // Schur formation, same-session A/B 4.17 -> 4.10 ms per iteration, same bits); register staging for odd leading
-        // dimensions and misaligned operands
-        if (!(g.lda & 1) && !(g.ldb & 1) && !(((uintptr_t)g.A | (uintptr_t)g.B) & 15)) cip_launch_b(k_syrkq_64<true>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
-        else cip_launch_b(k_syrkq_64<false>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (epi == EPI_ACCUM && !g.lower && !g.overwrite && (tiles < 256 || g.force64) && g.M % SB == 0 && g.N % SB == 0) {
-        // skinny, latency-critical: quarter-size tiles
-        const long t64 = (long)(g.M / SB) * (g.N / SB);
-        cip_launch_b(k_gemm_nt_64, dim3((unsigned)t64), dim3(256), 0, s, g);
-        CIP_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (epi != EPI_ACCUM) { cip_set_error("gemm: bad epilogue"); return -1; }      // (EPI_SYRKQ: lower tiles only, above)
-    cip_launch_b(k_gemm_nt_128<EPI_ACCUM>, dim3((unsigned)tiles), dim3(256), 0, s, g);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static GemmArgs gemm_batched_args(int M, int N, int K, double alpha, const GemmBatchIn &A, const GemmBatchIn &B, const GemmBatchOut &C,
+                                  const GemmBatchOut &Ct, int bz) {
+    GemmArgs g = gemm_args(M, N, K, alpha, A.p, A.ld, B.p, B.ld, C.p, C.ld);
+    g.bz = bz;
+    g.sAy = A.sy; g.sAz = A.sz; g.sBy = B.sy; g.sBz = B.sz; g.sCy = C.sy; g.sCz = C.sz;
+    g.Ct = Ct.p; g.ldct = Ct.ld; g.sCty = Ct.sy; g.sCtz = Ct.sz;
+    return g;
+}
+
+int cip_gemm_batched_64(hipStream_t s, int M, int N, int K, double alpha, const GemmBatchIn &A, const GemmBatchIn &B, const GemmBatchOut &C,
+                        const GemmBatchOut &Ct, int by, int bz, int tiles) {
+    int rc; if (!gemm_dims_ok(M, N, K, &rc)) return rc;
+    GemmArgs g = gemm_batched_args(M, N, K, alpha, A, B, C, Ct, bz);
+    g.tiles = tiles;
+    cip_launch_b(k_gemm_nt_64_batched, dim3((unsigned)((M / SB) * (N / SB)), by, bz), dim3(256), 0, s, g);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int cip_gemm_batched_16(hipStream_t s, int M, int N, int K, double alpha, const GemmBatchIn &A, const GemmBatchIn &B, const GemmBatchOut &C,
+                        const GemmBatchOut &Ct, int by, int bz) {
+    int rc; if (!gemm_dims_ok(M, N, K, &rc)) return rc;
+    if (K % 128) return cip_gemm_batched_64(s, M, N, K, alpha, A, B, C, Ct, by, bz, GEMM_TILES_ALL);     // (the waves split k in 32-column steps)
+    const GemmArgs g = gemm_batched_args(M, N, K, alpha, A, B, C, Ct, bz);
+    cip_launch_b(k_gemm_nt_16_batched, dim3((unsigned)((M / 16) * (N / 16)), by, bz), dim3(256), 0, s, g);
     CIP_HIP_CHECK(hipGetLastError());
     return 0;
 }

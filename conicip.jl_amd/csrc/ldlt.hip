@@ -17,6 +17,7 @@
 // Solves (HBM-bound, L read once per sweep): blocked substitution with the stored inverses of the diagonal blocks
 // (doubled up to 1024 wide), two gemv launches per block step and sweep.
 #include "cip_internal.h"
+#include "cip_gemm_tile.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -271,21 +272,18 @@ int cip_launch_trsm_subst(hipStream_t s, double *Ap, long ld, int rows, const do
 // right-looking update inside the outer block: after inner panel t, the remaining panel columns of the block
 //   K[c0+128:, c0+128 : C0+wblk] -= W_t[c0+128:, :] * L_t[c0+128 : C0+wblk, :]'        (K = 128, wide and short:
 // many quarter tiles, one short k-loop -- the latency-critical shape; the left-looking form had K up to 384)
-static bool rest_of_block_args(double *K, int Npad, long ld, double *Wb, int C0, int wblk, int t, GemmArgs &g) {
+struct RestOfBlock { int M, N; const double *A, *B; double *C; };      // A: W_t (ld Npad), B: L_t (ld), C: K (ld); K = 128, alpha = -1
+static bool rest_of_block(double *K, int Npad, long ld, double *Wb, int C0, int wblk, int t, RestOfBlock &r) {
     const int c1 = C0 + (t + 1) * CIP_NB;            // first row / column still to be factored in this block
     const int ncols = C0 + wblk - c1;
     if (ncols <= 0 || c1 >= Npad) return false;
-    g = GemmArgs{};
-    g.A = Wb + c1 + (long)(t * CIP_NB) * Npad; g.lda = Npad;
-    g.B = K + c1 + (long)(c1 - CIP_NB) * ld; g.ldb = ld;
-    g.C = K + c1 + (long)c1 * ld; g.ldc = ld;
-    g.M = Npad - c1; g.N = ncols; g.K = CIP_NB; g.alpha = -1.0; g.lower = 0;
+    r = RestOfBlock{Npad - c1, ncols, Wb + c1 + (long)(t * CIP_NB) * Npad, K + c1 + (long)(c1 - CIP_NB) * ld, K + c1 + (long)c1 * ld};
     return true;
 }
 static int update_rest_of_block(hipStream_t s, double *K, int Npad, long ld, double *Wb, int C0, int wblk, int t) {
-    GemmArgs g;
-    if (!rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t, g)) return 0;
-    return cip_launch_gemm(s, EPI_ACCUM, g);
+    RestOfBlock r;
+    if (!rest_of_block(K, Npad, ld, Wb, C0, wblk, t, r)) return 0;
+    return cip_gemm_rect(s, r.M, r.N, CIP_NB, -1.0, r.A, Npad, r.B, ld, r.C, ld);
 }
 // CIP_FUSE_DIAG=0 / cip_set_ldlt_fused_chain(0): the three-launch chain (diag -> TRSM -> update per panel), the give-up
 // fall-back and the bitwise reference of the fused one; 3 selects the fused chain, any other value only queries
@@ -327,7 +325,10 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
         const bool fuse = g_fuse_diag && !ws.unfused && (!cip_in_batch() || small_group);
         if (fuse) {
             tl_ran_fused = true;
-            const bool upd = t > 0 && rest_of_block_args(K, Npad, ld, Wb, C0, wblk, t - 1, gu);
+            RestOfBlock rb;
+            const bool upd = t > 0 && rest_of_block(K, Npad, ld, Wb, C0, wblk, t - 1, rb);
+            // the panel kernel runs the update's tile bodies itself (diag.hip): their parameter block, A .. alpha
+            if (upd) gu = GemmArgs{rb.A, Npad, rb.B, ld, rb.C, ld, rb.M, rb.N, CIP_NB, -1.0};
             unsigned *ctr = (unsigned *)(ws.info + 16);
             if ((rc = cip_launch_panel(s, K + c0 + (long)c0 * ld, ld, ws.Xm + (size_t)jb * 2048, ws.dvec + c0, ws.dinv + c0, ws.info, c0,
                                        ws.signs, ctr + jb, ctr + Npad / CIP_NB + jb, ctr + 2 * (Npad / CIP_NB) + jb, upd ? &gu : nullptr, r,
@@ -385,7 +386,6 @@ static int ensure_x_zeroed(hipStream_t s, int Npad, const LdltWorkspace &ws) {
 //   blockIdx.y <  nm:  MT_J = U_{J-1,J} XT_J,  J = jm0 + blockIdx.y       (U = L' from the upper triangle; XT_J upper triangular:
 //                      column tile j0 needs k < j0 + 64 only)
 //   blockIdx.y >= nm:  PT_J = L_{J+1,J} X_J,   J = jp0 + blockIdx.y - nm  (X_J lower triangular: k >= j0 only)
-#include "cip_gemm_tile.h"
 __global__ __launch_bounds__(256, 4) void k_solve_premul(const double *K, long ld, const double *X, const double *XT, double *MT,
                                                          double *PT, int Bs, int jm0, int nm, int jp0, CipBatch cb) {
     __shared__ __attribute__((aligned(16))) double lds[2 * 2 * CIP_KT * SB];   // 32 KB
@@ -463,23 +463,18 @@ static int build_solve_blocks(hipStream_t s, double *K, int Npad, long ld, const
         const int P = Bs / (2 * h);                          // pairs per block
         const long pX = 2L * h * (Bs + 1);                   // pair stride inside a block of X / XT
         const long pK = 2L * h * (ld + 1);                   // pair stride along the diagonal of K
-        GemmArgs g = {};
-        g.M = g.N = g.K = h; g.lower = 0; g.overwrite = 1; g.by = nbk; g.bz = P;
-        g.tiny16 = doubling_tiny(Bs, J0, Npad / Bs);
+        const bool tiny = doubling_tiny(Bs, J0, Npad / Bs);
+        auto product = [&](double alpha, const GemmBatchIn &A, const GemmBatchIn &B, const GemmBatchOut &C, const GemmBatchOut &Ct) {
+            return tiny ? cip_gemm_batched_16(s, h, h, h, alpha, A, B, C, Ct, nbk, P)
+                        : cip_gemm_batched_64(s, h, h, h, alpha, A, B, C, Ct, nbk, P, GEMM_TILES_ALL);
+        };
+        const GemmBatchIn xt11{XT0, Bs, bs2, pX}, l21{Kd + h, ld, (long)Bs * (ld + 1), pK}, tt_in{Tt0, h, tt2, (long)h * h};
+        const GemmBatchIn x22{X0 + h + (long)h * Bs, Bs, bs2, pX};
+        const GemmBatchOut tt{Tt0, h, tt2, (long)h * h}, x21{X0 + h, Bs, bs2, pX}, xt12{XT0 + (long)h * Bs, Bs, bs2, pX};
         // Tt = XT11 * L21'
-        g.alpha = 1.0;
-        g.A = XT0; g.lda = Bs; g.sAy = bs2; g.sAz = pX;
-        g.B = Kd + h; g.ldb = ld; g.sBy = (long)Bs * (ld + 1); g.sBz = pK;
-        g.C = Tt0; g.ldc = h; g.sCy = tt2; g.sCz = (long)h * h;
-        if ((rc = cip_launch_gemm(s, EPI_ACCUM, g))) return rc;
+        if ((rc = product(1.0, xt11, l21, tt, GemmBatchOut{}))) return rc;
         // X21 = -X22 * Tt'  and, from the same accumulators, XT12 = X21' (stored transposed by the epilogue)
-        g.alpha = -1.0;
-        g.A = X0 + h + (long)h * Bs; g.lda = Bs; g.sAy = bs2; g.sAz = pX;
-        g.B = Tt0; g.ldb = h; g.sBy = tt2; g.sBz = (long)h * h;
-        g.C = X0 + h; g.ldc = Bs; g.sCy = bs2; g.sCz = pX;
-        g.Ct = XT0 + (long)h * Bs; g.ldct = Bs; g.sCty = bs2; g.sCtz = pX;
-        if ((rc = cip_launch_gemm(s, EPI_ACCUM, g))) return rc;
-        g.Ct = nullptr;
+        if ((rc = product(-1.0, x22, tt_in, x21, xt12))) return rc;
     }
     return build_solve_premul(s, K, ld, ws, Npad / Bs, J0, J1);
 }
@@ -679,16 +674,9 @@ static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const L
         if ((rc = factor_outer_panels(s, K, Npad, ld, ws, ws.Wbuf, C0, wblk))) return rc;
         const int r0 = C0 + wblk;
         if (r0 < Npad) {
-            GemmArgs g = {};
-            g.A = ws.Wbuf + r0; g.lda = Npad;
-            g.B = K + r0 + (long)C0 * ld; g.ldb = ld;
-            g.C = K + r0 + (long)r0 * ld; g.ldc = ld;
-            g.M = Npad - r0; g.N = Npad - r0; g.K = wblk; g.alpha = -1.0; g.lower = 1;
-            int epi = EPI_ACCUM;
-            if (C0 == 0 && ws.lazyC) {                    // the trailing matrix is still in Q: read it from there, write K
-                epi = EPI_LAZYC;
-                g.Qin = ws.lazyC + r0 + (long)r0 * ws.lazy_ld; g.ldq = ws.lazy_ld; g.Cdiag = ws.lazy_diag + r0;
-            }
+            const double *Wr = ws.Wbuf + r0, *Lr = K + r0 + (long)C0 * ld;
+            double *Cr = K + r0 + (long)r0 * ld;
+            const bool lazy = C0 == 0 && ws.lazyC;        // the trailing matrix is still in Q: read it from there, write K
             LdltProfile *prof = prof_this;
             if (prof) {
                 if ((rc = prof_event(prof, s))) return rc;
@@ -696,7 +684,9 @@ static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const L
                 const double live = cip_in_batch() ? (double)__builtin_popcountll(cip_tl_bz.mask) : 1.0;
                 prof->flops.push_back(live * r * (r + 1.0) * (double)wblk);   // 2 flop/MAC on the lower triangle
             }
-            if ((rc = cip_launch_gemm(s, epi, g))) return rc;
+            if ((rc = lazy ? cip_gemm_lower_lazyc(s, Npad - r0, wblk, -1.0, Wr, Npad, Lr, ld, Cr, ld, ws.lazyC + r0 + (long)r0 * ws.lazy_ld, ws.lazy_ld,
+                                                  ws.lazy_diag + r0)
+                           : cip_gemm_lower(s, Npad - r0, wblk, -1.0, Wr, Npad, Lr, ld, Cr, ld))) return rc;
             if (prof && (rc = prof_event(prof, s))) return rc;
         }
     }

@@ -23,6 +23,7 @@
 //
 // apply / product / division stay on the workgroup-per-cone kernels (one or two r^3 GEMMs each, 0.1-0.3 ms at r = 256).
 #include "cip_handle.h"
+#include "cip_gemm_tile.h"
 #include "../../include/cipkkt.h"
 #include <math.h>
 #include <vector>
@@ -650,19 +651,15 @@ void cip_sdp_large_destroy(LargeWs *w) {
 }
 
 static dim3 lg_grid(long n) { return dim3((unsigned)((n + 255) / 256)); }
-// C_b = A_b B_b'  (rp x rp each, 64x64 fp64-MFMA tiles); stride 0 = operand shared by the batch
 // ONE product C = A B' of order rp <= 256 (the congruences of apply / max-step / NT scaling: ~60 per iteration of config 4).  The
 // 64x64-tile kernel has 16 workgroups for it and walks K = 256 in each: 14 us on 16 of 256 CUs.  Here a workgroup owns one 16x16
-// tile of C (256 workgroups at order 256) and its four waves split the k range; operands go from global memory (L2: 0.5 MB per
-// matrix) straight into the MFMA lanes -- lane l supplies row l % 16, k = l / 16 of its operand tile -- no LDS staging; the three
-// partial accumulators of waves 1..3 are added to wave 0's in a fixed order.  Register q of lane l holds C[i0 + l % 16, j0 + l / 16 + 4 q]
-// (the operand order of gemm_tile_64: B's rows first).
+// tile of C (256 workgroups at order 256) and its four waves split the k range (cip_gemm_tile.h: gemm_tile_16_splitk; operands
+// from L2, 0.5 MB per matrix).
 // BVEC: B is mat(xv) of a vecm vector (symmetric; zero outside the leading r x r block), read straight from the vector -- no k_lg_mat
 // pass; CVEC: the result goes out as vecm (entries i <= j < r, off-diagonal ones times sqrt 2; tiles below the diagonal are not
 // computed) -- no k_lg_vecm pass.  Same MFMAs on the same operands in the same order as the plain form: same bits.
 template <bool BVEC, bool CVEC>
 __global__ __launch_bounds__(256) void k_gemm_nt_small(const double *A, long lda, const double *B, long ldb, double *C, long ldc, int K, int r) {
-    __shared__ double red[3][4][64];
     if (CVEC && blockIdx.x > blockIdx.y) return;               // (16 i0 > 16 j0 + 15 for every entry of the tile)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -670,60 +667,32 @@ __global__ __launch_bounds__(256) void k_gemm_nt_small(const double *A, long lda
     const double *a = A + (long)blockIdx.x * 16 + l15 + (long)(wave * kq + l4) * lda;
     const double *b = B + (long)blockIdx.y * 16 + l15 + (long)(wave * kq + l4) * ldb;
     const int jb = blockIdx.y * 16 + l15, kb0 = wave * kq + l4;      // BVEC: this lane's row of mat(xv) and its first k
-    v4d acc0 = (v4d){0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
-    for (int k = 0; k < kq; k += 32) {
-        double av[8], bv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            av[u] = a[(long)(k + 4 * u) * lda];
-            if (BVEC) {
-                const int kk = kb0 + k + 4 * u;
-                double v = 0.0;
-                if (jb < r && kk < r) {
-                    const int lo = jb < kk ? jb : kk, hi = jb < kk ? kk : jb;
-                    v = B[lg_vidx(lo, hi, r)];
-                    if (lo != hi) v *= LG_SQRT1_2;
-                }
-                bv[u] = v;
-            } else {
-                bv[u] = b[(long)(k + 4 * u) * ldb];
+    gemm_tile_16_splitk(a, lda, K,
+        [&](int dk) {
+            if (!BVEC) return b[(long)dk * ldb];
+            const int kk = kb0 + dk;
+            double v = 0.0;
+            if (jb < r && kk < r) {
+                const int lo = jb < kk ? jb : kk, hi = jb < kk ? kk : jb;
+                v = B[lg_vidx(lo, hi, r)];
+                if (lo != hi) v *= LG_SQRT1_2;
             }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u += 2) {
-            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[u], av[u], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[u + 1], av[u + 1], acc1, 0, 0, 0);
-        }
-    }
-    acc0 += acc1;
-    if (wave > 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave - 1][q][lane] = acc0[q];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double c = ((acc0[q] + red[0][q][lane]) + red[1][q][lane]) + red[2][q][lane];
+            return v;
+        },
+        [&](int q, double c) {
             const int i = blockIdx.x * 16 + l15, j = blockIdx.y * 16 + l4 + 4 * q;
             if (CVEC) { if (i <= j && j < r) C[lg_vidx(i, j, r)] = (i == j) ? c : c * LG_SQRT2; }
             else C[i + (long)j * ldc] = c;
-        }
-    }
+        });
 }
-// part 2: only the 64-tiles that touch i <= j are computed (the others keep what C held); 3: only those that touch i >= j
-static int lg_gemm(hipStream_t s, double *C, long sC, const double *A, long sA, const double *B, long sB, int rp, int batch, int part = 0) {
-    if (batch == 1 && part == 0 && rp <= 256) {
+// C_b = A_b B_b'  (rp x rp each); stride 0 = operand shared by the batch; tiles: GEMM_TILES_*, which 64-tiles are computed
+static int lg_gemm(hipStream_t s, double *C, long sC, const double *A, long sA, const double *B, long sB, int rp, int batch, int tiles = GEMM_TILES_ALL) {
+    if (batch == 1 && tiles == GEMM_TILES_ALL && rp <= 256) {
         hipLaunchKernelGGL((k_gemm_nt_small<false, false>), dim3(rp / 16, rp / 16), dim3(256), 0, s, A, (long)rp, B, (long)rp, C, (long)rp, rp, rp);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    GemmArgs g = {};
-    g.A = A; g.lda = rp; g.B = B; g.ldb = rp; g.C = C; g.ldc = rp;
-    g.M = g.N = g.K = rp; g.alpha = 1.0; g.overwrite = 1; g.by = batch; g.bz = 1;
-    g.lower = part;
-    g.sAy = sA; g.sBy = sB; g.sCy = sC;
-    return cip_launch_gemm(s, EPI_ACCUM, g);
+    return cip_gemm_batched_64(s, rp, rp, rp, 1.0, GemmBatchIn{A, rp, sA, 0}, GemmBatchIn{B, rp, sB, 0}, GemmBatchOut{C, rp, sC, 0}, GemmBatchOut{}, batch, 1, tiles);
 }
 static int lg_set_attr(const void *fn, size_t bytes) {
     CIP_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -1714,7 +1683,7 @@ int cip_sdp_large_scale_At(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li
             X = w->batchX;
         }
         if ((rc = lg_gemm(s, w->batchT, n2, Rip, 0, X, n2, rp, nb))) return rc;                  // Rinv X      (X symmetric)
-        if ((rc = lg_gemm(s, w->batchX, n2, w->batchT, n2, Rip, 0, rp, nb, 3))) return rc;     // (Rinv X) Rinv': lower tiles, all k_lg_vecm_cols reads
+        if ((rc = lg_gemm(s, w->batchX, n2, w->batchT, n2, Rip, 0, rp, nb, GEMM_TILES_TOUCH_LOWER))) return rc;     // (Rinv X) Rinv': lower tiles, all k_lg_vecm_cols reads
         dim3 gv((unsigned)((dim + 63) / 64), (unsigned)((nb + 63) / 64));
         hipLaunchKernelGGL(k_lg_vecm_cols, gv, dim3(256), 0, s, w->batchX, nb, Wt + i0 + (long)cd.aoff * ldwt, ldwt, r, rp);
     }

@@ -223,7 +223,7 @@ def test_first_bad_pivot_is_reported_at_its_own_column(lib, chain):
 # terms and K merges of partial sums), one product with alpha and one addition to C: (2 K + 2) u <= 3 K u for K >= 16, relative
 # to |C| + |alpha| |A||B|'.
 GEMM_C = 3
-GEMM_FORMS = {          # (M, N, lower_only): 128-tiles -> kernel, by cip_launch_gemm's rules
+GEMM_FORMS = {          # (M, N, lower_only): 128-tiles -> kernel, by the rules of cip_gemm_lower / cip_gemm_rect (gemm_f64.hip)
     "k_gemm_nt_128": (2048, 2048, 0),            # 256 tiles: not "skinny"
     "k_gemm_nt_64": (1920, 2048, 0),             # 240 tiles < 256: quarter tiles
     "k_ldlt_trailing_64": (1024, 1024, 1),       # lower only
@@ -278,6 +278,33 @@ def test_gemm_entrywise_on_row_scaled_operands(lib, form, Kd):
         err, bound = err[tri], bound[tri]
     print("GEMM | %s | K %d | max |err| / bound %.3g" % (form, Kd, float(np.max(err / bound))))
     assert np.all(err <= bound), (form, Kd, float(np.max(err / bound)))
+
+
+@pytest.mark.parametrize("Kd", [16, 144])
+def test_gemm_lower_and_rectangular_forms_share_one_tile_body(lib, Kd):
+    """The rectangular quarter-tile form (k_gemm_nt_64, operands staged through registers) and the lower form (k_ldlt_trailing_64,
+    operands global -> LDS directly) run the same 64 x 64 tile body from a zero accumulator in the same k order on the same LDS
+    image: on equal inputs they agree bit for bit on every 64 x 64 tile with block row >= block column, and the lower form leaves
+    the 128-tiles above the diagonal as they were."""
+    from cipkkt import _lib as L
+    M = N = 256
+    rng = np.random.default_rng(4000 + Kd)
+    A, B, C0 = (torch.as_tensor(rng.standard_normal(shape), **F64) for shape in ((Kd, M), (Kd, N), (N, M)))   # column-major M x Kd, N x Kd, M x N
+    out = []
+    for lower in (0, 1):
+        dC = C0.clone()
+        L.check(lib.cip_gemm_nt_dev(None, M, N, Kd, -0.75, A.data_ptr(), M, B.data_ptr(), N, dC.data_ptr(), M, lower))
+        torch.cuda.synchronize()
+        out.append(dC.t().cpu().numpy())                       # [row, column]
+    rect, low = out
+    C0h = C0.t().cpu().numpy()
+    assert not np.array_equal(rect, C0h)
+    for bi in range(M // 64):
+        for bj in range(bi + 1):
+            t = np.s_[64 * bi:64 * bi + 64, 64 * bj:64 * bj + 64]
+            assert np.array_equal(low[t], rect[t]), (Kd, bi, bj)
+    above = (np.arange(M)[:, None] // 128) < (np.arange(N)[None, :] // 128)
+    assert np.array_equal(low[above], C0h[above])
 
 
 # -------------------------------------------------------------------------------------------------------------- handles
