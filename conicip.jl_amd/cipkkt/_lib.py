@@ -15,6 +15,7 @@ OP_F, OP_FT, OP_FINV, OP_FINVT = 0, 1, 2, 3
 MAT_Q, MAT_A, MAT_G = 0, 1, 2
 FLAG_DEVICE_PTRS = 1
 FLAG_CSR_HOST = 2
+FLAG_Q_CSR = 4
 E_SINGULAR = -5
 E_UNSUPPORTED = -6
 E_RETRY = -7
@@ -30,7 +31,8 @@ class CipProblem(C.Structure):
                 ("A", C.c_void_p), ("lda", C.c_int),
                 ("A_rowptr", C.c_void_p), ("A_colind", C.c_void_p), ("A_val", C.c_void_p),
                 ("G", C.c_void_p), ("ldg", C.c_int),
-                ("route", C.c_int), ("flags", C.c_int)]
+                ("route", C.c_int), ("flags", C.c_int),
+                ("Q_rowptr", C.c_void_p), ("Q_colind", C.c_void_p), ("Q_val", C.c_void_p)]
 
 
 class CipOptions(C.Structure):

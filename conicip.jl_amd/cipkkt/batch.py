@@ -41,7 +41,7 @@ def _solve_on_stream(pr, device):
     return sol
 
 
-def _solve_many_native(prs, device, in_flight):
+def _solve_many_native(prs, device, in_flight, sparse_q=False):
     """All problems of this rank through `cip_conicip_many` (csrc/batch.hip): one handle + HIP stream per problem,
     `in_flight` native interior-point loops at once on the library's own host threads (no Python in the loop)."""
     import ctypes as C
@@ -58,7 +58,7 @@ def _solve_many_native(prs, device, in_flight):
         for pr in prs:
             st = torch.cuda.Stream(device=device)
             with torch.cuda.stream(st):
-                ks = KKTSystem(pr["Q"], pr["A"], pr.get("G"), pr["cone_dims"], device=device)
+                ks = KKTSystem(pr["Q"], pr["A"], pr.get("G"), pr["cone_dims"], device=device, sparse_q=pr.get("sparse_q", sparse_q))
             ks.set_stream(st.cuda_stream)
             systems.append(ks)
             streams.append(st)
@@ -91,13 +91,14 @@ def _solve_many_native(prs, device, in_flight):
             ks.close()
 
 
-def _solve_problems_native(prs, device, in_flight, mode="auto"):
+def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False):
     """All problems of this rank through the library's batch entry points.
     mode "lockstep": `cip_conicip_lockstep` (csrc/lockstep.hip) -- problems of identical shape advance through the loop
     together, every step one launch with the problem index in the grid; "threads": `cip_conicip_problems`
     (csrc/batch.hip) -- `in_flight` host threads inside the library, each re-loading ONE handle on its own HIP stream
     with the next problem of the queue; "auto": `cip_conicip_mixed` -- every group of problems that share a shape (and
-    hold no chip-wide S cone) in lock-step, the others through the threads.  CIP_BATCH=threads|lockstep overrides "auto"."""
+    hold no chip-wide S cone) in lock-step, the others through the threads.  CIP_BATCH=threads|lockstep overrides "auto".
+    sparse_q (or a problem's own "sparse_q" key): Q goes over in CSR (cipkkt.kkt.make_problem); the form is part of the shape."""
     import ctypes as C
     from . import _lib as L
     from .driver import solution_from_result
@@ -114,7 +115,8 @@ def _solve_problems_native(prs, device, in_flight, mode="auto"):
     with torch.cuda.device(device):
         for i, pr in enumerate(prs):
             cd = [(str(t), int(kk)) for t, kk in pr["cone_dims"]]
-            st, kp, _ = make_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"), device)
+            st, kp, _ = make_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"), device,
+                                      sparse_q=pr.get("sparse_q", sparse_q))
             structs[i] = st
             keep.append(kp)
             dims.append((st.n, st.m, st.p))
@@ -149,7 +151,7 @@ def _solve_problems_native(prs, device, in_flight, mode="auto"):
 
 
 def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None, concurrency=1, native=False,
-                reduce_device=None):
+                reduce_device=None, sparse_q=False):
     """problems: list of dicts(Q, c, A, b, cone_dims, G, d, kwargs).  Each rank solves its
     shard with `solve_fn` (default: the HIP-backed cipkkt.conicIP) and the statistics are
     reduced over ranks:  SUM(iters, n_factor, n_solve, n_optimal, n_problems), MAX(wall).
@@ -159,7 +161,8 @@ def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None
     (n = 2048, 8 problems: 583 KKT solves/s one at a time, 899 with 2 in flight).  `native=True` hands the problems to
     the library's batch entry point `cip_conicip_problems` (host threads inside the library, one re-loaded handle per
     thread: what a C caller uses); `native="handles"` builds all handles first and calls `cip_conicip_many`
-    (605-683 KKT solves/s on the same batch: the setup is not overlapped).
+    (605-683 KKT solves/s on the same batch: the setup is not overlapped).  `sparse_q=True` (native paths; or a "sparse_q"
+    key of a problem dict) hands Q over in CSR.
     Returns (local_solutions, stats_dict)."""
     default_solver = solve_fn is None
     if solve_fn is None:
@@ -172,9 +175,10 @@ def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         shard = [problems[i] for i in mine]
         if native == "handles":
-            out = _solve_many_native(shard, dev, max(1, concurrency))
+            out = _solve_many_native(shard, dev, max(1, concurrency), sparse_q=sparse_q)
         else:
-            out = _solve_problems_native(shard, dev, max(1, concurrency), native if native in ("lockstep", "threads") else "auto")
+            out = _solve_problems_native(shard, dev, max(1, concurrency), native if native in ("lockstep", "threads") else "auto",
+                                         sparse_q=sparse_q)
         for i, sol in zip(mine, out):
             sols[i] = sol
     elif default_solver and concurrency > 1 and len(mine) > 1:

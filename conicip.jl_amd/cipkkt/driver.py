@@ -95,7 +95,7 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
             optTol=1e-6, DTB=0.01, verbose=False,
             maxRefinementSteps=3, maxIters=100, cache_nestodd=False,
             infeasTol=None, refinementThreshold=None,
-            device=None, system=None, keep_iterates=None, driver="native"):
+            device=None, system=None, keep_iterates=None, driver="native", sparse_q=False):
     """minimize 1/2 y'Qy - c'y  s.t.  Ay - b in K,  Gy = d   (src/ConicIP.jl:411-430).
 
     `kktsolver` selects the elimination route of the HIP KKT path: "schur"
@@ -111,7 +111,9 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
     every 3x3 right-hand side / solution crosses PCIe (that is the reference's own boundary).
 
     `driver`: "native" runs the loop in C++ inside libcipkkt (`cip_conicip`, csrc/driver.hip); "python" runs
-    the identical loop below through the per-operation C-ABI entry points (needed for `keep_iterates`)."""
+    the identical loop below through the per-operation C-ABI entry points (needed for `keep_iterates`).
+
+    `sparse_q=True` keeps Q in CSR on the device (cipkkt.kkt.make_problem); the default densifies Q, scipy-sparse or not."""
     t_start = time.perf_counter()
     if infeasTol is None:
         infeasTol = optTol
@@ -144,7 +146,7 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
             kktsolver = "full3x3"
         else:
             plugin, kktsolver = kktsolver, "schur"
-    ks = system if system is not None else KKTSystem(Q, A, G, cone_dims, route=kktsolver, device=device)
+    ks = system if system is not None else KKTSystem(Q, A, G, cone_dims, route=kktsolver, device=device, sparse_q=sparse_q)
     if driver == "native" and keep_iterates is None and plugin is None:
         return _conicIP_native(ks, c_h, b_h, d_h, n, m, p, optTol, DTB, infeasTol, refinementThreshold,
                                maxRefinementSteps, maxIters, verbose, t_start)

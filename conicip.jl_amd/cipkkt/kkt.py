@@ -85,11 +85,15 @@ def pack_scaling(cone_dims, F, FinvT=None):
 
 
 
-def make_problem(Q, A, G, cone_dims, route, device):
+def make_problem(Q, A, G, cone_dims, route, device, sparse_q=False):
     """(cip_problem, keep-alive list, A_is_sparse): every matrix handed over as a DEVICE pointer.  Host arrays are
     uploaded in whatever (row-major) layout they have and re-laid out column-major by a device transpose --
     numpy.asfortranarray of a 2048 x 2048 Q alone cost 33 ms of the 42 ms level 1 took, cip_create_ex itself 3 ms.
-    The staging copies run on torch's current stream: synchronise it before handing the struct to the library."""
+    The staging copies run on torch's current stream: synchronise it before handing the struct to the library.
+
+    sparse_q=True hands Q over as host CSR arrays (CIP_FLAG_Q_CSR: the whole symmetric matrix, O(nnz) on the device, no
+    dense image).  The default stays False -- even a scipy-sparse Q is densified unless the caller asks: the two forms
+    add Q's entries in different orders, and today's callers keep today's bits."""
     n = Q.shape[0]
     m = A.shape[0] if A is not None else 0
     p = G.shape[0] if G is not None else 0
@@ -109,9 +113,19 @@ def make_problem(Q, A, G, cone_dims, route, device):
         keep.append(Mt)            # row-major of M' == column-major of M
         return C.c_void_p(Mt.data_ptr())
 
-    pr.Q, pr.ldq = dense(Q, n, n), n
-    a_sparse = False
     csr_host = False
+    if sparse_q:
+        import scipy.sparse as sp
+        qc = sp.csr_matrix(Q.detach().cpu().numpy() if isinstance(Q, torch.Tensor) else Q)
+        qc.sort_indices()
+        q_h = [np.ascontiguousarray(x, dtype=dt) for x, dt in ((qc.indptr, np.int32), (qc.indices, np.int32), (qc.data, np.float64))]
+        keep += q_h
+        pr.Q_rowptr, pr.Q_colind, pr.Q_val = (C.c_void_p(x.ctypes.data) for x in q_h)
+        pr.Q, pr.ldq = None, n
+        csr_host = True
+    else:
+        pr.Q, pr.ldq = dense(Q, n, n), n
+    a_sparse = False
     if m > 0 and _is_sparse(A):          # (S cones too, round 4: the library expands their rows on the device)
         csr = A.tocsr()
         csr.sort_indices()
@@ -127,15 +141,16 @@ def make_problem(Q, A, G, cone_dims, route, device):
         pr.A, pr.lda = (dense(A, m, n) if m > 0 else None), max(m, 1)
     pr.G, pr.ldg = (dense(G, p, n) if p > 0 else None), max(p, 1)
     pr.route = L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
-    pr.flags = L.FLAG_DEVICE_PTRS | (L.FLAG_CSR_HOST if csr_host else 0)
+    pr.flags = L.FLAG_DEVICE_PTRS | (L.FLAG_CSR_HOST if csr_host else 0) | (L.FLAG_Q_CSR if sparse_q else 0)
     return pr, keep, a_sparse
 
 
 class KKTSystem:
     """Level-1 object: problem matrices resident in HBM, cone layout, workspaces.
-    ≙ what `kktsolver(Q,A,G,cone_dims)` captures (src/kktsolvers.jl:18-28, :180-190, :281-285)."""
+    ≙ what `kktsolver(Q,A,G,cone_dims)` captures (src/kktsolvers.jl:18-28, :180-190, :281-285).
+    sparse_q=True keeps Q in CSR on the device (see make_problem); the default densifies Q, scipy-sparse or not."""
 
-    def __init__(self, Q, A, G, cone_dims, route="schur", device=None):
+    def __init__(self, Q, A, G, cone_dims, route="schur", device=None, sparse_q=False):
         _require_gpu()
         self.lib = L.load()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
@@ -155,7 +170,8 @@ class KKTSystem:
         self.n, self.m, self.p = n, m, p
         self.route = L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
 
-        pr, keep, self.A_sparse = make_problem(Q, A, G, self.cone_dims, self.route, self.device)
+        self.Q_sparse = bool(sparse_q)
+        pr, keep, self.A_sparse = make_problem(Q, A, G, self.cone_dims, self.route, self.device, sparse_q=self.Q_sparse)
         h = C.c_void_p()
         torch.cuda.current_stream(self.device).synchronize()    # staging transposes ran on torch's current stream
         L.check(self.lib.cip_create_ex(C.byref(pr), C.byref(h)))
@@ -349,7 +365,7 @@ class KKTSystem:
         L.check(self.lib.cip_set_stream(self.h, C.c_void_p(stream)))
 
 
-def kktsolver_hip(Q, A, G, cone_dims, route="schur", device=None):
+def kktsolver_hip(Q, A, G, cone_dims, route="schur", device=None, sparse_q=False):
     """The reference's 3-level plugin closure, backed by the HIP library.
 
         solve3x3gen = kktsolver_hip(Q, A, G, cone_dims)
@@ -357,8 +373,8 @@ def kktsolver_hip(Q, A, G, cone_dims, route="schur", device=None):
         a, b, c     = solve3x3(x, y, z)
 
     solves [Q G' -A'; G 0 0; A 0 F'F][a;b;c] = [x;y;z] (src/ConicIP.jl:443-447).
-    F / F_invT are Block-like objects with the reference's element fields."""
-    sysm = KKTSystem(Q, A, G, cone_dims, route=route, device=device)
+    F / F_invT are Block-like objects with the reference's element fields.  sparse_q: see KKTSystem."""
+    sysm = KKTSystem(Q, A, G, cone_dims, route=route, device=device, sparse_q=sparse_q)
 
     def solve3x3gen(F, FinvT=None):
         sysm.set_scaling_packed(sysm.pack_scaling(F, FinvT))
@@ -373,7 +389,7 @@ def kktsolver_hip(Q, A, G, cone_dims, route="schur", device=None):
     return solve3x3gen
 
 
-def kktsolver_2x2_hip(Q, A, G, cone_dims, device=None):
+def kktsolver_2x2_hip(Q, A, G, cone_dims, device=None, sparse_q=False):
     """The reference's 2x2 plugin form (src/ConicIP.jl:450-466; src/kktsolvers.jl:281-310) on the device:
 
         solve2x2gen = kktsolver_2x2_hip(Q, A, G, cone_dims)
@@ -381,7 +397,7 @@ def kktsolver_2x2_hip(Q, A, G, cone_dims, device=None):
         dy, dw      = solve2x2(y, w)          # [Q + A'(F'F)^-1 A, G'; G, 0][dy; dw] = [y; w]
 
     to be wrapped by `pivot` exactly as `pivot(ConicIP.kktsolver_2x2)`."""
-    sysm = KKTSystem(Q, A, G, cone_dims, route="schur", device=device)
+    sysm = KKTSystem(Q, A, G, cone_dims, route="schur", device=device, sparse_q=sparse_q)
 
     def solve2x2gen(F, FinvT=None):
         sysm.set_scaling_packed(sysm.pack_scaling(F, FinvT))
@@ -420,6 +436,6 @@ def pivot(kktsolver_2x2):
     return kktsolver
 
 
-def kktsolver_hip_full3x3(Q, A, G, cone_dims, device=None):
+def kktsolver_hip_full3x3(Q, A, G, cone_dims, device=None, sparse_q=False):
     """Same interface, literal 3x3 assembly route (src/kktsolvers.jl:254-256)."""
-    return kktsolver_hip(Q, A, G, cone_dims, route="full3x3", device=device)
+    return kktsolver_hip(Q, A, G, cone_dims, route="full3x3", device=device, sparse_q=sparse_q)

@@ -97,7 +97,7 @@ static void free_all(cip_handle *h) {
     if (h->ldlt_side) { cip_ldlt_side_destroy(h->ldlt_side); h->ldlt_side = nullptr; }
     if (h->gx_solve) { (void)hipGraphExecDestroy(h->gx_solve); h->gx_solve = nullptr; }
     if (h->cs.lg) { cip_sdp_large_destroy(h->cs.lg); h->cs.lg = nullptr; }
-    void *ptrs[] = {h->cs.d_bigq, h->cs.d_ritems, h->cs.d_packq, h->cs.d_sidx_small, h->cs.d_sidx, h->cs.d_sdpws, h->cs.d_sdpvec, h->cs.d_sdpflag, h->Q, h->symv_ws, h->A, h->At, h->A_rp, h->A_ci, h->A_v, h->T_rp, h->T_ci, h->T_v, h->kdiag, h->row_cone, h->G, h->Gt,
+    void *ptrs[] = {h->cs.d_bigq, h->cs.d_ritems, h->cs.d_packq, h->cs.d_sidx_small, h->cs.d_sidx, h->cs.d_sdpws, h->cs.d_sdpvec, h->cs.d_sdpflag, h->Q, h->symv_ws, h->Q_rp, h->Q_ci, h->Q_v, h->A, h->At, h->A_rp, h->A_ci, h->A_v, h->T_rp, h->T_ci, h->T_v, h->kdiag, h->row_cone, h->G, h->Gt,
                     h->cs.d_cones, h->cs.d_items, h->cs.d_scal, h->cs.d_partial, h->cs.d_scalar, h->K, h->Wt, h->syrk_ws, h->Gm, h->AtS, h->WtS,
                     h->ws_base, h->rhs, h->mt1, h->mt2, h->mt3, h->nt1, h->pt1, h->dot_scratch, h->stage, h->drv, h->ref, h->c2x2, h->many, h->many_stage};
     for (void *p : ptrs)
@@ -140,14 +140,123 @@ static int transpose_dev(hipStream_t s, const double *src, long ld_src, int rows
     return 0;
 }
 
-// Contents of Q, G (+G'), A (+A', or the CSR of A and of A') into the handle's buffers, on its stream.
+// ---- CSR Q (CIP_FLAG_Q_CSR): the level-1 check, on the host, O(nnz).  Device-resident arrays are copied back first (as A's are).
+// Two counting-sort transposes: T = Q' lists, for every i, the stored (j, i) with j ascending; its transpose S is Q again with the
+// columns of every row ascending.  A duplicate is a repeated column in a row of S; Q is symmetric when S and T agree entry for entry,
+// values bit for bit.  On success the handle's staging vectors hold S (what is uploaded: the mat-vec's summation order does not
+// depend on the caller's column order) and *maxrow the longest row.  No device allocation, nothing enqueued.
+// expect_nnz >= 0 (cip_update_problem): the count the handle was created with.
+static void csr_transpose(int n, const std::vector<int> &rp, const std::vector<int> &ci, const std::vector<double> &v,
+                          std::vector<int> &trp, std::vector<int> &tci, std::vector<double> &tv) {
+    const int nnz = rp[n];
+    trp.assign(n + 1, 0); tci.assign(nnz > 0 ? nnz : 1, 0); tv.assign(nnz > 0 ? nnz : 1, 0.0);
+    for (int q = 0; q < nnz; ++q) trp[ci[q] + 1]++;
+    for (int i = 0; i < n; ++i) trp[i + 1] += trp[i];
+    std::vector<int> fill(trp.begin(), trp.end() - 1);
+    for (int r = 0; r < n; ++r)
+        for (int q = rp[r]; q < rp[r + 1]; ++q) { const int d = fill[ci[q]]++; tci[d] = r; tv[d] = v[q]; }
+}
+static int stage_Q_csr(cip_handle *h, const cip_problem *pr, int expect_nnz, int *maxrow) {
+    const int n = pr->n;
+    if (pr->Q) { cip_set_error("CIP_FLAG_Q_CSR is set but Q is not NULL"); return CIP_E_INVALID; }
+    if (!pr->Q_rowptr) { cip_set_error("CSR Q: Q_rowptr is NULL"); return CIP_E_INVALID; }
+    const bool csr_dev = (pr->flags & CIP_FLAG_DEVICE_PTRS) && !(pr->flags & CIP_FLAG_CSR_HOST);
+    std::vector<int> rp(n + 1), ci, trp, tci;
+    std::vector<double> v, tv;
+    if (csr_dev) CIP_HIP_CHECK(hipMemcpy(rp.data(), pr->Q_rowptr, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
+    else memcpy(rp.data(), pr->Q_rowptr, sizeof(int) * (n + 1));
+    if (rp[0] != 0) { cip_set_error("CSR Q: rowptr[0] is %d, not 0", rp[0]); return CIP_E_INVALID; }
+    for (int i = 0; i < n; ++i)
+        if (rp[i + 1] < rp[i]) { cip_set_error("CSR Q: the row pointer decreases at row %d (%d after %d)", i, rp[i + 1], rp[i]); return CIP_E_INVALID; }
+    const int nnz = rp[n];
+    if (expect_nnz >= 0 && nnz != expect_nnz) {
+        cip_set_error("cip_update_problem: CSR Q has %d non-zeros, the handle holds %d", nnz, expect_nnz);
+        return CIP_E_INVALID;
+    }
+    if (nnz > 0 && !pr->Q_colind) { cip_set_error("CSR Q: Q_colind is NULL"); return CIP_E_INVALID; }
+    if (nnz > 0 && !pr->Q_val) { cip_set_error("CSR Q: Q_val is NULL"); return CIP_E_INVALID; }
+    ci.assign(nnz > 0 ? nnz : 1, 0); v.assign(nnz > 0 ? nnz : 1, 0.0);
+    if (nnz > 0) {
+        if (csr_dev) {
+            CIP_HIP_CHECK(hipMemcpy(ci.data(), pr->Q_colind, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+            CIP_HIP_CHECK(hipMemcpy(v.data(), pr->Q_val, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+        } else {
+            memcpy(ci.data(), pr->Q_colind, sizeof(int) * nnz);
+            memcpy(v.data(), pr->Q_val, sizeof(double) * nnz);
+        }
+    }
+    int mx = 0;
+    for (int i = 0; i < n; ++i) {
+        if (rp[i + 1] - rp[i] > mx) mx = rp[i + 1] - rp[i];
+        for (int q = rp[i]; q < rp[i + 1]; ++q)
+            if (ci[q] < 0 || ci[q] >= n) {
+                cip_set_error("CSR Q: entry %d of row %d has column index %d outside [0, %d)", q - rp[i], i, ci[q], n);
+                return CIP_E_INVALID;
+            }
+    }
+    csr_transpose(n, rp, ci, v, trp, tci, tv);                 // T = Q'
+    std::vector<int> &srp = h->st_qrp, &sci = h->st_qci;
+    std::vector<double> &sv = h->st_qv;
+    csr_transpose(n, trp, tci, tv, srp, sci, sv);              // S = Q, columns ascending
+    for (int i = 0; i < n; ++i)
+        for (int q = srp[i] + 1; q < srp[i + 1]; ++q)
+            if (sci[q] == sci[q - 1]) { cip_set_error("CSR Q: entry (%d, %d) is stored twice", i, sci[q]); return CIP_E_INVALID; }
+    for (int i = 0; i < n; ++i) {
+        int a = srp[i], b = trp[i];
+        const int a1 = srp[i + 1], b1 = trp[i + 1];
+        while (a < a1 || b < b1) {
+            if (b == b1 || (a < a1 && sci[a] < tci[b])) {
+                cip_set_error("CSR Q: entry (%d, %d) has no stored mirror entry (%d, %d)", i, sci[a], sci[a], i);
+                return CIP_E_INVALID;
+            }
+            if (a == a1 || tci[b] < sci[a]) {
+                cip_set_error("CSR Q: entry (%d, %d) has no stored mirror entry (%d, %d)", tci[b], i, i, tci[b]);
+                return CIP_E_INVALID;
+            }
+            if (memcmp(&sv[a], &tv[b], sizeof(double)) != 0) {
+                cip_set_error("CSR Q: entry (%d, %d) = %.17g and its mirror entry (%d, %d) = %.17g differ", i, sci[a], sv[a], sci[a], i, tv[b]);
+                return CIP_E_INVALID;
+            }
+            ++a; ++b;
+        }
+    }
+    if (maxrow) *maxrow = mx;
+    return 0;
+}
+// the mat-vec form of a CSR Q, from its longest row: one thread per row, or one wave per row (vecops.hip) above the threshold
+static int q_wave_form(int maxrow) {
+    static const int wave_min = cip_env_int("CIP_QSPMV_WAVE_MIN", CIP_SPMV_WAVE_MIN);
+    return maxrow > wave_min ? 1 : 0;
+}
+
+// y = alpha Q x + beta y with the handle's Q, dense or CSR (cip_gemv_dev(CIP_MAT_Q), the refinement's residual).  symv: a dense Q
+// may go through the symmetric mat-vec (the refinement's residual never did: it keeps its bits)
+int cip_mul_Q(cip_handle *h, double alpha, const double *x, double beta, double *y, bool symv) {
+    hipStream_t s = h->stream;
+    if (h->Q_sparse)
+        return h->Q_wave ? cip_spmv_csr_wave(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y)
+                         : cip_spmv_csr(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y);
+    if (symv && h->symv_ws && !(((uintptr_t)x) & 15)) return cip_symv_lower(s, h->n, alpha, h->Q, h->n, x, beta, y, h->symv_ws);
+    return cip_gemv_t(s, h->n, h->n, alpha, h->Q, h->n, x, beta, y);
+}
+
+// Contents of Q, G (+G'), A (+A', or the CSR of A and of A') into the handle's buffers, on its stream.  A CSR Q has been checked and
+// staged by stage_Q_csr (the caller waited for an earlier upload from the staging vectors first).
 static int upload_problem(cip_handle *h, const cip_problem *pr) {
     const int n = h->n, m = h->m, p = h->p;
     const bool dev = (pr->flags & CIP_FLAG_DEVICE_PTRS) != 0;
     hipStream_t s = h->stream;
     int rc;
+    const bool was_live = h->staging_live;                  // an earlier upload may still be reading A's staging vectors
     cip_sdp_large_invalidate(h->cs.lg);                     // (the mat(a_i) images of the large S cones follow A)
-    if ((rc = upload_matrix(h->Q, n, pr->Q, pr->ldq > 0 ? pr->ldq : n, n, n, dev, s))) return rc;
+    if (h->Q_sparse) {
+        CIP_HIP_CHECK(hipMemcpyAsync(h->Q_rp, h->st_qrp.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, s));
+        if (h->Q_nnz > 0) {
+            CIP_HIP_CHECK(hipMemcpyAsync(h->Q_ci, h->st_qci.data(), sizeof(int) * h->Q_nnz, hipMemcpyHostToDevice, s));
+            CIP_HIP_CHECK(hipMemcpyAsync(h->Q_v, h->st_qv.data(), sizeof(double) * h->Q_nnz, hipMemcpyHostToDevice, s));
+        }
+        h->staging_live = true;
+    } else if ((rc = upload_matrix(h->Q, n, pr->Q, pr->ldq > 0 ? pr->ldq : n, n, n, dev, s))) return rc;
     if (p > 0) {
         if ((rc = upload_matrix(h->G, p, pr->G, pr->ldg > 0 ? pr->ldg : p, p, n, dev, s))) return rc;
         if ((rc = transpose_dev(s, h->G, p, p, n, h->Gt, n))) return rc;
@@ -161,7 +270,7 @@ static int upload_problem(cip_handle *h, const cip_problem *pr) {
     }
     // CSR of A (given) and of A' (built here on the host).  The host arrays live in the handle: the uploads below are
     // asynchronous and nothing here waits for them (a previous upload from the same vectors is waited for first).
-    if (h->staging_live) CIP_HIP_CHECK(hipStreamSynchronize(s));
+    if (was_live) CIP_HIP_CHECK(hipStreamSynchronize(s));
     std::vector<int> &rp = h->st_rp, &ci = h->st_ci, &trp = h->st_trp, &tci = h->st_tci;
     std::vector<double> &av = h->st_av, &tv = h->st_tv;
     rp.assign(m + 1, 0);
@@ -217,10 +326,17 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
     if (cip_kernels_init()) return CIP_E_HIP;
     const int n = pr->n, m = pr->m, p = pr->p;
     if (n <= 0 || m < 0 || p < 0 || pr->ncones < 0) { cip_set_error("bad dimensions n=%d m=%d p=%d", n, m, p); return CIP_E_INVALID; }
-    if (!pr->Q) { cip_set_error("Q is NULL"); return CIP_E_INVALID; }
+    const bool q_csr = (pr->flags & CIP_FLAG_Q_CSR) != 0;
+    if (!q_csr && !pr->Q) { cip_set_error("Q is NULL"); return CIP_E_INVALID; }
     if (m > 0 && !pr->A && !(pr->A_rowptr && pr->A_colind && pr->A_val)) { cip_set_error("A is NULL"); return CIP_E_INVALID; }
     if (p > 0 && !pr->G) { cip_set_error("G is NULL"); return CIP_E_INVALID; }
     if (pr->route != CIP_ROUTE_SCHUR && pr->route != CIP_ROUTE_FULL3X3) { cip_set_error("bad route"); return CIP_E_INVALID; }
+    if (q_csr) {                                          // checked on the host before anything is allocated on the device
+        int maxrow = 0;
+        const int rcq = stage_Q_csr(h, pr, -1, &maxrow);
+        if (rcq) return rcq;
+        h->Q_sparse = true; h->Q_nnz = h->st_qrp[n]; h->Q_wave = q_wave_form(maxrow);
+    }
     h->n = n; h->m = m; h->p = p; h->ncones = pr->ncones; h->route = pr->route;
     const bool dev = (pr->flags & CIP_FLAG_DEVICE_PTRS) != 0;
     hipStream_t s = h->stream;   // default (null) stream until cip_set_stream
@@ -365,8 +481,12 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
     h->ldk = h->Npad;
 
     // ---- Q, G, A: buffers here, contents by upload_problem (also used by cip_update_problem)
-    DMALLOC(h->Q, sizeof(double) * (size_t)n * n);
-    if (n >= 2048 && n % 128 == 0) DMALLOC(h->symv_ws, sizeof(double) * 2 * (size_t)(n / 128) * n);
+    if (h->Q_sparse) {                                    // O(nnz): neither the dense image nor the symv tables
+        DMALLOC(h->Q_rp, sizeof(int) * (n + 1)); DMALLOC(h->Q_ci, sizeof(int) * h->Q_nnz); DMALLOC(h->Q_v, sizeof(double) * h->Q_nnz);
+    } else {
+        DMALLOC(h->Q, sizeof(double) * (size_t)n * n);
+        if (n >= 2048 && n % 128 == 0) DMALLOC(h->symv_ws, sizeof(double) * 2 * (size_t)(n / 128) * n);
+    }
     DMALLOC(h->G, sizeof(double) * (size_t)p * n);
     DMALLOC(h->Gt, sizeof(double) * (size_t)p * n);
     h->A_sparse = (pr->A == NULL && m > 0);
@@ -478,8 +598,19 @@ extern "C" int cip_update_problem(cip_handle *h, const cip_problem *pr) {
         (pr->A == NULL && pr->m > 0) != h->A_sparse) { cip_set_error("cip_update_problem: shape differs from the handle's"); return CIP_E_INVALID; }
     for (int c = 0; c < pr->ncones; ++c)
         if (pr->cone_type[c] != h->h_cones[c].type || pr->cone_dim[c] != h->h_cones[c].dim) { cip_set_error("cip_update_problem: cone %d differs", c); return CIP_E_INVALID; }
-    if (!pr->Q || (h->p > 0 && !pr->G)) { cip_set_error("NULL matrix"); return CIP_E_INVALID; }
+    if (((pr->flags & CIP_FLAG_Q_CSR) != 0) != h->Q_sparse) {
+        cip_set_error("cip_update_problem: Q is %s, the handle was created with a %s Q", h->Q_sparse ? "dense" : "CSR", h->Q_sparse ? "CSR" : "dense");
+        return CIP_E_INVALID;
+    }
+    if ((!h->Q_sparse && !pr->Q) || (h->p > 0 && !pr->G)) { cip_set_error("NULL matrix"); return CIP_E_INVALID; }
     int rc;
+    if (h->Q_sparse) {
+        // refused (other nnz, or the level-1 check fails) before anything of the handle's device state is touched: it stays usable
+        if (h->staging_live) { CIP_HIP_CHECK(hipStreamSynchronize(h->stream)); h->staging_live = false; }
+        int maxrow = 0;
+        if ((rc = stage_Q_csr(h, pr, h->Q_nnz, &maxrow))) return rc;
+        h->Q_wave = q_wave_form(maxrow);
+    }
     if ((rc = upload_problem(h, pr))) return rc;
     h->assembled = h->factored = false;
     h->info_pending = false;
@@ -856,7 +987,7 @@ static int kkt3_residual(cip_handle *h, const double *x, const double *y, const 
     const int n = h->n, m = h->m, p = h->p;
     int rc;
     if ((rc = cip_axpby(s, n, 1.0, x, 0.0, rx))) return rc;
-    if ((rc = cip_gemv_t(s, n, n, -1.0, h->Q, n, a, 1.0, rx))) return rc;
+    if ((rc = cip_mul_Q(h, -1.0, a, 1.0, rx, false))) return rc;
     if (p > 0) {
         if ((rc = cip_gemv_t(s, p, n, -1.0, h->G, p, b, 1.0, rx))) return rc;
         if ((rc = cip_axpby(s, p, 1.0, y, 0.0, ry))) return rc;
@@ -1209,9 +1340,7 @@ extern "C" int cip_gemv_dev(cip_handle *h, int which, int trans, double alpha, c
     if (!h) return CIP_E_INVALID;
     hipStream_t s = h->stream;
     switch (which) {
-        case CIP_MAT_Q:                                                                     // Q symmetric
-            if (h->symv_ws && !(((uintptr_t)x) & 15)) return cip_symv_lower(s, h->n, alpha, h->Q, h->n, x, beta, y, h->symv_ws);
-            return cip_gemv_t(s, h->n, h->n, alpha, h->Q, h->n, x, beta, y);
+        case CIP_MAT_Q: return cip_mul_Q(h, alpha, x, beta, y);                             // Q symmetric
         case CIP_MAT_A: return trans ? mul_At(h, alpha, x, beta, y) : mul_A(h, alpha, x, beta, y);
         case CIP_MAT_G:
             if (h->p == 0) {

@@ -84,6 +84,58 @@ static void launch_copy_block_lower(hipStream_t s, double *K, long ldk, int r0, 
     }
 }
 
+// ---------------------------------------------------------------- Q block from a CSR Q (CIP_FLAG_Q_CSR)
+// Q is symmetric and stored whole (level 1 checks it), so whoever owns COLUMN j of the column-major K reads CSR ROW j: entry
+// (j, i) of the row is Q[i, j], and all of a column's writes land in that one column.  No duplicates: every entry of K is touched
+// at most once per launch -- no atomics, nothing to order between workgroups.
+// An entry is taken when the dense copy / the Schur formation would have written it: ((r0 + i) >> shift) >= ((r0 + j) >> shift),
+// shift 7 = the 128-tiles on or below the diagonal (k_copy_block_lower), 6 = the 64-quarter-tiles (cip_syrk_schur).
+//
+// Schur route with a CSR A (r0 = 0): ONE pass per column instead of the copy of n^2 / 2 doubles out of a dense Q -- the
+// workgroup zeroes column j from the top of its diagonal tile down to row n (16-byte stores when `vec`: K 16-byte aligned, ldk
+// even; the tile top is a multiple of 128), then scatters the column's entries.
+__global__ __launch_bounds__(256) void k_qcsr_fill_cols(double *K, long ldk, int n, const int *rp, const int *ci, const double *v, int vec,
+                                                         CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO4(cb, K, rp, ci, v);
+    const int j = blockIdx.x, tid = threadIdx.x;
+    if (j >= n) return;
+    double *col = K + (long)j * ldk;
+    const int z0 = j & ~127;
+    if (vec) {
+        const int nv = (n - z0) >> 1;
+        for (int t = tid; t < nv; t += 256) *(v2d *)(col + z0 + 2 * t) = (v2d){0.0, 0.0};
+        if (((n - z0) & 1) && tid == 0) col[n - 1] = 0.0;
+    } else {
+        for (int i = z0 + tid; i < n; i += 256) col[i] = 0.0;
+    }
+    __syncthreads();                                            // the zeroes of the whole workgroup land before its entries
+    const int q1 = rp[j + 1];
+    for (int q = rp[j] + tid; q < q1; q += 256) {
+        const int i = ci[q];
+        if ((i >> 7) >= (j >> 7)) col[i] = v[q];
+    }
+}
+// The scatter alone, one WAVE per column (four columns per workgroup), at row / column offset r0: K[r0 + i, r0 + j] = Q[i, j]
+// (full 3x3 route: K was zeroed) or += Q[i, j] (Schur route with a dense A, behind the Qin-less Schur formation)
+template <bool ADD>
+__global__ __launch_bounds__(256) void k_qcsr_scatter(double *K, long ldk, int r0, int n, const int *rp, const int *ci, const double *v,
+                                                       int shift, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO4(cb, K, rp, ci, v);
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n) return;
+    double *col = K + r0 + (long)(r0 + j) * ldk;
+    const int q1 = rp[j + 1];
+    for (int q = rp[j] + lane; q < q1; q += 64) {
+        const int i = ci[q];
+        if (((r0 + i) >> shift) < ((r0 + j) >> shift)) continue;
+        if (ADD) col[i] += v[q];
+        else col[i] = v[q];
+    }
+}
+
 // ---------------------------------------------------------------- sparse-A Schur terms (R and Q cones)
 // K[i, j] += sum_r w_r a_ri a_rj  (i >= j), w_r = 1/d_r^2 (R), -J_rr/beta^2 (Q).  One thread per variable i OWNS row i
 // of the lower triangle: it walks column i of A (= row i of the CSR of A', rows r ascending) and, for every r, row r
@@ -306,14 +358,17 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
         if ((rc = cip_cones_scale_At(s, h->cs, n, h->At, h->npad, h->Wt, h->npad))) return rc;
         // (algorithmic work of the Schur formation: m n^2 flop on the lower half)
         if ((rc = cip_prof_slot_begin(CIP_PROF_SYRK, s, (double)h->m * (double)n * (double)n * (cip_in_batch() ? (double)__builtin_popcountll(cip_tl_bz.mask) : 1.0)))) return rc;
+        // (CSR Q: the Schur formation stores W W' alone -- h->Q is NULL -- and the stored entries of Q are added, each touched once)
         if ((rc = cip_syrk_schur(s, h->npad, h->mpad, n, 1.0, h->Wt, h->npad, h->Q, n, h->K, h->ldk, h->syrk_ws, h->syrk_n, h->syrk_len))) return rc;
         if ((rc = cip_prof_slot_end(CIP_PROF_SYRK, s))) return rc;
+        if (h->Q_sparse && h->Q_nnz > 0)
+            cip_launch_b(k_qcsr_scatter<true>, dim3((n + 3) / 4), dim3(256), 0, s, h->K, h->ldk, 0, n, h->Q_rp, h->Q_ci, h->Q_v, 6);
     } else {
         const int lazy_now = g_lazy_copy.load(std::memory_order_relaxed);
         const int lazy_on = lazy_now < 0 ? cip_lazy_copy_set(-1) : lazy_now;
         bool all_r = h->m > 0 && h->nq == 0 && !h->cs.has_S;
         const int nb0 = cip_ldlt_outer_block_for(h->Npad);
-        if (lazy_on && lazy_ok && all_r && h->A_one_per_row && p == 0 && h->Npad == n && n > nb0 && h->reg_rel <= 0.0 && h->kdiag &&
+        if (!h->Q_sparse && lazy_on && lazy_ok && all_r && h->A_one_per_row && p == 0 && h->Npad == n && n > nb0 && h->reg_rel <= 0.0 && h->kdiag &&
             copy_lower_vectorisable(h->K, h->ldk, 0, h->Q, (long)n, n)) {
             launch_copy_block_lower(s, h->K, h->ldk, 0, h->Q, (long)n, n, 1.0, nb0);
             cip_launch_b(k_schur_diag_lazy, dim3((n + 255) / 256), dim3(256), 0, s, n, nb0, h->T_rp, h->T_ci, h->T_v, h->A_rp, h->A_ci, h->A_v,
@@ -322,7 +377,10 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
             h->ws.lazyC = h->Q; h->ws.lazy_ld = n; h->ws.lazy_diag = h->kdiag;
             return 0;
         }
-        if (n > 0) {
+        if (h->Q_sparse) {
+            const int vec = !(h->ldk & 1) && !(((uintptr_t)h->K) & 15);
+            cip_launch_b(k_qcsr_fill_cols, dim3(n), dim3(256), 0, s, h->K, h->ldk, n, h->Q_rp, h->Q_ci, h->Q_v, vec);
+        } else if (n > 0) {
             launch_copy_block_lower(s, h->K, h->ldk, 0, h->Q, (long)n, n, 1.0);
         }
         if (h->m > 0) {
@@ -372,7 +430,10 @@ static int assemble_full(cip_handle *h) {
             cip_launch_b(k_scatter_negA, dim3((n + 255) / 256), dim3(256), 0, s, n, h->T_rp, h->T_ci, h->T_v,
                                h->K, h->ldk, m);
     }
-    if (n > 0)
+    if (h->Q_sparse) {
+        if (h->Q_nnz > 0)
+            cip_launch_b(k_qcsr_scatter<false>, dim3((n + 3) / 4), dim3(256), 0, s, h->K, h->ldk, m, n, h->Q_rp, h->Q_ci, h->Q_v, 7);
+    } else if (n > 0)
         launch_copy_block_lower(s, h->K, h->ldk, m, h->Q, (long)n, n, 1.0);
     if (p > 0)
         cip_launch_b(k_copy_block, dim3((p + 255) / 256, n < 32768 ? n : 32768), dim3(256), 0, s, h->K, h->ldk, m + n, m, h->G,

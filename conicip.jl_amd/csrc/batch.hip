@@ -77,6 +77,7 @@ extern "C" int cip_conicip_problems(int count, const cip_problem *probs, const d
             const int i = next.fetch_add(1);
             if (i >= count) break;
             int rc = 0;
+            // (refused for another shape -- another Q form, dense or CSR, or another nnz of a CSR Q or A included: new handle)
             if (h && cip_update_problem(h, &probs[i]) != 0) { cip_destroy(h); h = nullptr; }     // other shape: new handle
             if (!h) {
                 rc = cip_create_ex(&probs[i], &h);

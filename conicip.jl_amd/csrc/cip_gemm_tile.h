@@ -5,7 +5,8 @@
 #include "cip_internal.h"
 
 // epilogue of a tile body.  EPI_LAZYC: C = Cin + alpha acc with Cin = Qin (ldq), Cdiag[i] on its diagonal
-enum { EPI_ACCUM = 0, EPI_SYRKQ = 2, EPI_STORE = 3, EPI_LAZYC = 4 };
+// EPI_SYRK0: EPI_SYRKQ without a Qin (C = alpha acc inside the valid corner): the Schur formation of a handle with a CSR Q
+enum { EPI_ACCUM = 0, EPI_SYRKQ = 2, EPI_STORE = 3, EPI_LAZYC = 4, EPI_SYRK0 = 5 };
 
 // The GEMM kernels' parameter block, filled by the launchers of gemm_f64.hip (and, on the device, by the kernels that run a tile
 // body on operands of their own: diag.hip, ldlt.hip: k_solve_premul).  A kernel reads the fields of its form only.
@@ -148,6 +149,11 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
                 const v2d c = g.alpha * val;
                 *(v2d *)cp = c;
                 if (g.Ct) { g.Ct[col + row * g.ldct] = c.x; g.Ct[col + (row + 1) * g.ldct] = c.y; }
+            } else if (EPI == EPI_SYRK0) {    // C = alpha acc inside the valid n x n corner
+                if (col < g.nvalid) {
+                    if (row + 1 < g.nvalid) *(v2d *)cp = g.alpha * val;
+                    else if (row < g.nvalid) *cp = g.alpha * val.x;
+                }
             } else if (col < g.nvalid) {      // EPI_SYRKQ: C = Qin + alpha acc inside the valid n x n corner
                 if (row + 1 < g.nvalid) {
                     const double *qp = g.Qin + row + col * g.ldq;       // Q keeps the caller's (possibly odd) pitch

@@ -18,7 +18,12 @@ struct cip_handle {
     bool arena_overflow = false;
 
     // ---- problem data, device resident for the lifetime of the handle (level 1)
-    double *Q = nullptr;            // n x n, ld n
+    double *Q = nullptr;            // n x n, ld n            (dense Q only)
+    // CSR Q (CIP_FLAG_Q_CSR): the whole symmetric matrix, columns of a row ascending (level 1 sorts them), no dense image and no
+    // symv tables.  Q_wave: the mat-vec form chosen at level 1 from the longest row (api.hip: cip_mul_Q)
+    bool Q_sparse = false;
+    int Q_nnz = 0, Q_wave = 0;
+    int *Q_rp = nullptr, *Q_ci = nullptr; double *Q_v = nullptr;
     double *symv_ws = nullptr;      // partial-sum tables of the symmetric mat-vec (n a multiple of 128, n >= 2048), else null
     bool A_sparse = false;
     bool A_one_per_row = false;     // CSR A with at most one entry per row (A = I, bound constraints): A'(F'F)^-1 A is diagonal for R cones
@@ -38,6 +43,7 @@ struct cip_handle {
     // host staging of the small tables and of the CSR arrays: asynchronous uploads read them after the call has returned
     std::vector<int> st_rp, st_ci, st_trp, st_tci, st_rowcone, st_sidx, st_small, st_bigq, st_ritems, st_packq;
     std::vector<double> st_av, st_tv;
+    std::vector<int> st_qrp, st_qci; std::vector<double> st_qv;
     bool staging_live = false;
 
     // ---- cones / scaling (level 2 input)
@@ -105,6 +111,7 @@ struct cip_handle {
 int cip_lazy_copy_set(int on);       // assemble.hip
 int cip_scatter_AtS(cip_handle *h);   // assemble.hip: CSR A with S cones: their rows of A' as a dense block (h->AtS)
 int cip_assemble(cip_handle *h, bool lazy_ok = false);     // assemble.hip; lazy_ok: the caller factors right away (see assemble_schur)
+int cip_mul_Q(cip_handle *h, double alpha, const double *x, double beta, double *y, bool symv = true);   // api.hip: y = alpha Q x + beta y, dense or CSR Q
 int cip_handle_alloc(cip_handle *h, void **out, size_t bytes);      // api.hip
 int cip_create_in_arena(const struct cip_problem *pr, char *slab, size_t cap, hipStream_t stream, cip_handle **out);   // api.hip
 size_t cip_driver_bytes(const cip_handle *h);                        // driver.hip: vectors of the interior-point loop

@@ -104,6 +104,7 @@ int cip_gemm_rect(hipStream_t s, int M, int N, int K, double alpha, const double
 // Schur formation C = Qin + alpha W W' for i, j < nvalid on the lower 128-tiles (W: M x K).  split_n > 1 with a workspace: the k range
 // is cut into split_n slices of split_len columns (cip_syrk_split), every slice's product goes to its own M x M image in
 // split_ws, a second launch adds them up in slice order together with Qin
+// Qin == NULL: C = alpha W W' (a CSR Q is added afterwards, assemble.hip) -- epilogues of their own, the forms with a Qin are untouched
 int cip_syrk_schur(hipStream_t s, int M, int K, int nvalid, double alpha, const double *W, long ldw, const double *Qin, long ldq, double *C, long ldc,
                    double *split_ws, int split_n, int split_len);
 // how cip_syrk_schur wants an (M x M, K) Schur formation split: number of slices (1: no split) and their length
@@ -310,6 +311,12 @@ int cip_gemv_t(hipStream_t s, int rows, int cols, double alpha, const double *A,
                const double *x, double beta, double *y);     // y[j] = alpha * sum_i A[i + j*lda] x[i] + beta y[j]
 int cip_spmv_csr(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val,
                  double alpha, const double *x, double beta, double *y);
+// the same with one WAVE per row (lane-strided loads, wave sum).  A CSR Q whose longest row has more than CIP_SPMV_WAVE_MIN entries takes it:
+// measured at n = 4096 on banded matrices, the two forms are level (3.5-3.7 us, launch-bound) up to 5 entries per row, at 9 the wave form
+// leads (3.6 against 3.9 us), at 33 it is 3.6 against 12.7, at 2049 20.6 against 1418 (DESIGN_LOG.md, "A CSR objective matrix")
+#define CIP_SPMV_WAVE_MIN 8
+int cip_spmv_csr_wave(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val,
+                      double alpha, const double *x, double beta, double *y);
 int cip_dots(hipStream_t s, int count, const double *const *x_host, const double *const *y_host,
              const int *len_host, double *scratch_dev, double *out_host);
 int cip_axpby(hipStream_t s, int len, double alpha, const double *x, double beta, double *y);

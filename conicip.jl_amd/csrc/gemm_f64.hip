@@ -8,7 +8,8 @@
 //   cip_gemm_rect         k_gemm_nt_64 (64x64, register staging, raised priority) below 256 128-tiles: the wide and short in-block
 //                         update of the three-launch panel chain (K = 128); k_gemm_nt_128 (128x128) from there on
 //   cip_syrk_schur        S = Q + (A'F^-1)(A'F^-1)', K = m: k_syrkq_64<GLDS> on quarter tiles; with few tiles and K >= 4096 the k range
-//                         in slices, k_syrk_splitk_64 (or, <= 64 tiles and K >= 16384, k_syrk_splitk_128) + k_syrk_reduce
+//                         in slices, k_syrk_splitk_64 (or, <= 64 tiles and K >= 16384, k_syrk_splitk_128) + k_syrk_reduce; without a
+//                         Qin (CSR Q) the same launches with epilogues that store alpha W W' alone (EPI_SYRK0, k_syrk_reduce<false>)
 //   cip_gemm_batched_64   k_gemm_nt_64_batched (64x64, optional transposed copy / tile selection): block-inverse doubling
 //                         (ldlt.hip), congruences of the large S cones (sdp_large.hip)
 //   cip_gemm_batched_16   k_gemm_nt_16_batched (16x16, k split over the four waves, no LDS staging): the doubling of the last
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(256) void k_gemm_nt_16_batched(GemmArgs g, CipBatch
 }
 
 // Schur formation S = Q + Wt Wt' (lower tiles) in quarter tiles: the long-K (K = m) counterpart of the trailing update
-template <bool GLDS>
+template <bool GLDS, int EPI = EPI_SYRKQ>
 __global__ __launch_bounds__(256, 4) void k_syrkq_64(GemmArgs g, CipBatch cb) {
     __shared__ __attribute__((aligned(16))) double lds[2 * 2 * CIP_KT * SB];   // 32 KB
     bool live;
@@ -248,7 +249,7 @@ __global__ __launch_bounds__(256, 4) void k_syrkq_64(GemmArgs g, CipBatch cb) {
     lower_tile_coords((int)(blockIdx.x >> 2), bi, bj);
     const int sub = blockIdx.x & 3;
     if (bi == bj && sub == 2) return;
-    gemm_tile_64<EPI_SYRKQ, GLDS>(g, lds, (long)bi * CIP_NB + (sub & 1) * SB, (long)bj * CIP_NB + (sub >> 1) * SB);
+    gemm_tile_64<EPI, GLDS>(g, lds, (long)bi * CIP_NB + (sub & 1) * SB, (long)bj * CIP_NB + (sub >> 1) * SB);
 }
 
 // The same with few output tiles and a long K -- config 4: S = 1024 x 1024 from K = m = 32896, 136 quarter tiles on a chip with
@@ -287,7 +288,9 @@ __global__ __launch_bounds__(256, 2) void k_syrk_splitk_128(GemmArgs g, CipBatch
     g.ldc = g.M;
     gemm_tile_128<true>(g, lds, bi, bj);
 }
-// C[i, j] = Qin[i, j] + sum_b image_b[i, j] for i >= j (by 64-tiles), i, j < nvalid; one thread per row pair of a 64 x 64 tile column
+// C[i, j] = Qin[i, j] + sum_b image_b[i, j] for i >= j (by 64-tiles), i, j < nvalid; one thread per row pair of a 64 x 64 tile column.
+// HAVEQ = false: no Qin (a CSR Q is added afterwards)
+template <bool HAVEQ>
 __global__ __launch_bounds__(256) void k_syrk_reduce(GemmArgs g, CipBatch cb) {
     bool live;
     (void)gemm_batch_prologue(g, cb, live);
@@ -303,8 +306,13 @@ __global__ __launch_bounds__(256) void k_syrk_reduce(GemmArgs g, CipBatch cb) {
         if (col >= g.nvalid || row >= g.nvalid) continue;
         v2d acc = (v2d){0.0, 0.0};
         for (int b = 0; b < g.ksplit_n; ++b) acc += *(const v2d *)(ws + b * img + row + col * g.M);
-        const double *qp = g.Qin + row + col * g.ldq;
         double *cp = g.C + row + col * g.ldc;
+        if (!HAVEQ) {
+            if (row + 1 < g.nvalid) *(v2d *)cp = g.alpha * acc;
+            else *cp = g.alpha * acc.x;
+            continue;
+        }
+        const double *qp = g.Qin + row + col * g.ldq;
         if (row + 1 < g.nvalid) *(v2d *)cp = (v2d){qp[0], qp[1]} + g.alpha * acc;
         else *cp = qp[0] + g.alpha * acc.x;
     }
@@ -403,11 +411,14 @@ int cip_syrk_schur(hipStream_t s, int M, int K, int nvalid, double alpha, const 
         if (syrk_split_128(M, K)) cip_launch_b(k_syrk_splitk_128, dim3((unsigned)tiles, (unsigned)split_n), dim3(256), 0, s, gs);
         else cip_launch_b(k_syrk_splitk_64, dim3((unsigned)(4 * tiles), (unsigned)split_n), dim3(256), 0, s, gs);
         const long t64 = (long)(M / SB) * (M / SB + 1) / 2;
-        cip_launch_b(k_syrk_reduce, dim3((unsigned)t64), dim3(256), 0, s, g);
+        if (Qin) cip_launch_b(k_syrk_reduce<true>, dim3((unsigned)t64), dim3(256), 0, s, g);
+        else cip_launch_b(k_syrk_reduce<false>, dim3((unsigned)t64), dim3(256), 0, s, g);
     } else if (syrkq_glds(W, ldw)) {
-        cip_launch_b(k_syrkq_64<true>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+        if (Qin) cip_launch_b(k_syrkq_64<true>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+        else cip_launch_b(k_syrkq_64<true, EPI_SYRK0>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
     } else {
-        cip_launch_b(k_syrkq_64<false>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+        if (Qin) cip_launch_b(k_syrkq_64<false>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
+        else cip_launch_b(k_syrkq_64<false, EPI_SYRK0>, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);
     }
     CIP_HIP_CHECK(hipGetLastError());
     return 0;

@@ -1,5 +1,5 @@
 // Lock-step batches: B independent problems of IDENTICAL shape (n, m, p, cone list, route, dense / CSR A with the same
-// number of non-zeros) advance through the interior-point loop of src/ConicIP.jl:468-939 together, every step of the
+// number of non-zeros, dense / CSR Q with the same number of non-zeros) advance through the interior-point loop of src/ConicIP.jl:468-939 together, every step of the
 // loop ONE launch whose grid carries the problem index in blockIdx.z (BASELINE config 5: 64 dense QPs of n = 2048;
 // SURVEY 7.4(5) "batch dimension").
 //
@@ -72,6 +72,12 @@ bool same_shape(const cip_problem &a, const cip_problem &b) {
         return q.A == nullptr && q.m > 0 && q.A_rowptr && ((q.flags & CIP_FLAG_CSR_HOST) || !(q.flags & CIP_FLAG_DEVICE_PTRS));
     };
     if (host_rowptr(a) && host_rowptr(b) && a.A_rowptr[a.m] != b.A_rowptr[b.m]) return false;
+    // Q: dense or CSR, and a CSR Q's number of non-zeros under the same rule
+    if ((a.flags & CIP_FLAG_Q_CSR) != (b.flags & CIP_FLAG_Q_CSR)) return false;
+    auto host_q_rowptr = [](const cip_problem &q) {
+        return (q.flags & CIP_FLAG_Q_CSR) && q.Q_rowptr && ((q.flags & CIP_FLAG_CSR_HOST) || !(q.flags & CIP_FLAG_DEVICE_PTRS));
+    };
+    if (host_q_rowptr(a) && host_q_rowptr(b) && a.Q_rowptr[a.n] != b.Q_rowptr[b.n]) return false;
     return true;
 }
 
@@ -122,7 +128,7 @@ void arena_release(char *ptr, size_t bytes) {
     g_cache.slots.push_back({ptr, bytes, dev});
 }
 std::vector<long> shape_signature(const cip_problem &pr, int solve_block) {
-    std::vector<long> sg = {pr.n, pr.m, pr.p, pr.ncones, pr.route, pr.A == nullptr, solve_block, cip_ldlt_outer_block()};
+    std::vector<long> sg = {pr.n, pr.m, pr.p, pr.ncones, pr.route, pr.A == nullptr, solve_block, cip_ldlt_outer_block(), (pr.flags & CIP_FLAG_Q_CSR) != 0};
     for (int c = 0; c < pr.ncones; ++c) { sg.push_back(pr.cone_type[c]); sg.push_back(pr.cone_dim[c]); }
     return sg;
 }
@@ -232,7 +238,11 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     const bool csr_host = csr && probs[0].A_rowptr && ((probs[0].flags & CIP_FLAG_CSR_HOST) || !(probs[0].flags & CIP_FLAG_DEVICE_PTRS));
     std::vector<long> sig = shape_signature(probs[0], cip_tl_solve_block_max);
     if (csr_host) sig.push_back((long)probs[0].A_rowptr[m]);
-    if (!csr || csr_host) {
+    // the same for a CSR Q (its slab share is O(nnz)): a count that cannot be read here means "always probe"
+    const bool qcsr = (probs[0].flags & CIP_FLAG_Q_CSR) != 0;
+    const bool qcsr_host = qcsr && probs[0].Q_rowptr && ((probs[0].flags & CIP_FLAG_CSR_HOST) || !(probs[0].flags & CIP_FLAG_DEVICE_PTRS));
+    if (qcsr_host) sig.push_back(-1L - (long)probs[0].Q_rowptr[n]);
+    if ((!csr || csr_host) && (!qcsr || qcsr_host)) {
         std::lock_guard<std::mutex> lk(g_cache.mu);
         if (g_cache.sig == sig) slab = g_cache.slab;
     }
@@ -266,6 +276,11 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
         hz->drv = (double *)drv;
         if (hz->arena_overflow || (z > 0 && hz->arena_used != G.h[0]->arena_used)) {
             cip_set_error("lock-step batch: problem %d does not fit problem 0's slab layout", z);
+            return CIP_E_UNSUPPORTED;
+        }
+        // the group's launches are problem 0's: a CSR Q whose longest row asks for the other mat-vec form (other bits) cannot follow
+        if (hz->Q_wave != G.h[0]->Q_wave) {
+            cip_set_error("lock-step batch: the CSR Q of problem %d takes another mat-vec form than problem 0's", z);
             return CIP_E_UNSUPPORTED;
         }
     }

@@ -187,6 +187,30 @@ int cip_spmv_csr(hipStream_t s, int rows, const int *rowptr, const int *colind, 
     return 0;
 }
 
+// One wave per row (four rows per workgroup): lane l takes the row's entries l, l + 64, .. in that order, the 64 partial sums
+// are added by cip_wave_sum's fixed tree -- the same bits on every run.  For long rows (a CSR Q that is nearly full: thread per
+// row reads each row serially from one lane); an empty row gives y = beta y, and y is not read when beta == 0.
+__global__ __launch_bounds__(256) void k_spmv_csr_wave(int rows, const int *rowptr, const int *colind, const double *val,
+                                                        double alpha, const double *x, double beta, double *y, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO5(cb, rowptr, colind, val, x, y);
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;                                      // (wave-uniform: the wave sum below sees whole waves only)
+    const int q1 = rowptr[r + 1];
+    double s = 0;
+    for (int q = rowptr[r] + lane; q < q1; q += 64) s += val[q] * x[colind[q]];
+    s = wsum(s);
+    if (lane == 0) y[r] = alpha * s + (beta == 0.0 ? 0.0 : beta * y[r]);
+}
+int cip_spmv_csr_wave(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val, double alpha,
+                      const double *x, double beta, double *y) {
+    if (rows <= 0) return 0;
+    cip_launch_b(k_spmv_csr_wave, dim3((rows + 3) / 4), dim3(256), 0, s, rows, rowptr, colind, val, alpha, x, beta, y);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // ---- multi-dot: stage 1 = (count x DOT_NB) partial sums, stage 2 = one block per dot
 #define DOT_NB 32
 struct DotPtrs { const double *x; const double *y; int len; int pad; };

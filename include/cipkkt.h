@@ -61,8 +61,9 @@ typedef struct cip_handle cip_handle;
 
 /* flags for cip_create_ex */
 #define CIP_FLAG_DEVICE_PTRS 1   /* Q/A/G arrays are device pointers */
-#define CIP_FLAG_CSR_HOST    2   /* ... except the CSR arrays of A, which are host pointers (the library needs them on the
-                                    host anyway, to build the CSR of A') */
+#define CIP_FLAG_CSR_HOST    2   /* ... except the CSR arrays of A (and of Q), which are host pointers (the library needs them on
+                                    the host anyway, to build the CSR of A' and to check Q) */
+#define CIP_FLAG_Q_CSR       4   /* Q is given in CSR (Q_rowptr / Q_colind / Q_val); Q itself must be NULL */
 
 #define CIP_OK            0
 #define CIP_E_INVALID    -1
@@ -76,7 +77,15 @@ typedef struct cip_handle cip_handle;
 /* Problem description for cip_create_ex.  A may be given dense (A != NULL) or
  * in CSR (A == NULL, A_rowptr/A_colind/A_val != NULL, 0-based) -- with any mix of cone types (the rows of S cones are expanded
  * into a dense block on the device; R / Q rows stay CSR).  S cones: matrix order r <= 2048 and at most 1024 cones of order >= 133
- * (CIP_E_UNSUPPORTED beyond either; the reference has no limit, src/ConicIP.jl:196-210). */
+ * (CIP_E_UNSUPPORTED beyond either; the reference has no limit, src/ConicIP.jl:196-210).
+ * Q may be given dense (Q != NULL) or, with CIP_FLAG_Q_CSR, in CSR (Q == NULL; the three Q_* arrays, 0-based, are read only when
+ * the flag is set, so a caller compiled against the struct without them is never read past its end).  The CSR Q is the WHOLE
+ * symmetric matrix -- both triangles stored, as a SparseMatrixCSC or a scipy matrix holds it; a symmetric CSC is its own CSR --
+ * with the columns of a row in any order, no duplicate entries, nnz == 0 for the zero objective.  Level 1 checks it on the host
+ * in O(nnz) (device-resident arrays are copied back first, as A's are): rowptr[0] == 0, a monotone row pointer, indices in range,
+ * no duplicates, every (i, j) with a stored (j, i) of bit-equal value; a violation is CIP_E_INVALID naming the first offending
+ * entry, before any device allocation.  Such a handle holds O(nnz) device memory for Q and every entry point keeps its meaning;
+ * the flag together with Q != NULL is CIP_E_INVALID, Q == NULL without it stays CIP_E_INVALID "Q is NULL". */
 typedef struct cip_problem {
     int n, m, p;
     int ncones;
@@ -88,6 +97,7 @@ typedef struct cip_problem {
     const double *G;  int ldg; /* p x n (may be NULL when p == 0) */
     int route;                 /* CIP_ROUTE_* */
     int flags;                 /* CIP_FLAG_* */
+    const int *Q_rowptr; const int *Q_colind; const double *Q_val; /* CSR of Q, n+1 / nnz / nnz (CIP_FLAG_Q_CSR only) */
 } cip_problem;
 
 /* ---- level 1: kktsolver(Q, A, G, cone_dims)  (src/ConicIP.jl:667; src/kktsolvers.jl:18-28, :180-190, :281-285) */
@@ -95,7 +105,8 @@ int cip_create(int n, int m, int p, int ncones, const int *cone_type, const int 
                const double *Q, const double *A, const double *G, int route, cip_handle **out);
 int cip_create_ex(const cip_problem *prob, cip_handle **out);
 /* level 1 again on an existing handle: new Q / A / G of the same shape (n, m, p, cones, route, dense-or-CSR A with the
- * same nnz); keeps every device allocation (hipMalloc / hipFree synchronise the whole device) */
+ * same nnz, dense-or-CSR Q with the same nnz -- else CIP_E_INVALID, the handle stays as it was); keeps every device allocation
+ * (hipMalloc / hipFree synchronise the whole device) */
 int cip_update_problem(cip_handle *h, const cip_problem *prob);
 int cip_destroy(cip_handle *h);
 const char *cip_last_error(void);
@@ -228,7 +239,7 @@ int cip_batch_conicip(cip_batch *b, const double *const *c, const double *const 
 int cip_conicip_problems(int count, const cip_problem *probs, const double *const *c, const double *const *bvec,
                          const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                          double *const *v, cip_result *res, int in_flight);
-/* the same, in LOCK-STEP: the problems must have identical shape (n, m, p, cone list, route, dense-or-CSR A) and no S
+/* the same, in LOCK-STEP: the problems must have identical shape (n, m, p, cone list, route, dense-or-CSR A, dense-or-CSR Q with the same nnz) and no S
  * cone of matrix order >= 133; they advance through the loop together, every step ONE launch with the problem index in the grid (groups of up
  * to 64).  Results are bit-identical to cip_conicip on each problem run with the same solve block (lock-step handles use
  * min(cip_set_solve_block_max, cip_lockstep_solve_block_for(B)): a standalone handle of order >= 1024 sums its triangular solves in wider blocks unless

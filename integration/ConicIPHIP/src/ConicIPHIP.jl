@@ -98,15 +98,17 @@ function _pack_scaling(F::Block, F⁻ᵀ::Block, cone_dims)
 end
 
 """
-    kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_SCHUR)
+    kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_SCHUR, sparse_q = false)
 
 Drop-in `kktsolver` for `conicIP` running the Newton step on an AMD MI355X.  A `SparseMatrixCSC` A goes to the
 device as CSR whatever the cones (O(nnz) Schur assembly for "R" / "Q" rows: the README box-QP, A = I; the rows of "S"
-cones are expanded into a dense block on the device); a dense A is uploaded dense.
+cones are expanded into a dense block on the device); a dense A is uploaded dense.  `sparse_q = true` hands a
+`SparseMatrixCSC` Q (anything else is converted with `sparse`) over as CSR too (CIP_FLAG_Q_CSR: O(nnz) on the device
+instead of a dense n x n image); the default densifies Q as before.
 """
-function kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_SCHUR)
+function kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_SCHUR, sparse_q = false)
     n, m, p = size(Q, 1), size(A, 1), size(G, 1)
-    h = _cip_create(Q, A, G, cone_dims, route)                                # level 1
+    h = _cip_create(Q, A, G, cone_dims, route; sparse_q = sparse_q)           # level 1
 
     function solve3x3gen(F, F⁻ᵀ)                                              # level 2
         packed = _pack_scaling(F, F⁻ᵀ, cone_dims)
@@ -157,9 +159,9 @@ _as_csr_source(A::Diagonal) = sparse(A)
 _as_csr_source(A::LinearAlgebra.Adjoint{<:Any, <:SparseMatrixCSC}) = sparse(A)
 _as_csr_source(A::LinearAlgebra.Transpose{<:Any, <:SparseMatrixCSC}) = sparse(A)
 _as_csr_source(A) = nothing
-function _cip_create(Q, A, G, cone_dims, route)
+function _cip_create(Q, A, G, cone_dims, route; sparse_q = false)
     As = _as_csr_source(A)
-    As === nothing ? _cip_create_dense(Q, A, G, cone_dims, route) : _cip_create_sparse(Q, As, G, cone_dims, route)
+    (As === nothing && !sparse_q) ? _cip_create_dense(Q, A, G, cone_dims, route) : _cip_create_sparse(Q, A, G, cone_dims, route, sparse_q)
 end
 
 function _cip_create_dense(Q, A, G, cone_dims, route)
@@ -187,10 +189,14 @@ struct CipProblem                      # mirrors `cip_problem` of include/cipkkt
     G::Ptr{Float64}; ldg::Cint
     route::Cint
     flags::Cint
+    Q_rowptr::Ptr{Cint}; Q_colind::Ptr{Cint}; Q_val::Ptr{Float64}     # CSR of Q, read only with CIP_FLAG_Q_CSR
 end
+const CIP_FLAG_Q_CSR = Cint(4)
 
 # Everything a `cip_problem` points at, staged as Julia arrays that must stay alive (GC.@preserve) across the call that
-# reads the struct.  A: CSR when sparse-structured (see _as_csr_source), else dense column-major.
+# reads the struct.  A: CSR when sparse-structured (see _as_csr_source), else dense column-major.  Q: dense column-major, or
+# with sparse_q the arrays of its SparseMatrixCSC -- Q is symmetric, so its CSC is its own CSR (the library checks that, entry
+# by entry); the shift to 0-based indices is the one A's arrays get.
 struct _Staged
     n::Int; m::Int; p::Int
     ctype::Vector{Cint}; cdim::Vector{Cint}
@@ -198,33 +204,44 @@ struct _Staged
     rowptr::Vector{Cint}; colind::Vector{Cint}; val::Vector{Float64}
     sparseA::Bool
     route::Cint
+    qrowptr::Vector{Cint}; qcolind::Vector{Cint}; qval::Vector{Float64}
+    sparseQ::Bool
 end
-function _stage(Q, A, G, cone_dims, route)
+function _stage(Q, A, G, cone_dims, route; sparse_q = false)
     n, m, p = size(Q, 1), size(A, 1), size(G, 1)
     ctype = Cint[_CONE_CODE[c[1]] for c in cone_dims]
     cdim  = Cint[c[2] for c in cone_dims]
+    Qs = sparse_q ? dropzeros(sparse(Q)) : nothing
+    Qd = sparse_q ? zeros(0, 0) : Matrix{Float64}(Q)
+    qrp = sparse_q ? Cint.(Qs.colptr .- 1) : Cint[]
+    qci = sparse_q ? Cint.(Qs.rowval .- 1) : Cint[]
+    qv  = sparse_q ? Vector{Float64}(Qs.nzval) : Float64[]
     As = _as_csr_source(A)
     if As === nothing
-        return _Staged(n, m, p, ctype, cdim, Matrix{Float64}(Q), Matrix{Float64}(A), Matrix{Float64}(G),
-                       Cint[], Cint[], Float64[], false, route)
+        return _Staged(n, m, p, ctype, cdim, Qd, Matrix{Float64}(A), Matrix{Float64}(G),
+                       Cint[], Cint[], Float64[], false, route, qrp, qci, qv, sparse_q)
     end
     At = sparse(As')                                       # CSC of A' == CSR of A
-    _Staged(n, m, p, ctype, cdim, Matrix{Float64}(Q), zeros(0, 0), Matrix{Float64}(G),
-            Cint.(At.colptr .- 1), Cint.(At.rowval .- 1), Vector{Float64}(At.nzval), true, route)
+    _Staged(n, m, p, ctype, cdim, Qd, zeros(0, 0), Matrix{Float64}(G),
+            Cint.(At.colptr .- 1), Cint.(At.rowval .- 1), Vector{Float64}(At.nzval), true, route, qrp, qci, qv, sparse_q)
 end
 # the struct itself: only valid while `st` is preserved
 function _problem(st::_Staged)
     null = Ptr{Float64}(C_NULL)
+    inull = Ptr{Cint}(C_NULL)
     CipProblem(st.n, st.m, st.p, length(st.ctype), pointer(st.ctype), pointer(st.cdim),
-               pointer(st.Qd), max(st.n, 1),
+               st.sparseQ ? null : pointer(st.Qd), max(st.n, 1),
                (st.sparseA || st.m == 0) ? null : pointer(st.Ad), max(st.m, 1),
                st.sparseA ? pointer(st.rowptr) : Ptr{Cint}(C_NULL), st.sparseA ? pointer(st.colind) : Ptr{Cint}(C_NULL),
                st.sparseA ? pointer(st.val) : null,
-               st.p > 0 ? pointer(st.Gd) : null, max(st.p, 1), st.route, 0)
+               st.p > 0 ? pointer(st.Gd) : null, max(st.p, 1), st.route, st.sparseQ ? CIP_FLAG_Q_CSR : Cint(0),
+               st.sparseQ ? pointer(st.qrowptr) : inull, (st.sparseQ && !isempty(st.qcolind)) ? pointer(st.qcolind) : inull,
+               (st.sparseQ && !isempty(st.qval)) ? pointer(st.qval) : null)
 end
 
-function _cip_create_sparse(Q, A::SparseMatrixCSC, G, cone_dims, route)
-    st = _stage(Q, A, G, cone_dims, route)
+# (the cip_create_ex path: a sparse-structured A, a CSR Q, or both)
+function _cip_create_sparse(Q, A, G, cone_dims, route, sparse_q = false)
+    st = _stage(Q, A, G, cone_dims, route; sparse_q = sparse_q)
     href = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve st begin
         prob = Ref(_problem(st))
@@ -237,9 +254,9 @@ end
 # `kktsolver_2x2_hip` has the shape of ConicIP.kktsolver_2x2 and is meant to be wrapped by the reference's own
 # `pivot`:   conicIP(...; kktsolver = pivot(kktsolver_2x2_hip))
 # (cip_solve2x2 solves [Q + Aᵀ(FᵀF)⁻¹A  Gᵀ; G 0][Δy; Δw] = [y; w] on the factor of the Schur route).
-function kktsolver_2x2_hip(Q, A, G, cone_dims)
+function kktsolver_2x2_hip(Q, A, G, cone_dims; sparse_q = false)
     n, p = size(Q, 1), size(G, 1)
-    h = _cip_create(Q, A, G, cone_dims, CIP_ROUTE_SCHUR)
+    h = _cip_create(Q, A, G, cone_dims, CIP_ROUTE_SCHUR; sparse_q = sparse_q)
     function solve2x2gen(F, F⁻ᵀ)
         packed = _pack_scaling(F, F⁻ᵀ, cone_dims)
         _cipcheck(ccall(_sym(:cip_set_scaling_packed), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, packed))
@@ -261,7 +278,7 @@ end
 #     conicIP(...; kktsolver = (Q, A, G, cd) -> kktsolver_hip(Q, A, G, cd; route = CIP_ROUTE_FULL3X3))
 
 "`kktsolver` for the literal 3×3 assembly of `kktsolver_sparse` (src/kktsolvers.jl:254-256) on the device."
-kktsolver_hip_full3x3(Q, A, G, cone_dims) = kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_FULL3X3)
+kktsolver_hip_full3x3(Q, A, G, cone_dims; sparse_q = false) = kktsolver_hip(Q, A, G, cone_dims; route = CIP_ROUTE_FULL3X3, sparse_q = sparse_q)
 
 # --- the whole interior-point loop on the device (SURVEY 8 f1 from the reference side) --------------------------
 # `cip_conicip` is src/ConicIP.jl:468-939 inside the library: every vector stays in HBM, the host sees scalars.  From
@@ -305,15 +322,15 @@ names and defaults are `conicIP`'s (src/ConicIP.jl:468-509): `optTol = 1e-6`, `D
 `maxRefinementSteps = 3`, `maxIters = 100`, `infeasTol = optTol`, `refinementThreshold = optTol/1e7`; `cache_nestodd` is
 accepted and ignored as in the reference; `kktsolver` is accepted and ignored (the device loop brings its own: the Schur
 route by default, `route = CIP_ROUTE_FULL3X3` for the literal 3x3 assembly).  `stats = Ref{CipResult}()` receives the
-raw result (factorisations, solves, wall-clock of the loop).
+raw result (factorisations, solves, wall-clock of the loop).  `sparse_q = true` hands Q over as CSR (see `kktsolver_hip`).
 """
 function conicIP_hip(Q, c::AbstractVector, A, b::AbstractVector, cone_dims,
                      G = spzeros(0, length(c)), d = zeros(0);
                      kktsolver = nothing, optTol = 1e-6, DTB = 0.01, verbose = true, maxRefinementSteps = 3,
                      maxIters = 100, cache_nestodd = false, infeasTol = optTol, refinementThreshold = optTol / 1e7,
-                     route = CIP_ROUTE_SCHUR, stats = nothing)
+                     route = CIP_ROUTE_SCHUR, stats = nothing, sparse_q = false)
     n, m, p = _check_dims(Q, c, A, b, G, d)
-    h = _cip_create(Q, A, G, cone_dims, route)
+    h = _cip_create(Q, A, G, cone_dims, route; sparse_q = sparse_q)
     opt = Ref(CipOptions(optTol, DTB, infeasTol, refinementThreshold, maxRefinementSteps, maxIters, verbose ? 1 : 0))
     res = Ref(CipResult())
     y, w, v = zeros(n), zeros(p), zeros(m)                  # fresh, Julia-owned: they become the Solution's fields
@@ -332,13 +349,14 @@ end
 
 Independent problems in, solutions out, on one GPU (`cip_conicip_mixed`): the problems that share a shape advance through
 the loop in lock-step (one launch per step for all of them), the others through `in_flight` host threads inside the
-library.  `problems[i]` is a tuple `(Q, c, A, b, cone_dims)` or `(Q, c, A, b, cone_dims, G, d)`; the keywords are
+library (`sparse_q = true`: every Q as CSR; the form is part of the shape).  `problems[i]` is a tuple `(Q, c, A, b, cone_dims)` or `(Q, c, A, b, cone_dims, G, d)`; the keywords are
 `conicIP`'s and apply to every problem.  (The reference solves one problem per `conicIP` call, src/ConicIP.jl:472-480: this
 is N independent calls.  Sharding over several GPUs is one process per GPU, problem i on rank i mod N.)
 """
 function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, route = CIP_ROUTE_SCHUR,
                            optTol = 1e-6, DTB = 0.01, verbose = false, maxRefinementSteps = 3, maxIters = 100,
-                           cache_nestodd = false, infeasTol = optTol, refinementThreshold = optTol / 1e7, stats = nothing)
+                           cache_nestodd = false, infeasTol = optTol, refinementThreshold = optTol / 1e7, stats = nothing,
+                           sparse_q = false)
     k = length(problems)
     k == 0 && return ConicIP.Solution[]
     staged = Vector{_Staged}(undef, k)
@@ -349,7 +367,7 @@ function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, rou
         G = length(pr) >= 7 ? pr[6] : spzeros(0, length(c))
         d = length(pr) >= 7 ? pr[7] : zeros(0)
         n, m, p = _check_dims(Q, c, A, b, G, d)
-        staged[i] = _stage(Q, A, G, K, route)
+        staged[i] = _stage(Q, A, G, K, route; sparse_q = sparse_q)
         cs[i], bs[i], ds[i] = Vector{Float64}(c), Vector{Float64}(b), Vector{Float64}(d)
         ys[i], ws[i], vs[i] = zeros(n), zeros(p), zeros(m)
     end
