@@ -200,12 +200,20 @@ __device__ __forceinline__ void diag_step_a(double *a, double *xm, int kb, int l
     const int l15 = lane & 15, g = lane >> 4;
     const int c = kb * 16;
     const int row = diag_perm(l15);                            // the tile row / X column this lane holds
-    v4d U, X, L = (v4d){0.0, 0.0, 0.0, 0.0};
-    double dd[4] = {0.0, 0.0, 0.0, 0.0};                       // lane group jb: the reciprocals rho_j of the four pivots of its block
+    // (round 7) L and dd carry no initial value: lane group jb writes all four of each in round jb and no lane reads them before
+    // (the zeros cost eight register moves per micro-panel on the serial wave)
+    v4d U, X, L;
+    double dd[4];                                              // lane group jb: the reciprocals rho_j of the four pivots of its block
+#pragma unroll
+    for (int q = 0; q < 4; ++q) asm volatile("" : "=v"(L[q]), "=v"(dd[q]));      // ("defined" without an instruction: left undefined, the compiler zero-fills them for the lanes outside each block)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         U[q] = PRELOADED ? U0[q] : a[(c + row) + (c + 4 * g + q) * DP];
         X[q] = (4 * g + q == row) ? 1.0 : 0.0;
+        // (round 7) the identity is the same in every micro-panel, so the optimiser kept it in registers across the loop and copied it
+        // three times on the way into the first block (once for the lanes outside it, once for the block's in-place fmacs, once to
+        // join the two): opaque here, it is materialised once per micro-panel in the registers the block works in
+        asm volatile("" : "+v"(X[q]));
     }
     double *scr = xm + kb * 256;                               // [set][kk][l15], three sets: this slot is written at the very end
     // operand lanes of the rank-4 updates: lane (l15, kk) carries the vector of pivot kk; P-side lanes whose hardware
@@ -215,26 +223,27 @@ __device__ __forceinline__ void diag_step_a(double *a, double *xm, int kb, int l
     stepa_round<1>(U, X, L, dd, scr, l15, g);
     stepa_round<2>(U, X, L, dd, scr, l15, g);
     stepa_round<3>(U, X, L, dd, scr, l15, g);
-    double rsel = 0.0;                                         // the reciprocal the lane's diagonal pivot was used with
+    // lane (l15, g = l15 & 3) holds the diagonal element of column `row` (= 4g + (l15 >> 2)) in register l15 >> 2
+    const bool diag_lane = g == (l15 & 3);
+    // the reciprocal the lane's diagonal pivot was used with.  (Round 7) only the 16 diagonal lanes use it -- for the stored pivot, its
+    // reciprocal and the checks below -- so the pick is by the register index alone and starts from dd[0] instead of a zero:
+    // three selects instead of four, and the other lanes' value is never stored
+    double rsel = dd[0];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int col = 4 * g + q;
-        if (col == row) rsel = dd[q];
-    }
+    for (int q = 1; q < 4; ++q)
+        if ((l15 >> 2) == q) rsel = dd[q];
     const double dsel = fast_rcp(rsel);                        // the stored pivot d := 1 / rho (correctly rounded in all but 1 of 4000 cases)
+    // l_ij below the diagonal (above: not stored) from one base address with constant offsets; the diagonal lanes' slot receives d
+    // BEHIND it, with d and 1/d below (the DS operations of a wave complete in order): no select between d and l per register
+    double *at = a + c * (DP + 1) + 4 * g * DP + row;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int col = 4 * g + q;
-        const double v = (col == row) ? dsel : L[q];           // d on the diagonal, l_ij below (above: not stored)
-        if (col <= row) a[(c + row) + (c + col) * DP] = v;
-    }
+    for (int q = 0; q < 4; ++q)
+        if (4 * g + q <= row) at[q * DP] = L[q];
 #pragma unroll
     for (int q = 0; q < 4; ++q) xm[kb * 256 + row * 16 + 4 * g + q] = X[q];      // xm[k = cc][jj = r] = X[r][cc]
     {
-        // lane (l15, g = l15 & 3) holds the diagonal element of column `row` (= 4g + (l15 >> 2)); these 16 lanes are in
-        // column order, so the lowest set bit of a ballot is the FIRST bad column of the micro-block (one atomic per flag
-        // instead of one per bad lane racing for the word)
-        const bool diag_lane = g == (l15 & 3);
+        // the 16 diagonal lanes are in column order, so the lowest set bit of a ballot is the FIRST bad column of the
+        // micro-block (one atomic per flag instead of one per bad lane racing for the word)
         // a bad pivot: zero, non-finite, or -- the matrix is quasi-definite in this static order -- of the wrong sign
         const int col = col0 + c + row;
         const bool want_pos = (col >= sg.p0 && col < sg.p1) || col >= sg.N;
@@ -246,6 +255,7 @@ __device__ __forceinline__ void diag_step_a(double *a, double *xm, int kb, int l
         if (mbad && lane == __ffsll((long long)mbad) - 1) atomicCAS(info, 0, col + 1);
         if (mdead && lane == __ffsll((long long)mdead) - 1) atomicCAS(info + 2, 0, col + 1);
         if (diag_lane) {
+            a[(c + row) * (DP + 1)] = dsel;
             a[128 + (c + row) * DP] = dsel;
             a[129 + (c + row) * DP] = rsel;
         }
@@ -443,7 +453,7 @@ __device__ __forceinline__ void diag_body(double *sm, double *Kb, long ld, doubl
                                           unsigned ready_target) {
     double *a = sm;
     double *xm = sm + XM_OFF;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (a scalar: the roles below branch on it)
     const int l15 = lane & 15, g = lane >> 4;
 
     // waves 4, 8, .. would share wave 0's SIMD (waves are dealt round-robin to the four SIMDs) and slow the serial wave by
@@ -558,7 +568,11 @@ __device__ __forceinline__ void diag_body(double *sm, double *Kb, long ld, doubl
         for (int kb = 0; kb < 7; ++kb) {
             const int c = kb * 16;
             double xa[4], di4[4], d4[4];
-            BcOperands bo;
+            // (round 7) ONE branch per step, on the wave index as a scalar: the serial wave's step and a helper's are two straight pieces
+            // of code.  As four `wave == 0` regions in a row (the loads, B + C, A, the helpers' tiles) every one of them cost the serial
+            // wave an EXEC save and restore, the tile handed from C to A was a value of BOTH sides of a branch (eleven register moves for
+            // the helpers' zeros, executed by the serial wave too, and four more to carry the C11 operand to the accumulator), and the
+            // loads of the two sides shared registers, so each was preceded by a wait.  Per wave the same operations in the same order.
             if (wave == 0) {
                 // the serial wave: the poll for the helpers' tiles of step kb - 1 and EVERY operand of its B + C in ONE LDS round trip
                 // (the DS operations of a wave return in order; its own A(kb) stores are in front of them).  The tiles are normally
@@ -574,35 +588,14 @@ __device__ __forceinline__ void diag_body(double *sm, double *Kb, long ld, doubl
                     di4[s] = a[129 + (c + g + 4 * s) * DP];
                     d4[s] = a[128 + (c + g + 4 * s) * DP];
                 }
-                bo = diag_step_bc_load(a, kb, l15, g);
+                BcOperands bo = diag_step_bc_load(a, kb, l15, g);
                 if (tf < (unsigned)(kb * NH)) {
                     wait_for(tflag, (unsigned)(kb * NH));
                     bo = diag_step_bc_load(a, kb, l15, g);
                 } else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            } else {
-                wait_for(aflag, (unsigned)kb);                             // A(kb): counted by the serial wave (A(0): the barrier above)
-                wait_for(tflag, (unsigned)(kb * NH));                      // the helpers' tiles of step kb - 1
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    xa[s] = xm[kb * 256 + (g + 4 * s) * 16 + l15];       // Aop[jj = l15][k = g + 4s]
-                    di4[s] = a[129 + (c + g + 4 * s) * DP];
-                    d4[s] = a[128 + (c + g + 4 * s) * DP];
-                }
-            }
-            // (kb+1, kb+1): steps 0 .. kb-1 were applied by a helper during step kb-1, step kb is this wave's
-            v4d U1 = (v4d){0.0, 0.0, 0.0, 0.0};
-            if (wave == 0) U1 = diag_step_bc_perm(a, kb, l15, g, bo, xa, di4, d4);
-            else { for (int it = kb + 2 + hid; it < 8; it += NH) diag_step_b(a, it, c, l15, g, xa, di4); }
-            count(bflag);
-            if (PUB && wave != 0 && kb > 0) {
-                // the stage count of micro-panel kb - 1, whose write-through stores this wave issued at the end of the last step:
-                // they have had the serial wave's A(kb) and this B to land (waiting for them right behind the stores put a store
-                // round trip -- 1.5-2 us inside a busy launch -- on every helper's step, and the serial wave then waited for the
-                // helpers' tiles)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0) atomicAdd(stage, 1u);
-            }
-            if (wave == 0) {
+                // (kb+1, kb+1): steps 0 .. kb-1 were applied by a helper during step kb-1, step kb is this wave's
+                const v4d U1 = diag_step_bc_perm(a, kb, l15, g, bo, xa, di4, d4);
+                count(bflag);
                 diag_step_a<true>(a, xm, kb + 1, lane, info, col0, sg, U1);
                 count(aflag);
                 if (PUB && kb == 6) {
@@ -624,6 +617,24 @@ __device__ __forceinline__ void diag_body(double *sm, double *Kb, long ld, doubl
                     if (lane == 0) atomicAdd(stage, PANEL_STAGE_LAST);
                 }
             } else {
+                wait_for(aflag, (unsigned)kb);                             // A(kb): counted by the serial wave (A(0): the barrier above)
+                wait_for(tflag, (unsigned)(kb * NH));                      // the helpers' tiles of step kb - 1
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    xa[s] = xm[kb * 256 + (g + 4 * s) * 16 + l15];       // Aop[jj = l15][k = g + 4s]
+                    di4[s] = a[129 + (c + g + 4 * s) * DP];
+                    d4[s] = a[128 + (c + g + 4 * s) * DP];
+                }
+                for (int it = kb + 2 + hid; it < 8; it += NH) diag_step_b(a, it, c, l15, g, xa, di4);
+                count(bflag);
+                if (PUB && kb > 0) {
+                    // the stage count of micro-panel kb - 1, whose write-through stores this wave issued at the end of the last step:
+                    // they have had the serial wave's A(kb) and this B to land (waiting for them right behind the stores put a store
+                    // round trip -- 1.5-2 us inside a busy launch -- on every helper's step, and the serial wave then waited for the
+                    // helpers' tiles)
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if (lane == 0) atomicAdd(stage, 1u);
+                }
                 wait_for(bflag, (unsigned)((kb + 1) * (NH + 1)));         // everybody's B(kb): the tiles below read them
                 // left-looking: the tiles that are needed NEXT -- column kb+1 below its diagonal tile (the panel of step kb+1) and
                 // the diagonal tile (kb+2, kb+2) (wave 0's C11 of step kb+1) -- receive all their steps 0 .. kb now
