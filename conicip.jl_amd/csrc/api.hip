@@ -669,12 +669,6 @@ extern "C" int cip_assemble_only(cip_handle *h) {
     return cip_assemble(h);
 }
 
-// Relative size of the automatic regularisation.  Miles problem 3 under the reference's 10 scalings (test/runtests.jl:
-// 618-637), iterations to :Optimal (oracle: 15 16 16 15 21 29 30 | 20 29 32): 1e-9 -> one false :Unbounded; 1e-11 -> 11 16 16
-// 15 21 26 24 | 20 28 27; 1e-13 -> 16 16 16 15 21 29 29 | 21 29 32.  The refinement inside solve3x3 is what makes the
-// small value work.  CIP_AUTO_REG overrides.
-#define CIP_AUTO_REG 1e-13
-
 // ---- hipGraph replay of the LDL' factorisation / the triangular solves of SMALL systems (opt-in: CIP_GRAPH=1).  The
 // launch sequence of a handle never changes (same pointers, same sizes), so it is recorded once as an explicit graph
 // (cip_launch, cip_internal.h) and replayed: ~60 launches per factorisation and ~10-33 per solve become one graph launch.
@@ -1016,12 +1010,23 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
     if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
     if (h->info_pending) h->spec_solves += 1;
     h->n_solve += 1;
-    if (h->reg_rel <= 0.0) return solve3x3_once(h, x, y, z, a, b, c);
+    // which problems of the call sit on a regularised factor: the handle's own state for one problem, the group's mask in a batch
+    const bool batch = cip_in_batch();
+    const unsigned long long mask0 = cip_tl_bz.mask;
+    unsigned long long live = batch ? (mask0 & cip_tl_bz.reg_mask) : (h->reg_rel > 0.0 ? 1ull : 0ull);
+    if (!live) return solve3x3_once(h, x, y, z, a, b, c);
     // Regularised factor: iterative refinement against the true operator (the factor is of K + E, |E_ii| = reg_rel
     // times the row's largest entry): a few steps bring the residual to rounding level while ||K^-1 E|| < 1.
+    // In a batch the first solve runs for every problem of the mask, from the private copy of the right-hand side (copies are
+    // exact: the others get the bits of solve3x3_once on the original); the refinement then runs under the mask of the regularised
+    // problems, each leaving it when ITS residual has converged, stagnates or is not finite -- every problem sees the launches it
+    // sees alone.
     hipStream_t s = h->stream;
     const size_t tot = (size_t)n + p + m;
-    if (!h->ref) DMALLOC(h->ref, sizeof(double) * 3 * (tot + 8));
+    if (!h->ref) {
+        if (batch) { cip_set_error("cip_solve3x3: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
+        if ((rc = cip_alloc_refine_buffers(h))) return rc;
+    }
     double *xs = h->ref, *ys = xs + n, *zs = ys + p;              // private copy of the right-hand side (z may alias c)
     double *rx = h->ref + tot + 8, *ry = rx + n, *rz = ry + p;
     double *da = h->ref + 2 * (tot + 8), *db = da + n, *dc = db + p;
@@ -1029,21 +1034,35 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
     if (p > 0) { int rcc = cip_copy(s, p, y, ys); if (rcc) return rcc; }
     if (m > 0) { int rcc = cip_copy(s, m, z, zs); if (rcc) return rcc; }
     if ((rc = solve3x3_once(h, xs, ys, zs, a, b, c))) return rc;
-    double prev = __builtin_inf();
-    for (int it = 0; it < 6; ++it) {
+    struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
+    const int B = batch ? cip_tl_bz.B : 1;
+    double prev[CIP_BATCH_MAX], d6[6 * CIP_BATCH_MAX];
+    for (int q = 0; q < B; ++q) prev[q] = __builtin_inf();
+    for (int it = 0; it < 6 && live; ++it) {
+        if (batch) cip_tl_bz.mask = live;
         if ((rc = kkt3_residual(h, xs, ys, zs, a, b, c, rx, ry, rz))) return rc;
         const double *px[6] = {rx, ry, rz, xs, ys, zs};
         const int ln[6] = {n, p, m, n, p, m};
-        double d6[6];
-        if ((rc = cip_dots(s, 6, px, px, ln, h->dot_scratch, d6))) return rc;
-        const double rn = sqrt(d6[0] + d6[1] + d6[2]), bn = sqrt(d6[3] + d6[4] + d6[5]);
-        if (!(rn > 1e-14 * bn) || !(rn < prev)) break;           // converged, stagnating, or not finite
-        prev = rn;
+        if ((rc = cip_dots(s, 6, px, px, ln, h->dot_scratch, d6))) return rc;       // (a batch: B x 6, problem-major)
+        for (int q = 0; q < B; ++q) {
+            if (!((live >> q) & 1ull)) continue;
+            const double *dq = d6 + 6 * q;
+            const double rn = sqrt(dq[0] + dq[1] + dq[2]), bn = sqrt(dq[3] + dq[4] + dq[5]);
+            if (!(rn > 1e-14 * bn) || !(rn < prev[q])) live &= ~(1ull << q);         // converged, stagnating, or not finite
+            prev[q] = rn;
+        }
+        if (!live) break;
+        if (batch) cip_tl_bz.mask = live;
         if ((rc = solve3x3_once(h, rx, ry, rz, da, db, dc))) return rc;
         if ((rc = cip_axpby(s, n, 1.0, da, 1.0, a))) return rc;
         if (p > 0 && (rc = cip_axpby(s, p, 1.0, db, 1.0, b))) return rc;
         if (m > 0 && (rc = cip_axpby(s, m, 1.0, dc, 1.0, c))) return rc;
     }
+    return 0;
+}
+int cip_alloc_refine_buffers(cip_handle *h) {
+    if (!h->ref) DMALLOC(h->ref, sizeof(double) * 3 * ((size_t)h->n + h->p + h->m + 8));
+    if (!h->c2x2 && h->m > 0 && h->route == CIP_ROUTE_SCHUR) DMALLOC(h->c2x2, sizeof(double) * h->m);
     return 0;
 }
 
@@ -1075,11 +1094,23 @@ extern "C" int cip_solve2x2_dev(cip_handle *h, const double *y, const double *w,
     if (!h->factored) { cip_set_error("cip_solve2x2: no factorisation (call cip_factor first)"); return CIP_E_NOTFACTORED; }
     int rc;
     if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
-    if (h->reg_rel > 0.0 && h->m > 0) {
-        // regularised factor: go through the refined 3x3 solve with z = 0 (its first two components are the 2x2 solution)
+    const bool batch = cip_in_batch();
+    const unsigned long long mask0 = cip_tl_bz.mask;
+    const unsigned long long regd = batch ? (mask0 & cip_tl_bz.reg_mask) : (h->reg_rel > 0.0 ? 1ull : 0ull);
+    if (regd && h->m > 0) {
+        // regularised factor: go through the refined 3x3 solve with z = 0 (its first two components are the 2x2 solution); in a batch
+        // only the regularised problems of the mask do, the others take the 2x2 form below under theirs
+        struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
+        if (batch) cip_tl_bz.mask = regd;
         { int rcc = cip_zero(h->stream, h->m, h->mt1); if (rcc) return rcc; }
-        if (!h->c2x2) DMALLOC(h->c2x2, sizeof(double) * h->m);
-        return cip_solve3x3_dev(h, y, w, h->mt1, dy, dw, h->c2x2);
+        if (!h->c2x2) {
+            if (batch) { cip_set_error("cip_solve2x2: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
+            if ((rc = cip_alloc_refine_buffers(h))) return rc;
+        }
+        if ((rc = cip_solve3x3_dev(h, y, w, h->mt1, dy, dw, h->c2x2))) return rc;
+        if (!batch || regd == mask0) return 0;
+        cip_tl_bz.mask = mask0 & ~regd;
+        return solve3x3_once(h, y, w, nullptr, dy, dw, nullptr);
     }
     if (h->info_pending) h->spec_solves += 1;
     h->n_solve += 1;
@@ -1274,7 +1305,13 @@ extern "C" int cip_solve4x4_dev(cip_handle *h, const double *lambda, const doubl
     // element-wise generic path, which tolerates it
     const size_t len4 = (size_t)n + p + 2 * (size_t)m;
     const bool aliased = dz < r + len4 && r < dz + len4;
-    if (h->all_r && !aliased && h->route == CIP_ROUTE_SCHUR && h->reg_rel <= 0.0) {
+    // a lock-step group with regularised problems (lockstep.hip): they take the generic path below with its refined solve, as they do
+    // alone; the others of the mask take the fused path first, under their own mask
+    const unsigned long long mask0 = cip_tl_bz.mask;
+    const unsigned long long regd = cip_in_batch() ? (mask0 & cip_tl_bz.reg_mask) : 0ull;
+    struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
+    if (h->all_r && !aliased && h->route == CIP_ROUTE_SCHUR && h->reg_rel <= 0.0 && regd != mask0) {
+        cip_tl_bz.mask = mask0 & ~regd;
         // all cones R (F = diag(f), f = the packed scaling): the element-wise launches around the sweeps fused into one kernel
         // in front and one behind them (vecops.hip: k_s4_pre_r / k_s4_post_r), the same operations on every element
         if (!h->factored) { cip_set_error("cip_solve4x4: no factorisation (call cip_factor first)"); return CIP_E_NOTFACTORED; }
@@ -1289,7 +1326,9 @@ extern "C" int cip_solve4x4_dev(cip_handle *h, const double *lambda, const doubl
             if (!h->A_sparse && (rc = mul_At(h, 1.0, t, 1.0, h->rhs))) return rc;
             if ((rc = graph_run(h, &h->gx_solve, [&]() { return cip_ldlt_solve(s, h->K, h->Npad, h->ldk, h->ws, h->rhs); }))) return rc;
             if (!h->A_sparse && (rc = mul_A(h, 1.0, h->rhs, 0.0, u))) return rc;
-            return cip_s4_post_r(s, m, n, p, f, t, h->rhs, h->A_sparse ? nullptr : u, h->A_sparse ? h->A_rp : nullptr, h->A_ci, h->A_v, dy, dw, dv, ds);
+            if ((rc = cip_s4_post_r(s, m, n, p, f, t, h->rhs, h->A_sparse ? nullptr : u, h->A_sparse ? h->A_rp : nullptr, h->A_ci, h->A_v, dy, dw, dv, ds))) return rc;
+            if (!regd) return 0;
+            cip_tl_bz.mask = regd;
         }
     }
     // ds is used as t1; dv temporarily holds r.v + t1 (input z of the 3x3 solve; solve3x3 copies it before writing c)

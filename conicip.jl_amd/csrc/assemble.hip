@@ -448,31 +448,82 @@ static int assemble_full(cip_handle *h) {
 // row part j <= i and its column part below the diagonal), s_i = +1 on the positive-pivot block [p0, p1), -1 elsewhere.
 // Late interior-point iterates spread the diagonal of S over 20 orders of magnitude; one global delta either drowns
 // the small rows or does nothing for the large ones.
-__global__ __launch_bounds__(256) void k_rowmax_lower(const double *K, long ldk, int N, double *rowmax, CipBatch cb) {
+//
+// One pass over the lower triangle: a workgroup per 128 x 128 tile reads its tile once, 16 columns at a time with the threads
+// along the rows (coalesced), and reduces |K_ij| into the maxima of its 128 rows (in registers) and of its 128 columns (through
+// LDS: 16 lanes per column, then four shuffle steps).  The partial maxima of all tiles meet in mx[0 .. N) by atomicMax on the bit
+// pattern -- non-negative doubles order like unsigned integers, and a maximum does not depend on the order it is taken in, so
+// mx[i] has the bits of fmax over the whole row whatever the tiles' schedule.  fmax(0, |x|) drops a NaN entry, as fmax always did
+// here.  A diagonal tile takes j <= i for the row part and r > i for the column part (what lies above the diagonal is not K).
+// Before: one thread per row over the row parts (N / 256 workgroups), then one workgroup per column over the column parts -- two
+// reads of the triangle, the first on a fraction of the chip (DESIGN_LOG.md, "Problems that need the regularised LDL' stay in
+// their group", has both forms' timings).
+#define REG_TILE 128
+#define REG_COLS 16                       // columns per pass: 256 threads = 128 rows x 2 halves of 8 columns
+__global__ __launch_bounds__(256) void k_regmax_tiles(const double *K, long ldk, int N, double *mx_d, CipBatch cb) {
     CIP_BATCH_GUARD(cb);
-    CIP_BO2(cb, K, rowmax);
-    // thread <-> row i: the row part K[i, 0..i] (coalesced across the threads of a workgroup)
+    CIP_BO2(cb, K, mx_d);
+    unsigned long long *mx = (unsigned long long *)mx_d;
+    __shared__ double sh[2][REG_COLS][REG_TILE + 1];      // |K| of one pass, by column (two buffers: one barrier per pass)
+    __shared__ double shrow[REG_TILE];
+    // tile (ti, tj), tj <= ti, from the linear index ti (ti + 1) / 2 + tj
+    const int t = blockIdx.x;
+    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((long)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    while ((long)ti * (ti + 1) / 2 > t) --ti;
+    const int tj = t - (int)((long)ti * (ti + 1) / 2);
+    const int r = threadIdx.x & (REG_TILE - 1), hh = threadIdx.x >> 7;
+    const int cc = threadIdx.x >> 4, sg = threadIdx.x & 15;
+    const int gi = ti * REG_TILE + r;
+    double rmx = 0.0;
+    for (int q = 0; q < REG_TILE / REG_COLS; ++q) {
+        double (*buf)[REG_TILE + 1] = sh[q & 1];
+        double a[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int gj = tj * REG_TILE + q * REG_COLS + hh * 8 + k;
+            a[k] = (gi < N && gj <= gi) ? fmax(0.0, fabs(K[gi + (long)gj * ldk])) : 0.0;     // (gj <= gi < N)
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int gj = tj * REG_TILE + q * REG_COLS + hh * 8 + k;
+            rmx = fmax(rmx, a[k]);
+            buf[hh * 8 + k][r] = gj < gi ? a[k] : 0.0;          // the diagonal belongs to the row part only
+        }
+        __syncthreads();
+        double v = 0.0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v = fmax(v, buf[cc][sg + 16 * e]);
+        for (int o = 8; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+        const int gc = tj * REG_TILE + q * REG_COLS + cc;
+        if (sg == 0 && gc < N && v > 0.0) atomicMax(&mx[gc], (unsigned long long)__double_as_longlong(v));
+    }
+    if (hh == 1) shrow[r] = rmx;
+    __syncthreads();
+    if (hh == 0) {
+        rmx = fmax(rmx, shrow[r]);
+        if (gi < N && rmx > 0.0) atomicMax(&mx[gi], (unsigned long long)__double_as_longlong(rmx));
+    }
+}
+__global__ __launch_bounds__(256) void k_regularize_diag(double *K, long ldk, int N, int p0, int p1, double rel, const double *mx, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO2(cb, K, mx);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    double mx = 0.0;
-    for (int j = 0; j <= i; ++j) mx = fmax(mx, fabs(K[i + (long)j * ldk]));
-    rowmax[i] = mx;
+    const double delta = rel * mx[i];
+    K[i + (long)i * ldk] += (i >= p0 && i < p1) ? delta : -delta;
 }
-__global__ __launch_bounds__(256) void k_regularize_rows(double *K, long ldk, int N, int p0, int p1, double rel, const double *rowmax, CipBatch cb) {
-    CIP_BATCH_GUARD(cb);
-    CIP_BO2(cb, K, rowmax);
-    // workgroup <-> column i: the column part K[i+1.., i], then the diagonal update
-    __shared__ double red[4];
-    const int i = blockIdx.x;
-    double mx = 0.0;
-    for (int r = i + 1 + threadIdx.x; r < N; r += 256) mx = fmax(mx, fabs(K[r + (long)i * ldk]));
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double delta = rel * fmax(fmax(fmax(red[0], red[1]), fmax(red[2], red[3])), rowmax[i]);
-        K[i + (long)i * ldk] += (i >= p0 && i < p1) ? delta : -delta;
-    }
+// three launches (zero, tile pass, diagonal update) for every problem of the thread's mask; the maxima live in h->rhs (free between
+// an assembly and the next solve).  The diagonal is modified only after every maximum has been taken: its launch is behind the tiles'
+int cip_regularize(cip_handle *h, double rel) {
+    if (h->N <= 0) return 0;
+    const int T = (h->N + REG_TILE - 1) / REG_TILE;
+    { const int rc = cip_zero(h->stream, h->N, h->rhs); if (rc) return rc; }
+    cip_launch_b(k_regmax_tiles, dim3((unsigned)((long)T * (T + 1) / 2)), dim3(256), 0, h->stream, (const double *)h->K, h->ldk, h->N, h->rhs);
+    cip_launch_b(k_regularize_diag, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->K, h->ldk, h->N, h->ws.signs.p0, h->ws.signs.p1, rel,
+                 (const double *)h->rhs);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int cip_assemble(cip_handle *h, bool lazy_ok) {
@@ -480,14 +531,7 @@ int cip_assemble(cip_handle *h, bool lazy_ok) {
     // K is about to be overwritten: the side stream may still be reading the previous factor (a factorisation without solves)
     { const int rj = cip_ldlt_side_join(h->stream, h->ws, -1); if (rj) return rj; }
     int rc = (h->route == CIP_ROUTE_SCHUR) ? assemble_schur(h, lazy_ok) : assemble_full(h);
-    if (rc == 0 && h->reg_rel > 0.0) {
-        // (the diagonal is modified only after every row / column maximum has been read: the second kernel reads
-        //  column i strictly below the diagonal, the first one has finished before it starts)
-        cip_launch_b(k_rowmax_lower, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, h->K, h->ldk, h->N, h->rhs);
-        cip_launch_b(k_regularize_rows, dim3(h->N), dim3(256), 0, h->stream, h->K, h->ldk, h->N, h->ws.signs.p0,
-                           h->ws.signs.p1, h->reg_rel, h->rhs);
-        CIP_HIP_CHECK(hipGetLastError());
-    }
+    if (rc == 0 && h->reg_rel > 0.0) rc = cip_regularize(h, h->reg_rel);
     if (rc == 0) { h->assembled = true; h->factored = false; }
     return rc;
 }

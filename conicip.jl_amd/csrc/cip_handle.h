@@ -111,6 +111,18 @@ struct cip_handle {
 int cip_lazy_copy_set(int on);       // assemble.hip
 int cip_scatter_AtS(cip_handle *h);   // assemble.hip: CSR A with S cones: their rows of A' as a dense block (h->AtS)
 int cip_assemble(cip_handle *h, bool lazy_ok = false);     // assemble.hip; lazy_ok: the caller factors right away (see assemble_schur)
+// Relative size of the automatic regularisation.  Miles problem 3 under the reference's 10 scalings (test/runtests.jl:
+// 618-637), iterations to :Optimal (oracle: 15 16 16 15 21 29 30 | 20 29 32): 1e-9 -> one false :Unbounded; 1e-11 -> 11 16 16
+// 15 21 26 24 | 20 28 27; 1e-13 -> 16 16 16 15 21 29 29 | 21 29 32.  The refinement inside solve3x3 is what makes the
+// small value work.  CIP_AUTO_REG overrides (api.hip: factor_resolve; lockstep.hip: GroupLoop).
+#define CIP_AUTO_REG 1e-13
+
+// assemble.hip: the assembled K of every problem of the thread's mask becomes K + E, E_ii = +-rel * max_j |K_ij| (what cip_assemble does
+// behind the assembly while h->reg_rel > 0; a lock-step group calls it under the mask of its regularised problems)
+int cip_regularize(cip_handle *h, double rel);
+// api.hip: the buffers the refined solves of a regularised factor allocate on first use (h->ref, h->c2x2), now -- in a lock-step arena
+// every buffer of problem z must sit at problem 0's offset, so a group that may regularise creates them with its handles
+int cip_alloc_refine_buffers(cip_handle *h);
 int cip_mul_Q(cip_handle *h, double alpha, const double *x, double beta, double *y, bool symv = true);   // api.hip: y = alpha Q x + beta y, dense or CSR Q
 int cip_handle_alloc(cip_handle *h, void **out, size_t bytes);      // api.hip
 int cip_create_in_arena(const struct cip_problem *pr, char *slab, size_t cap, hipStream_t stream, cip_handle **out);   // api.hip

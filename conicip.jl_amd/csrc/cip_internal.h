@@ -66,6 +66,9 @@ struct CipBatch { long stride; unsigned long long mask; };            // stride 
 struct CipBatchCtx {
     int B; long stride; unsigned long long mask;
     double *gather_dev; double *gather_host;       // B x CIP_GATHER doubles (device / pinned host): per-problem scalar results
+    // bit z: problem z's factor is of the regularised matrix K + E -- its solves are refined against the true operator (api.hip:
+    // cip_solve3x3_dev).  Kept current by the group (lockstep.hip: GroupLoop); 0 outside a batch, where h->reg_rel says the same
+    unsigned long long reg_mask;
 };
 #define CIP_GATHER 64
 #define CIP_BATCH_MAX 64

@@ -18,7 +18,9 @@
 // Per-problem control flow is the mask: problems that have reached a final status stop taking part; the refinement loop
 // runs on the subset that still needs it.  What differs is the policy on pivot flags (GroupLoop below): a problem whose
 // factorisation meets a bad pivot (it would switch to the regularised factorisation: LPs, singular Q with free
-// variables) is taken out of the lock-step group and solved afterwards by cip_conicip on its own handle.
+// variables) is taken out of the lock-step group and solved afterwards by cip_conicip on its own handle -- or, with
+// cip_set_lockstep_regularize(1), switched to the regularised factorisation INSIDE its group: the group keeps a mask of
+// its regularised problems, regularises their K behind the assembly and refines their solves (api.hip: cip_solve3x3_dev).
 //
 // Not supported in lock-step (the caller falls back to the thread pool of batch.hip): S cones of order >= 133 (their
 // chip-wide kernels own one workspace), problems of differing shape.
@@ -35,7 +37,7 @@
 
 using namespace cipdrv;
 
-thread_local CipBatchCtx cip_tl_bz = {1, 0, 1ull, nullptr, nullptr};
+thread_local CipBatchCtx cip_tl_bz = {1, 0, 1ull, nullptr, nullptr, 0ull};
 
 namespace {
 
@@ -127,8 +129,9 @@ void arena_release(char *ptr, size_t bytes) {
     }
     g_cache.slots.push_back({ptr, bytes, dev});
 }
-std::vector<long> shape_signature(const cip_problem &pr, int solve_block) {
-    std::vector<long> sg = {pr.n, pr.m, pr.p, pr.ncones, pr.route, pr.A == nullptr, solve_block, cip_ldlt_outer_block(), (pr.flags & CIP_FLAG_Q_CSR) != 0};
+// (keep_reg: the handles carry the refinement buffers of the regularised factorisation -- another slab)
+std::vector<long> shape_signature(const cip_problem &pr, int solve_block, bool keep_reg) {
+    std::vector<long> sg = {pr.n, pr.m, pr.p, pr.ncones, pr.route, pr.A == nullptr, solve_block, cip_ldlt_outer_block(), (pr.flags & CIP_FLAG_Q_CSR) != 0, keep_reg};
     for (int c = 0; c < pr.ncones; ++c) { sg.push_back(pr.cone_type[c]); sg.push_back(pr.cone_dim[c]); }
     return sg;
 }
@@ -148,45 +151,111 @@ struct Group {
     }
 };
 
-thread_local int g_last_stats[3] = {0, 0, 0};      // groups, problems, problems that left their group (last call of this thread)
+// groups, problems, problems that left their group, problems regularised inside their group (last call of this thread)
+#define N_STATS 4
+thread_local int g_last_stats[N_STATS] = {0, 0, 0, 0};
+// cip_set_lockstep_regularize: 1 = a problem whose factorisation meets a bad pivot stays in its group (process-wide; a group reads it once)
+std::atomic<int> g_keep_regularized{0};
 
 // The group's policy on pivot flags: assembly + LDL' of every problem of the mask, the four flag words of each problem copied
-// into its row of the gather buffer (they ride on the next read-back, normally the dots'), and the problems that met a bad
-// pivot or whose fused panel chain gave up an in-launch wait taken out of the group (ejected: solved alone afterwards)
+// into its row of the gather buffer (they ride on the next read-back, normally the dots'), and the problems whose fused panel
+// chain gave up an in-launch wait taken out of the group (ejected: solved alone afterwards).  A problem that met a bad pivot is
+// ejected too (keep == false), or joins `reg` (keep): the group's problems on the regularised factorisation, for good -- what
+// factor_resolve (api.hip) does to one handle, per problem of the group.  `reg` lives with the group: the side-by-side groups of
+// a split call have their own.  A group of ONE problem is no batch for the kernels (no mask): there bit 0 of `reg` is the
+// handle's own reg_rel, which cip_assemble and the solves read as they do for a stand-alone handle.
 struct GroupLoop final : Loop {
     Group &G;
     std::vector<char> ejected;
-    explicit GroupLoop(Group &g) : Loop(g.h[0], g.B), G(g), ejected(g.B, 0) {}
-    int factor() override {
+    const bool keep;
+    const double rel;
+    unsigned long long reg = 0;
+    GroupLoop(Group &g, bool keep_) : Loop(g.h[0], g.B), G(g), ejected(g.B, 0), keep(keep_), rel(cip_env_double("CIP_AUTO_REG", CIP_AUTO_REG)) {}
+    // assembly, regularisation of the regularised ones, LDL': the problems of mk (the thread's mask on entry, and again on return)
+    int factor_under(unsigned long long mk) {
         int rc;
+        const unsigned long long rg = mk & reg;
         h->assembled = h->factored = false;
-        h->reg_rel = 0.0;
-        if ((rc = cip_assemble(h, true))) return rc;
+        if (!cip_in_batch()) {
+            h->reg_rel = rg ? rel : 0.0;
+            if ((rc = cip_assemble(h, true))) return rc;
+        } else {
+            // (a regularised matrix cannot take the lazy copy, and the copy is per launch: nobody takes it while one of them is in)
+            h->reg_rel = 0.0;
+            if ((rc = cip_assemble(h, rg == 0))) return rc;
+            if (rg) {
+                cip_tl_bz.mask = rg;
+                rc = cip_regularize(h, rel);
+                cip_tl_bz.mask = mk;
+                if (rc) return rc;
+            }
+        }
         if ((rc = cip_ldlt_factor(h->stream, h->K, h->Npad, h->ldk, h->ws))) return rc;
         h->factored = true; h->info_pending = false;
         return 0;
     }
+    int factor() override { return factor_under(cip_tl_bz.mask); }
     int ride_pivots() override {       // (under the mask the factorisation ran under)
         cip_launch_b(k_gather_info, dim3(1), dim3(64), 0, h->stream, (const int *)h->ws.info, G.gather_dev);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
+    int fetch() {
+        CIP_HIP_CHECK(hipMemcpyAsync(G.gather_host, G.gather_dev, sizeof(double) * (size_t)B * CIP_GATHER, hipMemcpyDeviceToHost, h->stream));
+        return cip_wait(h->stream);
+    }
+    const double *flags(int z) const { return G.gather_host + (size_t)z * CIP_GATHER + INFO_SLOT; }
+    // what every factorisation's flags may say, bad pivots aside.  Returns > 0: the problem has left the group
+    int common_flags(int z) {
+        const double *gi = flags(z);
+        if (gi[1] != 0.0) { cip_set_error("LDL': a triangular sweep bailed out (problem %d)", z); return -1; }
+        // gi[3]: an in-launch wait of the fused panel launch gave up -- a GPU shared with other processes can keep a launch's
+        // workgroups off the chip for longer than the bound.  The problem leaves the group like one with a bad pivot and is
+        // solved alone afterwards, on the three-launch chain (no in-launch wait, same bits)
+        if (gi[3] != 0.0) {
+            G.h[z]->ws.unfused = 1; G.h[z]->n_chain_fallbacks += 1; h->ws.unfused = 1;      // (h: the group's launches follow problem 0's workspace -- three launches per panel from here on)
+            eject(z);
+            return 1;
+        }
+        return 0;
+    }
+    void eject(int z) { ejected[z] = 1; active &= ~(1ull << z); reg &= ~(1ull << z); publish(); }
+    void publish() { cip_tl_bz.reg_mask = reg; }
+    // a regularised factor: a wrong-sign pivot -- |d| ~ delta, rounding decides its sign -- is harmless (the refined solves work
+    // against the true operator); a zero / non-finite one ends the problem with :Error, as it does alone (driver.hip: OneProblem)
+    void regularised_flags(int z) {
+        if (flags(z)[2] == 0.0) return;
+        outcome[z].status = CIP_STATUS_ERROR;
+        active &= ~(1ull << z);
+    }
     int take_pivots(bool fresh) override {
         // (a group of ONE problem is no batch for the kernels: its dot products do not go through the gather buffer)
-        if (!fresh || !cip_in_batch()) {
-            CIP_HIP_CHECK(hipMemcpyAsync(G.gather_host, G.gather_dev, sizeof(double) * (size_t)B * CIP_GATHER, hipMemcpyDeviceToHost, h->stream));
-            const int rcw = cip_wait(h->stream);
-            if (rcw) return rcw;
-        }
+        int rc;
+        if ((!fresh || !cip_in_batch()) && (rc = fetch())) return rc;
+        unsigned long long joining = 0;
         for (int z = 0; z < B; ++z) {
             if (!((active >> z) & 1ull)) continue;
-            const double *gi = G.gather_host + (size_t)z * CIP_GATHER + INFO_SLOT;
-            if (gi[1] != 0.0) { cip_set_error("LDL': a triangular sweep bailed out (problem %d)", z); return CIP_E_HIP; }
-            // gi[3]: an in-launch wait of the fused panel launch gave up -- a GPU shared with other processes can keep a launch's
-            // workgroups off the chip for longer than the bound.  The problem leaves the group like one with a bad pivot and is
-            // solved alone afterwards, on the three-launch chain (no in-launch wait, same bits)
-            if (gi[3] != 0.0) { G.h[z]->ws.unfused = 1; G.h[z]->n_chain_fallbacks += 1; h->ws.unfused = 1; }      // (h: the group's launches follow problem 0's workspace -- three launches per panel from here on)
-            if (gi[0] != 0.0 || gi[3] != 0.0) { ejected[z] = 1; active &= ~(1ull << z); }
+            if ((rc = common_flags(z)) < 0) return CIP_E_HIP;
+            if (rc > 0) continue;
+            if ((reg >> z) & 1ull) regularised_flags(z);
+            else if (flags(z)[0] != 0.0) { if (keep) joining |= 1ull << z; else eject(z); }
+        }
+        if (!joining) return 0;
+        // the problems that have just met their first bad pivot: assembly, regularisation and LDL' again, for them alone, and their
+        // flags back.  No solve has been enqueued on the factorisation being replaced (Loop::run takes the flags first), and the redo
+        // is not a factorisation of its own in n_factor -- as for one problem (api.hip: factor_resolve)
+        reg |= joining; publish();
+        const unsigned long long mk = cip_tl_bz.mask;
+        cip_tl_bz.mask = joining;
+        rc = factor_under(joining);
+        if (!rc) rc = ride_pivots();
+        if (!rc) rc = fetch();
+        cip_tl_bz.mask = mk;
+        if (rc) return rc;
+        for (int z = 0; z < B; ++z) {
+            if (!((joining >> z) & 1ull)) continue;
+            if ((rc = common_flags(z)) < 0) return CIP_E_HIP;
+            if (rc == 0) regularised_flags(z);
         }
         return 0;
     }
@@ -236,7 +305,8 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     // (the probe is a full handle creation: 0.9 ms per call, 4 % of an 8-problem pass), else always probe
     const bool csr = probs[0].A == nullptr && m > 0;
     const bool csr_host = csr && probs[0].A_rowptr && ((probs[0].flags & CIP_FLAG_CSR_HOST) || !(probs[0].flags & CIP_FLAG_DEVICE_PTRS));
-    std::vector<long> sig = shape_signature(probs[0], cip_tl_solve_block_max);
+    const bool keep_reg = g_keep_regularized.load() != 0;            // (read once: the group's slab and its policy must agree)
+    std::vector<long> sig = shape_signature(probs[0], cip_tl_solve_block_max, keep_reg);
     if (csr_host) sig.push_back((long)probs[0].A_rowptr[m]);
     // the same for a CSR Q (its slab share is O(nnz)): a count that cannot be read here means "always probe"
     const bool qcsr = (probs[0].flags & CIP_FLAG_Q_CSR) != 0;
@@ -249,6 +319,7 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     if (slab == 0) {
         cip_handle *probe = nullptr;
         if ((rc = cip_create_ex(&probs[0], &probe))) return rc;
+        if (keep_reg && (rc = cip_alloc_refine_buffers(probe))) { cip_destroy(probe); return rc; }
         slab = probe->alloc_bytes + ((cip_driver_bytes(probe) + 255) & ~(size_t)255);
         const bool large_S = probe->cs.nlarge > 0;
         cip_destroy(probe);
@@ -274,6 +345,8 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
         void *drv = nullptr;
         if ((rc = cip_handle_alloc(hz, &drv, cip_driver_bytes(hz)))) return rc;
         hz->drv = (double *)drv;
+        // what a regularised factor's refined solves would allocate on first use: in a slab every problem's buffer sits at problem 0's offset
+        if (keep_reg && (rc = cip_alloc_refine_buffers(hz))) return rc;
         if (hz->arena_overflow || (z > 0 && hz->arena_used != G.h[0]->arena_used)) {
             cip_set_error("lock-step batch: problem %d does not fit problem 0's slab layout", z);
             return CIP_E_UNSUPPORTED;
@@ -286,9 +359,9 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     }
     t_create = since();
     hipStream_t s = G.stream;
-    CipBatchCtx ctx = {B, (long)G.stride, full_mask(B), G.gather_dev, G.gather_host};
+    CipBatchCtx ctx = {B, (long)G.stride, full_mask(B), G.gather_dev, G.gather_host, 0ull};
     BatchScope scope(ctx);
-    GroupLoop L(G);
+    GroupLoop L(G, keep_reg);
     if ((rc = L.run(c, b, d, o, res, nullptr, 0))) return rc;
     if (timing) { (void)hipStreamSynchronize(s); t_loop = since(); }
     // ---- results of the lock-step problems
@@ -312,10 +385,11 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     }
     g_last_stats[0] += 1; g_last_stats[1] += B;
     for (int z = 0; z < B; ++z) g_last_stats[2] += L.ejected[z] ? 1 : 0;
+    g_last_stats[3] += __builtin_popcountll(L.reg);                  // (a problem that left the group afterwards is no longer in it)
     exit_timer.on = timing; exit_timer.t0 = std::chrono::steady_clock::now();
     // ---- problems that left the group: the one-problem loop on their own handle (regularised factorisation and all)
     {
-        BatchScope single(CipBatchCtx{1, 0, 1ull, nullptr, nullptr});
+        BatchScope single(CipBatchCtx{1, 0, 1ull, nullptr, nullptr, 0ull});
         for (int z = 0; z < B; ++z) {
             if (!L.ejected[z]) continue;
             cip_handle *hz = G.h[z];
@@ -358,7 +432,7 @@ extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const d
             return CIP_E_UNSUPPORTED;
         }
     if (cip_tl_builder) { cip_set_error("lock-step batch inside a graph recording"); return CIP_E_INVALID; }
-    if (!g_stats_accumulate) g_last_stats[0] = g_last_stats[1] = g_last_stats[2] = 0;
+    if (!g_stats_accumulate) for (int &q : g_last_stats) q = 0;
     auto range = [&](int i0, int i1) -> int {                // groups of up to 64 over [i0, i1), one after the other, on the calling thread
         for (int g0 = i0; g0 < i1; g0 += CIP_BATCH_MAX) {
             const int B = (i1 - g0 < CIP_BATCH_MAX) ? (i1 - g0) : CIP_BATCH_MAX;
@@ -386,21 +460,21 @@ extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const d
     CIP_HIP_CHECK(hipGetDevice(&device));
     std::vector<int> rcs(nsplit, 0);
     std::vector<std::string> errs(nsplit);
-    std::vector<int> st(3 * (size_t)nsplit, 0);
+    std::vector<int> st(N_STATS * (size_t)nsplit, 0);
     std::vector<std::thread> th;
     const int per = (count + nsplit - 1) / nsplit;
     for (int t = 0; t < nsplit; ++t)
         th.emplace_back([&, t] {
             (void)hipSetDevice(device);
-            g_last_stats[0] = g_last_stats[1] = g_last_stats[2] = 0;
+            for (int &q : g_last_stats) q = 0;
             const int i0 = t * per, i1 = (t + 1) * per < count ? (t + 1) * per : count;
             rcs[t] = i0 < i1 ? range(i0, i1) : 0;
             if (rcs[t]) errs[t] = cip_last_error();
-            for (int q = 0; q < 3; ++q) st[3 * t + q] = g_last_stats[q];
+            for (int q = 0; q < N_STATS; ++q) st[N_STATS * t + q] = g_last_stats[q];
         });
     for (auto &x : th) x.join();
     for (int t = 0; t < nsplit; ++t)
-        for (int q = 0; q < 3; ++q) g_last_stats[q] += st[3 * t + q];
+        for (int q = 0; q < N_STATS; ++q) g_last_stats[q] += st[N_STATS * t + q];
     for (int t = 0; t < nsplit; ++t)
         if (rcs[t]) { cip_set_error("%s", errs[t].c_str()); return rcs[t]; }
     return 0;
@@ -431,7 +505,7 @@ extern "C" int cip_conicip_mixed(int count, const cip_problem *probs, const doub
         if (k == bins.size()) bins.emplace_back();
         bins[k].push_back(i);
     }
-    g_last_stats[0] = g_last_stats[1] = g_last_stats[2] = 0;
+    for (int &q : g_last_stats) q = 0;
     struct Acc { Acc() { g_stats_accumulate = true; } ~Acc() { g_stats_accumulate = false; } } acc;
     std::vector<int> rest;
     auto run = [&](const std::vector<int> &idx, bool lock) -> int {
@@ -479,5 +553,19 @@ extern "C" int cip_release_cached_memory(void) {
 extern "C" int cip_lockstep_stats(int *out3) {
     if (!out3) return CIP_E_INVALID;
     for (int i = 0; i < 3; ++i) out3[i] = g_last_stats[i];
+    return 0;
+}
+
+// 1: a problem whose factorisation meets a bad pivot is switched to the regularised factorisation inside its lock-step group; 0 (default):
+// it leaves the group and is solved alone.  Process-wide; any other argument only queries.  Returns the previous value
+extern "C" int cip_set_lockstep_regularize(int on) {
+    const int prev = g_keep_regularized.load();
+    if (on == 0 || on == 1) g_keep_regularized.store(on);
+    return prev;
+}
+// the calling thread's last cip_conicip_lockstep / cip_conicip_mixed: problems switched to the regularised factorisation inside their group
+extern "C" int cip_lockstep_regularized(int *count) {
+    if (!count) return CIP_E_INVALID;
+    *count = g_last_stats[3];
     return 0;
 }

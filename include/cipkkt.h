@@ -244,8 +244,11 @@ int cip_conicip_problems(int count, const cip_problem *probs, const double *cons
  * to 64).  Results are bit-identical to cip_conicip on each problem run with the same solve block (lock-step handles use
  * min(cip_set_solve_block_max, cip_lockstep_solve_block_for(B)): a standalone handle of order >= 1024 sums its triangular solves in wider blocks unless
  * cip_set_solve_block_max(that value) is called first -- the difference is rounding).  Returns CIP_E_UNSUPPORTED (nothing written) when
- * the batch does not qualify -- fall back to cip_conicip_problems.  A problem whose factorisation meets a bad pivot leaves
- * the group and is solved by the one-problem loop afterwards. */
+ * the batch does not qualify -- fall back to cip_conicip_problems.  A problem whose factorisation meets a zero or wrong-sign pivot in
+ * the static order (every LP with a free variable, singular Q with free variables) needs the regularised factorisation.  With
+ * cip_set_lockstep_regularize(0), the default, it leaves the group and is solved by the one-problem loop afterwards; with
+ * cip_set_lockstep_regularize(1) it stays: the group regularises its matrix and refines its solves under a mask of its own, with
+ * the launches and the bits of the one-problem loop.  Either way a problem whose panel chain gave up an in-launch wait leaves. */
 int cip_conicip_lockstep(int count, const cip_problem *probs, const double *const *c, const double *const *bvec,
                          const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                          double *const *v, cip_result *res);
@@ -260,6 +263,12 @@ int cip_conicip_mixed(int count, const cip_problem *probs, const double *const *
 int cip_release_cached_memory(void);
 /* diagnostics of the calling thread's last cip_conicip_lockstep: {groups, problems, problems that left their group} */
 int cip_lockstep_stats(int *out3);
+/* 1: problems that need the regularised factorisation stay in their lock-step group (see cip_conicip_lockstep); 0 (default): they
+ * leave it.  Process-wide; returns the previous value; any other argument only queries. */
+int cip_set_lockstep_regularize(int on);
+/* the calling thread's last cip_conicip_lockstep / cip_conicip_mixed: how many problems were switched to the regularised factorisation
+ * inside their group (summed over the groups, like cip_lockstep_stats; its third entry counts only the problems that still left) */
+int cip_lockstep_regularized(int *count);
 /* a lock-step call of at least 2 x 8 problems of one shape runs as k groups (default 2) SIDE BY SIDE, each on its own host thread and stream (the
  * groups fill each other's launch-latency gaps; per problem nothing changes: same kernels, same solve block, same bits).  k = 1: one
  * group after the other (the form up to round 5).  Also CIP_LOCKSTEP_SPLIT.  Process-wide; returns the previous value (k < 1: query).

@@ -349,14 +349,17 @@ end
 
 Independent problems in, solutions out, on one GPU (`cip_conicip_mixed`): the problems that share a shape advance through
 the loop in lock-step (one launch per step for all of them), the others through `in_flight` host threads inside the
-library (`sparse_q = true`: every Q as CSR; the form is part of the shape).  `problems[i]` is a tuple `(Q, c, A, b, cone_dims)` or `(Q, c, A, b, cone_dims, G, d)`; the keywords are
+library (`sparse_q = true`: every Q as CSR; the form is part of the shape).  `keep_regularized = true`: a problem whose
+factorisation needs the regularised LDL' (an LP with a free variable, `Q = spzeros` with free variables) stays in its lock-step group
+instead of being solved alone afterwards (`cip_set_lockstep_regularize`, set around the call and restored; `regularized[]`, a
+`Ref{Cint}`, receives how many were).  `problems[i]` is a tuple `(Q, c, A, b, cone_dims)` or `(Q, c, A, b, cone_dims, G, d)`; the keywords are
 `conicIP`'s and apply to every problem.  (The reference solves one problem per `conicIP` call, src/ConicIP.jl:472-480: this
 is N independent calls.  Sharding over several GPUs is one process per GPU, problem i on rank i mod N.)
 """
 function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, route = CIP_ROUTE_SCHUR,
                            optTol = 1e-6, DTB = 0.01, verbose = false, maxRefinementSteps = 3, maxIters = 100,
                            cache_nestodd = false, infeasTol = optTol, refinementThreshold = optTol / 1e7, stats = nothing,
-                           sparse_q = false)
+                           sparse_q = false, keep_regularized = false, regularized = nothing)
     k = length(problems)
     k == 0 && return ConicIP.Solution[]
     staged = Vector{_Staged}(undef, k)
@@ -377,10 +380,15 @@ function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, rou
         probs = [_problem(st) for st in staged]
         ptrs(xs) = Ptr{Float64}[isempty(x) ? Ptr{Float64}(C_NULL) : pointer(x) for x in xs]
         # (a NULL entry is fine where the problem's m or p is 0: include/cipkkt.h, cip_conicip_mixed)
-        _cipcheck(ccall(_sym(:cip_conicip_mixed), Cint,
+        # (the switch is process-wide: put back before the return code is looked at, so that an error leaves it as it was)
+        prev = keep_regularized ? ccall(_sym(:cip_set_lockstep_regularize), Cint, (Cint,), 1) : Cint(-1)
+        rc = ccall(_sym(:cip_conicip_mixed), Cint,
             (Cint, Ptr{CipProblem}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ref{CipOptions},
              Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{CipResult}, Cint),
-            k, probs, ptrs(cs), ptrs(bs), ptrs(ds), opt, ptrs(ys), ptrs(ws), ptrs(vs), res, in_flight))
+            k, probs, ptrs(cs), ptrs(bs), ptrs(ds), opt, ptrs(ys), ptrs(ws), ptrs(vs), res, in_flight)
+        prev >= 0 && ccall(_sym(:cip_set_lockstep_regularize), Cint, (Cint,), prev)
+        _cipcheck(rc)
+        regularized === nothing || _cipcheck(ccall(_sym(:cip_lockstep_regularized), Cint, (Ref{Cint},), regularized))
     end
     stats === nothing || (stats[] = res)
     [_solution(ys[i], ws[i], vs[i], res[i]) for i in 1:k]
