@@ -58,6 +58,11 @@ certificates or norm-wise bounds, with c = 8 throughout:
     |Lz|_F / Lambda_i^1/2 through U and Lz, and column j of S R^-T = Ls V Lambda^1/2 has norm at most
     |Ls|_F Lambda_j^1/2, so (R^-1 S R^-T)_ij is within b (sqrt(Lambda_i / Lambda_j) + sqrt(Lambda_j / Lambda_i))
     of diag(Lambda): the diagonal within 2 b, like R' Z R.
+
+S cones above order ~300 (the last section of this file).  A full extended-precision product and the extended-precision
+Jacobi are no longer affordable there; Choleskys, a few rows of a product and matrix-vector products are.  The same
+quantities with the same bounds are evaluated on sampled rows (entrywise bound) and against +-1 probe vectors (row sums
+of the entrywise bound), Lambda against LAPACK within 2 b, and the max step by the certificate alone.
 """
 import mpmath as mp
 import numpy as np
@@ -482,3 +487,184 @@ def s_point(r, span, rng):
     lam = np.logspace(0.0, np.log10(span), r) * 10.0 ** rng.uniform(-2, 2) if r > 1 else np.array([1.0 + rng.random()])
     M = (Q * rng.permutation(lam)) @ Q.T
     return vecm(0.5 * (M + M.T))
+
+
+# ------------------------------------------------------------------------------------------ S cone above order ~300
+# A full extended-precision product costs r^3 (18 s at order 1025) and the extended-precision Jacobi minutes; Choleskys, a
+# few rows of a product (|S| r^2) and matrix-vector products stay cheap at every order.  The forms below evaluate the same
+# quantities and the same entrywise bounds as s_congruence, s_ftf, s_prod and the two NT identities above, on a set of
+# rows and against probe vectors.  Values are np.longdouble and in matrix form: the caller compares rows S of
+# mat(device output, LD) (resp. mat(device output, LD) @ W) with them.  In matrix form the sqrt2 of vecm is gone from value
+# and bound alike, so the bound of entry (i, j) is the bound of its vecm entry divided by the same factor.
+def sample_rows(r, seed, extra=8):
+    """the first and the last row of every band of 64 rows (clipped to r), rows 0 and r - 1, and `extra` rows drawn from
+    `seed`: every 64 x 64 tile of an r x r result is crossed by at least two full rows"""
+    S = {0, r - 1}
+    for b0 in range(0, r, 64):
+        S.update((b0, min(b0 + 63, r - 1)))
+    S.update(int(i) for i in np.random.default_rng(seed).integers(0, r, extra))
+    return np.array(sorted(S))
+
+
+def probe_vectors(r, seed, count=2):
+    """`count` columns of +-1 drawn from `seed` (r x count, extended precision)"""
+    return np.where(np.random.default_rng(seed).random((r, count)) < 0.5, -1.0, 1.0).astype(LD)
+
+
+def _mm(A, B):
+    """A @ B.  numpy has no BLAS for np.longdouble and walks B down its columns: with B' laid out first the same
+    sums, accumulated in extended precision, run several times faster"""
+    if A.dtype != LD:
+        return A @ B
+    return np.einsum("ik,jk->ij", A, np.ascontiguousarray(B.T))
+
+
+def _rows_of(terms, S):
+    """rows S of sum_t A_1 A_2 .. A_k over the factor lists `terms`: |S| r^2 per factor"""
+    out = 0
+    for mats in terms:
+        T = mats[0][S, :]
+        for M in mats[1:]:
+            T = _mm(T, M)
+        out = out + T
+    return out
+
+
+def _applied(terms, W):
+    """(sum_t A_1 A_2 .. A_k) W by matrix-vector products, right to left"""
+    out = 0
+    for mats in terms:
+        T = W
+        for M in reversed(mats):
+            T = _mm(M, T)
+        out = out + T
+    return out
+
+
+def _magnitudes(terms):
+    return [[np.abs(M).astype(np.float64) for M in mats] for mats in terms]
+
+
+def _congruence_terms(P, x, tr):
+    Pl = np.asarray(P, dtype=np.float64).astype(LD)
+    r = Pl.shape[0]
+    return [[Pl, mat(x, LD), Pl.T] if tr else [Pl.T, mat(x, LD), Pl]], C * (2 * r + 2) * U
+
+
+def _ftf_terms(R, x):
+    Rl = np.asarray(R, dtype=np.float64).astype(LD)
+    r = Rl.shape[0]
+    return [[Rl, Rl.T, mat(x, LD), Rl, Rl.T]], C * (4 * r + 4) * U
+
+
+def _prod_terms(x, y):
+    X, Y = mat(x, LD), mat(y, LD)
+    return [[X, Y], [Y, X]], C * (X.shape[0] + 2) * U
+
+
+def _sampled(terms_const, S):
+    terms, const = terms_const
+    return _rows_of(terms, S), const * _rows_of(_magnitudes(terms), S)
+
+
+def _probed(terms_const, W):
+    """the per-row bound is the row sum of the entrywise bound, |(E w)_i| <= sum_j |E_ij| for w in {+-1}^r: deterministic and
+    valid, about r times coarser than the entrywise bound (which is why there are sampled rows as well)"""
+    terms, const = terms_const
+    r = terms[0][0].shape[0]
+    return _applied(terms, W), const * _applied(_magnitudes(terms), np.ones(r))
+
+
+def s_congruence_rows(P, x, tr, S):
+    """(rows S of P' X P (tr False) or P X P', rows S of the entrywise bound of s_congruence), matrix form"""
+    return _sampled(_congruence_terms(P, x, tr), S)
+
+
+def s_congruence_probe(P, x, tr, W):
+    """((P' X P) W by matrix-vector products, the row sums of the entrywise bound of s_congruence)"""
+    return _probed(_congruence_terms(P, x, tr), W)
+
+
+def s_ftf_rows(R, x, S):
+    return _sampled(_ftf_terms(R, x), S)
+
+
+def s_ftf_probe(R, x, W):
+    return _probed(_ftf_terms(R, x), W)
+
+
+def s_prod_rows(x, y, S):
+    return _sampled(_prod_terms(x, y), S)
+
+
+def s_prod_probe(x, y, W):
+    return _probed(_prod_terms(x, y), W)
+
+
+def s_rzr_rows(R, z, lam, b, S):
+    """(rows S of R' Z R - diag(lam), their bound 2 b), lam the device's Lambda in R's column order"""
+    Rl = np.asarray(R, dtype=np.float64).astype(LD)
+    T = _rows_of([[Rl.T, mat(z, LD), Rl]], S)
+    T[np.arange(len(S)), S] -= np.asarray(lam, dtype=LD)[S]
+    return T, np.full(T.shape, 2 * b)
+
+
+def s_rzr_probe(R, z, lam, b, W):
+    Rl = np.asarray(R, dtype=np.float64).astype(LD)
+    r = Rl.shape[0]
+    return _applied([[Rl.T, mat(z, LD), Rl]], W) - np.asarray(lam, dtype=LD)[:, None] * W, np.full(r, 2 * b * r)
+
+
+def s_risri_rows(Ri, s, lam, b, S):
+    """(rows S of R^-1 S R^-T - diag(lam), rows S of s_rinv_bound(lam, b))"""
+    Ril = np.asarray(Ri, dtype=np.float64).astype(LD)
+    T = _rows_of([[Ril, mat(s, LD), Ril.T]], S)
+    T[np.arange(len(S)), S] -= np.asarray(lam, dtype=LD)[S]
+    return T, s_rinv_bound(lam, b)[S, :]
+
+
+def s_risri_probe(Ri, s, lam, b, W):
+    Ril = np.asarray(Ri, dtype=np.float64).astype(LD)
+    q = np.sqrt(np.asarray(lam, dtype=np.float64))
+    bound = b * (q * np.sum(1.0 / q) + np.sum(q) / q)                                       # row sums of s_rinv_bound
+    return _applied([[Ril, mat(s, LD), Ril.T]], W) - np.asarray(lam, dtype=LD)[:, None] * W, bound
+
+
+def s_nt_fp64(z, s):
+    """(Lambda sorted ascending, its bound 2 b, Lz, Ls, b) above order 300, where ``svals_ld`` takes minutes: Lz and Ls in
+    extended precision (for b and the two NT identities, which pin Lambda: R' Z R = Lambda and R^-1 S R^-T = Lambda make
+    Lambda^2 similar to Z S), the singular values by LAPACK from the factors rounded to fp64.  The rounding of the
+    factors, the fp64 product Lz' Ls and LAPACK's SVD are norm-wise backward stable with the same constants as the
+    device's Choleskys, GEMM and Jacobi, so the reference is itself within b = c r u |Lz|_F |Ls|_F of the exact singular
+    values: device and reference differ by at most 2 b, one b for the device's error and one for the reference's."""
+    Lz, Ls = chol_ld(mat(z, LD)), chol_ld(mat(s, LD))
+    r = Lz.shape[0]
+    b = 8 * r * U * fro(Lz) * fro(Ls)
+    sv = np.linalg.svd(Lz.astype(np.float64).T @ Ls.astype(np.float64), compute_uv=False)
+    return np.sort(sv), 2 * b, Lz, Ls, b
+
+
+def s_nt_rotated(z, s):
+    """(Lambda sorted ascending, its bound, Lz, Ls, b) as ``s_nt``, several times faster at orders 200 .. 300: the
+    extended-precision Jacobi starts from G W, W the right singular vectors of G from LAPACK with one Newton-Schulz step
+    W = V (3 I - V'V) / 2 in extended precision.  The columns of G W are orthogonal to u cond(G), so two or three sweeps
+    are left of a dozen.  The singular values are those of G W and not of G: with eps = |W'W - I|_inf,
+    |sigma_i(G W) - sigma_i(G)| <= eps sigma_i(G), and 2 eps (eps about 1e-17, evaluated here; the factor 2 for the
+    rounding of W'W itself) times the largest singular value is added to b."""
+    Lz, Ls = chol_ld(mat(z, LD)), chol_ld(mat(s, LD))
+    r = Lz.shape[0]
+    G = _mm(Lz.T, Ls)
+    V = np.linalg.svd(G.astype(np.float64))[2].T.astype(LD)
+    I = np.eye(r, dtype=LD)
+    W = _mm(V, 1.5 * I - 0.5 * _mm(V.T, V))
+    eps = float(np.abs(_mm(W.T, W) - I).sum(axis=1).max())
+    sv = svals_ld(_mm(G, W)).astype(np.float64)
+    b = 8 * r * U * fro(Lz) * fro(Ls)
+    return sv, b + 2 * eps * float(sv.max()), Lz, Ls, b
+
+
+def lambda_min_certified(M, b):
+    """(the certificate |lambda_min(M)| <= b of ``lambda_min_within``: two extended-precision Choleskys,
+    |lambda_min| / b from LAPACK on M rounded to fp64: for the ratio bookkeeping only, it carries LAPACK's own error)"""
+    ok = lambda_min_within(M, 0.0, b)
+    return ok, float(abs(np.linalg.eigvalsh(np.asarray(M, dtype=np.float64)).min()) / b)

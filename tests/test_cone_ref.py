@@ -140,3 +140,127 @@ def test_oracle_meets_the_s_bounds(r, span):
             st = oc.maxstep_sdc(z, d * scale)
             M = CR.mat(z, CR.LD) - CR.LD(st) * CR.LD(scale) * CR.mat(d, CR.LD)
             assert CR.lambda_min_within(M, 0.0, CR.s_maxstep_bound(z, d, scale, st)), "oracle route"
+
+
+# ------------------------------------------------------------------------------------------ sampled rows and probes
+def _ld_terms(P, x):
+    Pl = np.asarray(P, dtype=np.float64).astype(CR.LD)
+    return Pl, CR.mat(x, CR.LD)
+
+
+@pytest.mark.parametrize("r", [20, 70])
+def test_sampled_and_probe_forms_agree_with_the_full_forms(r):
+    """The sampled and probe forms against (a) the same formula evaluated in full in extended precision, to 1e-17 of the
+    magnitude product (the sums run in another order: r 2^-64 < 1e-17 of the magnitudes), and (b) the existing full forms,
+    which return their value rounded to fp64 in vecm coordinates: to 3 u of the value on top (the rounding, and the sqrt2 of
+    vecm taken out again by mat).  The bounds agree to the rounding of their fp64 magnitude products."""
+    rng = np.random.default_rng(r)
+    S, W = CR.sample_rows(r, r), CR.probe_vectors(r, r)
+    assert {0, r - 1, 63 if r > 64 else r - 1}.issubset(S.tolist()) and (r <= 64 or 64 in S) and len(S) <= 2 * (-(-r // 64)) + 10
+    assert W.shape == (r, 2) and np.all(np.abs(W) == 1) and not np.array_equal(W[:, 0], W[:, 1])
+    z, s, x = CR.s_point(r, 1e8, rng), CR.s_point(r, 1e8, rng), rng.standard_normal(r * (r + 1) // 2)
+    P = rng.standard_normal((r, r))
+    Pl, X = _ld_terms(P, x)
+    Z = CR.mat(z, CR.LD)
+    Pa, Xa, Za = np.abs(P), np.abs(CR.mat(x)), np.abs(CR.mat(z))
+    PP, PPa = Pl @ Pl.T, Pa @ Pa.T
+    full = {
+        "P'XP": (Pl.T @ X @ Pl, Pa.T @ Xa @ Pa, CR.s_congruence(P, x, False), CR.s_congruence_rows(P, x, False, S), CR.s_congruence_probe(P, x, False, W)),
+        "PXP'": (Pl @ X @ Pl.T, Pa @ Xa @ Pa.T, CR.s_congruence(P, x, True), CR.s_congruence_rows(P, x, True, S), CR.s_congruence_probe(P, x, True, W)),
+        "F'F": (PP @ X @ PP, PPa @ Xa @ PPa, CR.s_ftf(P, x), CR.s_ftf_rows(P, x, S), CR.s_ftf_probe(P, x, W)),
+        "prod": (X @ Z + Z @ X, Xa @ Za + Za @ Xa, CR.s_prod(x, z), CR.s_prod_rows(x, z, S), CR.s_prod_probe(x, z, W)),
+    }
+    for name, (Y, mag, (ref64, bnd64), (rows, rbnd), (prb, pbnd)) in full.items():
+        assert rows.dtype == CR.LD and prb.dtype == CR.LD, name
+        assert np.all(np.abs(rows - Y[S]) <= 1e-17 * mag[S]), name
+        assert np.all(np.abs(prb - Y @ W) <= 1e-17 * mag.sum(1)[:, None]), name
+        assert np.all(np.abs(CR.mat(ref64)[S] - rows.astype(np.float64)) <= 3 * CR.U * np.abs(CR.mat(ref64)[S]) + 1e-17 * mag[S]), name
+        B = CR.mat(bnd64)                                       # the entrywise bound in matrix form
+        np.testing.assert_allclose(rbnd, B[S], rtol=1e-12, err_msg=name)
+        np.testing.assert_allclose(pbnd, B.sum(1), rtol=1e-12, err_msg=name)
+    # the two NT identities, with the oracle's R
+    R = oc.nestod_sdc(z, s)
+    Ri = np.linalg.inv(R)
+    lam = np.diag(R.T @ oc.mat(z) @ R).copy()
+    b = CR.s_nt(z, s)[1]
+    Rl, Ril = R.astype(CR.LD), Ri.astype(CR.LD)
+    D = np.diag(lam).astype(CR.LD)
+    for Y, mag, (rows, rbnd), (prb, pbnd), B in (
+            (Rl.T @ Z @ Rl - D, np.abs(R).T @ Za @ np.abs(R) + np.diag(lam), CR.s_rzr_rows(R, z, lam, b, S), CR.s_rzr_probe(R, z, lam, b, W),
+             np.full((r, r), 2 * b)),
+            (Ril @ CR.mat(s, CR.LD) @ Ril.T - D, np.abs(Ri) @ np.abs(CR.mat(s)) @ np.abs(Ri).T + np.diag(lam), CR.s_risri_rows(Ri, s, lam, b, S),
+             CR.s_risri_probe(Ri, s, lam, b, W), CR.s_rinv_bound(lam, b))):
+        assert np.all(np.abs(rows - Y[S]) <= 1e-17 * mag[S])
+        assert np.all(np.abs(prb - Y @ W) <= 1e-17 * mag.sum(1)[:, None])
+        np.testing.assert_allclose(rbnd, B[S], rtol=1e-12)
+        np.testing.assert_allclose(pbnd, B.sum(1), rtol=1e-12)
+        assert np.all(np.abs(rows) <= rbnd) and np.all(np.abs(prb) <= pbnd[:, None])        # the oracle's R meets them
+    # Lambda: the rotated Jacobi and LAPACK against svals_ld
+    sv, b0, _, _ = CR.s_nt(z, s)
+    svr, br, _, _, b1 = CR.s_nt_rotated(z, s)
+    assert b1 == b0 and b0 <= br <= b0 * (1 + 1e-3) and np.all(np.abs(svr - sv) <= 4 * CR.U * sv.max())
+    svf, bf, _, _, b2 = CR.s_nt_fp64(z, s)
+    assert b2 == b0 and bf == 2 * b0 and np.all(np.abs(svf - sv) <= b0)
+    # the certificate with its informational ratio
+    M = np.diag(np.array([3.0, 1e-14, 5.0])).astype(CR.LD)
+    ok, ratio = CR.lambda_min_certified(M, 1e-13)
+    assert ok and abs(ratio - 0.1) < 1e-6
+    assert not CR.lambda_min_certified(M, 1e-15)[0]
+
+
+def _reject(got, rows, rbnd, prb, pbnd, S, W):
+    """(rejected by the sampled rows, rejected by a probe) for a full output matrix `got`"""
+    G = np.asarray(got).astype(CR.LD)
+    return (bool(np.any(~(np.abs(G[S] - rows) <= rbnd))), bool(np.any(~(np.abs(CR._mm(G, W) - prb) <= pbnd[:, None]))))
+
+
+def test_sampled_rows_and_probes_reject_wrong_outputs():
+    """a congruence at order 300, span 1e8: what a tiled GEMM and the vecm store can get wrong is caught by the sampled rows
+    or by the probes, and the exact result rounded to fp64 passes"""
+    r = 300
+    rng = np.random.default_rng(300)
+    x = CR.s_point(r, 1e8, rng)
+    P = rng.standard_normal((r, r))
+    S, W = CR.sample_rows(r, 300), CR.probe_vectors(r, 300)
+    rows, rbnd = CR.s_congruence_rows(P, x, False, S)
+    prb, pbnd = CR.s_congruence_probe(P, x, False, W)
+    Pl, X = _ld_terms(P, x)
+    T = CR._mm(X, Pl)
+    Y = CR._mm(Pl.T, T)
+    Y = 0.5 * (Y + Y.T)
+    good = Y.astype(np.float64)
+    assert _reject(good, rows, rbnd, prb, pbnd, S, W) == (False, False)
+    t1, t2, t3 = slice(64, 128), slice(128, 192), slice(192, 256)
+
+    def both(M, I, J, tile):
+        M = M.copy()
+        M[I, J] = tile
+        M[J, I] = tile.T
+        return M
+    free = np.setdiff1d(np.arange(r), S)
+    i, j = free[5], free[40]                                   # neither row i nor row j is sampled
+    entry = good.copy()
+    entry[i, j] = entry[j, i] = good[i, j] * (1 + 1e-6)
+    srow = good.copy()
+    srow[S[3], 17] = srow[17, S[3]] = good[S[3], 17] * (1 + 1e-6)
+    sqrt2 = good.copy()
+    sqrt2[i, :] *= np.sqrt(2.0)
+    sqrt2[:, i] = sqrt2[i, :]
+    sqrt2[i, i] = good[i, i]
+    wrong = {
+        "tile transposed": both(good, t1, t2, good[t1, t2].T),
+        "tile from its neighbour": both(good, t1, t2, good[t1, t3]),
+        "k-slab of 32 dropped": both(good, t1, t2, (Y[t1, t2] - CR._mm(Pl[32:64, t1].T, T[32:64, t2])).astype(np.float64)),
+        "entry of a sampled row off by 1e-6": srow,
+        "entry elsewhere off by 1e-6": entry,
+        "sqrt2 missing in a row": sqrt2,
+    }
+    for name, M in wrong.items():
+        by_rows, by_probe = _reject(M, rows, rbnd, prb, pbnd, S, W)
+        assert by_rows or by_probe, name
+        if name.startswith(("tile", "k-slab", "entry of a sampled")):
+            assert by_rows, name                               # two full rows cross every tile
+        if name == "entry elsewhere off by 1e-6":
+            assert by_probe and not by_rows, name              # neither its row nor its column is sampled: the probes alone
+        if name == "sqrt2 missing in a row":
+            assert by_probe and by_rows, name                  # the row by the probes, its mirror column by every sampled row

@@ -98,6 +98,15 @@ CASES = {
     "full_dense_odd_m": ("full3x3", "dense", 256, 5, [("R", 100), ("Q", 300), ("Q", 3), ("Q", 8), ("Q", 64), ("Q", 65), ("Q", 1)]),
     # full 3x3, CSR A, even m and n: k_scatter_negA, the 16-byte k_copy_block_lower_v, k_sdp_fill_ftf for order 8 and 133
     "full_csr_sdp": ("full3x3", "csr", 300, 3, [("S", 36), ("R", 53), ("S", 8911)]),
+    # a large S cone above padded order 256 (order 257 -> rp = 512): cip_sdp_large_scale_At on the batched-64 GEMM path, the
+    # second product with the lower tiles selected, then k_lg_vecm_cols at rp = 512.  npad 128 = 1 tile and mpad 33168 >=
+    # 16384: split-K 128 with 16 slices (the cap) of 2080 rows, the last one 1968
+    "dense_sdp_257": ("schur", "dense", 40, 2, [("R", 10), ("S", 257 * 258 // 2)]),
+    # the same cones from a CSR A: k_scatter_AtS, then the same scaling at rp = 512
+    "csr_sdp_257": ("schur", "csr", 40, 2, [("R", 10), ("S", 257 * 258 // 2)]),
+    # order 513 -> rp = 1024: cip_sdp_large_scale_At on the batched-64 path with the lower tiles selected and k_lg_vecm_cols at
+    # rp = 1024, the S cone first (row offset 0).  mpad 131856: split-K 128, 16 slices of 8256 rows, the last one 8016
+    "dense_sdp_513": ("schur", "dense", 12, 0, [("S", 513 * 514 // 2), ("R", 7)]),
 }
 
 
@@ -119,7 +128,8 @@ def _syrk_form(n, m):
 
 # what the comments of CASES claim, kept in step with the dispatch rules
 FORMS = {"splitk64_uneven": ("splitk_64", 9), "splitk128_odd_n": ("splitk_128", 9), "splitk64_many_tiles": ("splitk_64", 5),
-         "syrkq_no_split": ("syrkq_64", 1), "dense_sdp_small_large": ("splitk_64", 16)}
+         "syrkq_no_split": ("syrkq_64", 1), "dense_sdp_small_large": ("splitk_64", 16),
+         "dense_sdp_257": ("splitk_128", 16), "csr_sdp_257": ("splitk_128", 16), "dense_sdp_513": ("splitk_128", 16)}
 
 
 def test_case_table_reaches_the_named_forms():
