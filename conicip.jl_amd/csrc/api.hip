@@ -922,7 +922,11 @@ static int mul_A(cip_handle *h, double alpha, const double *x, double beta, doub
     return cip_gemv_t(h->stream, h->n, h->m, alpha, h->At, h->npad, x, beta, y);
 }
 static int mul_At(cip_handle *h, double alpha, const double *x, double beta, double *y) {     // y = alpha A' x + beta y (n)
-    if (h->m == 0) { if (beta == 0.0) { int rcc = cip_zero(h->stream, h->n, y); if (rcc) return rcc; } return 0; }
+    if (h->m == 0) {                                                                          // y = beta y, as the G branch of cip_gemv_dev
+        if (beta == 0.0) return cip_zero(h->stream, h->n, y);
+        if (beta != 1.0) return cip_axpby(h->stream, h->n, 0.0, y, beta, y);
+        return 0;
+    }
     if (h->A_sparse) return cip_spmv_csr(h->stream, h->n, h->T_rp, h->T_ci, h->T_v, alpha, x, beta, y);
     return cip_gemv_t(h->stream, h->m, h->n, alpha, h->A, h->m, x, beta, y);
 }
