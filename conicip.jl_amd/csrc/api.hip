@@ -81,6 +81,7 @@ int cip_handle_alloc(cip_handle *h, void **out, size_t bytes) {
         e = hipMalloc(out, bytes);
     }
     CIP_HIP_CHECK(e);
+    h->owned.push_back(*out);                      // (a piece of the arena is not the handle's to free)
     return debug_poison(*out, bytes);
 }
 #define DMALLOC(ptr, bytes)                                                        \
@@ -88,8 +89,31 @@ int cip_handle_alloc(cip_handle *h, void **out, size_t bytes) {
         int rc__ = cip_handle_alloc(h, (void **)&(ptr), (size_t)(bytes));          \
         if (rc__) return rc__;                                                     \
     } while (0)
-static bool in_arena(const cip_handle *h, const void *p) {
-    return h->arena && (const char *)p >= h->arena && (const char *)p < h->arena + h->arena_cap;
+
+// ---- views of the handle's packed (8-byte granular) scratch buffers; each layout function sizes the allocation and carves for every user
+#define CIP_MANY_CHUNK 64
+struct Vec3 { double *x, *y, *z; };            // an (n, p, m) triple of k columns each
+static Vec3 take3(CipLayout &L, const cip_handle *h, size_t k = 1) { return Vec3{L.take<double>(h->n * k, 8), L.take<double>(h->p * k, 8), L.take<double>(h->m * k, 8)}; }
+// h->stage (k = cap = 1), h->many_stage (cap = CIP_MANY_CHUNK): input and output triple of k <= cap columns, each at the front of its half
+struct StageView { Vec3 in, out; };
+static size_t stage_layout(CipLayout L, const cip_handle *h, size_t k, size_t cap, StageView *v) {
+    const size_t slack = ((size_t)h->n + h->p + h->m) * (cap - k);
+    v->in = take3(L, h, k); L.take<double>(slack, 8);
+    v->out = take3(L, h, k); L.take<double>(slack, 8);
+    return L.bytes();
+}
+// h->ref: right-hand side, residual and correction of the refined solve, 8 spare doubles behind each
+struct RefView { Vec3 rhs, res, cor; };
+static size_t ref_layout(CipLayout L, const cip_handle *h, RefView *v) {
+    for (Vec3 *b : {&v->rhs, &v->res, &v->cor}) { *b = take3(L, h); L.take<double>(8, 8); }
+    return L.bytes();
+}
+// h->many, CIP_MANY_CHUNK columns each: the Npad-row right-hand sides R, the m-row blocks T and U of the Schur route, the sweeps' scratch S
+struct ManyView { double *R, *T, *U, *S; };
+static size_t many_layout(CipLayout L, const cip_handle *h, ManyView *v) {
+    const size_t c = CIP_MANY_CHUNK;
+    *v = ManyView{L.take<double>(c * h->Npad, 8), L.take<double>(c * h->m, 8), L.take<double>(c * h->m, 8), L.take<double>(c * h->ws.Bs, 8)};
+    return L.bytes();
 }
 
 static void free_all(cip_handle *h) {
@@ -97,11 +121,8 @@ static void free_all(cip_handle *h) {
     if (h->ldlt_side) { cip_ldlt_side_destroy(h->ldlt_side); h->ldlt_side = nullptr; }
     if (h->gx_solve) { (void)hipGraphExecDestroy(h->gx_solve); h->gx_solve = nullptr; }
     if (h->cs.lg) { cip_sdp_large_destroy(h->cs.lg); h->cs.lg = nullptr; }
-    void *ptrs[] = {h->cs.d_bigq, h->cs.d_ritems, h->cs.d_packq, h->cs.d_sidx_small, h->cs.d_sidx, h->cs.d_sdpws, h->cs.d_sdpvec, h->cs.d_sdpflag, h->Q, h->symv_ws, h->Q_rp, h->Q_ci, h->Q_v, h->A, h->At, h->A_rp, h->A_ci, h->A_v, h->T_rp, h->T_ci, h->T_v, h->kdiag, h->row_cone, h->G, h->Gt,
-                    h->cs.d_cones, h->cs.d_items, h->cs.d_scal, h->cs.d_partial, h->cs.d_scalar, h->K, h->Wt, h->syrk_ws, h->Gm, h->AtS, h->WtS,
-                    h->ws_base, h->rhs, h->mt1, h->mt2, h->mt3, h->nt1, h->pt1, h->dot_scratch, h->stage, h->drv, h->ref, h->c2x2, h->many, h->many_stage};
-    for (void *p : ptrs)
-        if (p && !in_arena(h, p)) (void)hipFree(p);
+    for (auto it = h->owned.rbegin(); it != h->owned.rend(); ++it) (void)hipFree(*it);
+    h->owned.clear();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev2) (void)hipEventDestroy(h->ev2);
@@ -542,7 +563,7 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
     DMALLOC(h->mt1, sizeof(double) * m); DMALLOC(h->mt2, sizeof(double) * m); DMALLOC(h->mt3, sizeof(double) * m);
     DMALLOC(h->nt1, sizeof(double) * n); DMALLOC(h->pt1, sizeof(double) * p);
     DMALLOC(h->dot_scratch, sizeof(double) * (32 * 32 + 32));
-    DMALLOC(h->stage, sizeof(double) * 2 * (size_t)(n + p + m));
+    { StageView v; DMALLOC(h->stage, stage_layout(nullptr, h, 1, 1, &v)); }
     CIP_HIP_CHECK(hipEventCreate(&h->ev0)); CIP_HIP_CHECK(hipEventCreate(&h->ev1)); CIP_HIP_CHECK(hipEventCreate(&h->ev2));
     // (the pinned pivot-flag words are allocated by the first factorisation: pinned allocations cost ~0.1 ms each, and the
     //  64 handles of a lock-step group never use theirs)
@@ -1026,14 +1047,14 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
     // problems, each leaving it when ITS residual has converged, stagnates or is not finite -- every problem sees the launches it
     // sees alone.
     hipStream_t s = h->stream;
-    const size_t tot = (size_t)n + p + m;
     if (!h->ref) {
         if (batch) { cip_set_error("cip_solve3x3: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
         if ((rc = cip_alloc_refine_buffers(h))) return rc;
     }
-    double *xs = h->ref, *ys = xs + n, *zs = ys + p;              // private copy of the right-hand side (z may alias c)
-    double *rx = h->ref + tot + 8, *ry = rx + n, *rz = ry + p;
-    double *da = h->ref + 2 * (tot + 8), *db = da + n, *dc = db + p;
+    RefView v;
+    ref_layout(h->ref, h, &v);
+    double *xs = v.rhs.x, *ys = v.rhs.y, *zs = v.rhs.z;           // private copy of the right-hand side (z may alias c)
+    double *rx = v.res.x, *ry = v.res.y, *rz = v.res.z, *da = v.cor.x, *db = v.cor.y, *dc = v.cor.z;
     { int rcc = cip_copy(s, n, x, xs); if (rcc) return rcc; }
     if (p > 0) { int rcc = cip_copy(s, p, y, ys); if (rcc) return rcc; }
     if (m > 0) { int rcc = cip_copy(s, m, z, zs); if (rcc) return rcc; }
@@ -1065,7 +1086,7 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
     return 0;
 }
 int cip_alloc_refine_buffers(cip_handle *h) {
-    if (!h->ref) DMALLOC(h->ref, sizeof(double) * 3 * ((size_t)h->n + h->p + h->m + 8));
+    if (!h->ref) { RefView v; DMALLOC(h->ref, ref_layout(nullptr, h, &v)); }
     if (!h->c2x2 && h->m > 0 && h->route == CIP_ROUTE_SCHUR) DMALLOC(h->c2x2, sizeof(double) * h->m);
     return 0;
 }
@@ -1075,16 +1096,17 @@ extern "C" int cip_solve3x3(cip_handle *h, const double *x, const double *y, con
     if (!h) return CIP_E_INVALID;
     hipStream_t s = h->stream;
     const int n = h->n, m = h->m, p = h->p;
-    double *in = h->stage, *out = h->stage + (n + p + m);
-    CIP_HIP_CHECK(hipMemcpyAsync(in, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(in + n, y, sizeof(double) * p, hipMemcpyHostToDevice, s));
-    if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(in + n + p, z, sizeof(double) * m, hipMemcpyHostToDevice, s));
+    StageView v;
+    stage_layout(h->stage, h, 1, 1, &v);
+    CIP_HIP_CHECK(hipMemcpyAsync(v.in.x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(v.in.y, y, sizeof(double) * p, hipMemcpyHostToDevice, s));
+    if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(v.in.z, z, sizeof(double) * m, hipMemcpyHostToDevice, s));
     int rc;
     if (h->factored && (rc = factor_resolve(h, true))) return rc;      // this entry point is synchronous anyway
-    if ((rc = cip_solve3x3_dev(h, in, in + n, in + n + p, out, out + n, out + n + p))) return rc;
-    CIP_HIP_CHECK(hipMemcpyAsync(a, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(b, out + n, sizeof(double) * p, hipMemcpyDeviceToHost, s));
-    if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(c, out + n + p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    if ((rc = cip_solve3x3_dev(h, v.in.x, v.in.y, v.in.z, v.out.x, v.out.y, v.out.z))) return rc;
+    CIP_HIP_CHECK(hipMemcpyAsync(a, v.out.x, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(b, v.out.y, sizeof(double) * p, hipMemcpyDeviceToHost, s));
+    if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(c, v.out.z, sizeof(double) * m, hipMemcpyDeviceToHost, s));
     CIP_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }
@@ -1124,14 +1146,15 @@ extern "C" int cip_solve2x2(cip_handle *h, const double *y, const double *w, dou
     if (!h) return CIP_E_INVALID;
     hipStream_t s = h->stream;
     const int n = h->n, p = h->p;
-    double *in = h->stage, *out = h->stage + (n + p + h->m);
-    CIP_HIP_CHECK(hipMemcpyAsync(in, y, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(in + n, w, sizeof(double) * p, hipMemcpyHostToDevice, s));
+    StageView v;
+    stage_layout(h->stage, h, 1, 1, &v);
+    CIP_HIP_CHECK(hipMemcpyAsync(v.in.x, y, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(v.in.y, w, sizeof(double) * p, hipMemcpyHostToDevice, s));
     int rc;
     if (h->factored && (rc = factor_resolve(h, true))) return rc;
-    if ((rc = cip_solve2x2_dev(h, in, in + n, out, out + n))) return rc;
-    CIP_HIP_CHECK(hipMemcpyAsync(dy, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(dw, out + n, sizeof(double) * p, hipMemcpyDeviceToHost, s));
+    if ((rc = cip_solve2x2_dev(h, v.in.x, v.in.y, v.out.x, v.out.y))) return rc;
+    CIP_HIP_CHECK(hipMemcpyAsync(dy, v.out.x, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(dw, v.out.y, sizeof(double) * p, hipMemcpyDeviceToHost, s));
     CIP_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }
@@ -1140,20 +1163,15 @@ extern "C" int cip_solve2x2(cip_handle *h, const double *y, const double *w, dou
 // X n x nrhs, Y p x nrhs, Z m x nrhs (col-major, ld = rows); the same as nrhs calls of the single entry point, 64 columns at a time:
 // the cone operations and the CSR products per column, the dense A / A' products and the LDL' sweeps over all columns of a chunk
 // (solve_many.hip).  Regularised factor: nrhs refined single solves.
-#define CIP_MANY_CHUNK 64
-static int many_buffers(cip_handle *h) {
-    if (h->many) return 0;
-    DMALLOC(h->many, sizeof(double) * CIP_MANY_CHUNK * ((size_t)h->Npad + 2 * (size_t)h->m + (size_t)h->ws.Bs));
-    return 0;
-}
 // kc <= 64 columns of solve3x3_once (z == NULL: the 2x2 form of the Schur route); c may alias z
 static int solve3x3_chunk(cip_handle *h, int kc, const double *x, const double *y, const double *z, double *a, double *b, double *c) {
     hipStream_t s = h->stream;
     const int n = h->n, p = h->p, N = h->N, Npad = h->Npad;
     const int m = z ? h->m : 0;
     const long ldr = Npad;
-    double *R = h->many, *T = R + (size_t)CIP_MANY_CHUNK * Npad, *U = T + (size_t)CIP_MANY_CHUNK * h->m;
-    double *S = U + (size_t)CIP_MANY_CHUNK * h->m;
+    ManyView v;
+    many_layout(h->many, h, &v);
+    double *R = v.R, *T = v.T, *U = v.U, *S = v.S;
     int rc;
     if (h->route == CIP_ROUTE_SCHUR) {
         // t = (F'F)^-1 z ; [S G'; G 0][a; b] = [x + A't; y] ; c = t - (F'F)^-1 A a
@@ -1219,7 +1237,7 @@ static int solve_many_impl(cip_handle *h, bool two2, int nrhs, const double *X, 
     }
     if (h->info_pending) h->spec_solves += nrhs;
     h->n_solve += nrhs;
-    if ((rc = many_buffers(h))) return rc;
+    if (!h->many) { ManyView v; DMALLOC(h->many, many_layout(nullptr, h, &v)); }
     CipRange rg(two2 ? "cip:solve2x2_many" : "cip:solve3x3_many");
     for (int c0 = 0; c0 < nrhs; c0 += CIP_MANY_CHUNK) {
         const int kc = nrhs - c0 < CIP_MANY_CHUNK ? nrhs - c0 : CIP_MANY_CHUNK;
@@ -1240,12 +1258,12 @@ static int solve_many_host(cip_handle *h, bool two2, int nrhs, const double *X, 
                            double *C) {
     hipStream_t s = h->stream;
     const int n = h->n, p = h->p, m = two2 ? 0 : h->m;
-    const size_t col = (size_t)n + p + h->m;
-    if (!h->many_stage) DMALLOC(h->many_stage, sizeof(double) * 2 * col * CIP_MANY_CHUNK);
+    StageView v;
+    if (!h->many_stage) DMALLOC(h->many_stage, stage_layout(nullptr, h, CIP_MANY_CHUNK, CIP_MANY_CHUNK, &v));
     for (int c0 = 0; c0 < nrhs; c0 += CIP_MANY_CHUNK) {
         const int kc = nrhs - c0 < CIP_MANY_CHUNK ? nrhs - c0 : CIP_MANY_CHUNK;
-        double *xi = h->many_stage, *yi = xi + (size_t)n * kc, *zi = yi + (size_t)p * kc;
-        double *ao = h->many_stage + col * CIP_MANY_CHUNK, *bo = ao + (size_t)n * kc, *co = bo + (size_t)p * kc;
+        stage_layout(h->many_stage, h, kc, CIP_MANY_CHUNK, &v);
+        double *xi = v.in.x, *yi = v.in.y, *zi = v.in.z, *ao = v.out.x, *bo = v.out.y, *co = v.out.z;
         CIP_HIP_CHECK(hipMemcpyAsync(xi, X + (size_t)c0 * n, sizeof(double) * n * kc, hipMemcpyHostToDevice, s));
         if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(yi, Y + (size_t)c0 * p, sizeof(double) * p * kc, hipMemcpyHostToDevice, s));
         if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(zi, Z + (size_t)c0 * m, sizeof(double) * m * kc, hipMemcpyHostToDevice, s));

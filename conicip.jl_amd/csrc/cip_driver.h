@@ -18,26 +18,21 @@ struct Vec4 {          // (y[n], w[p], v[m], s[m]) stored contiguously
     double *base = nullptr, *y = nullptr, *w = nullptr, *v = nullptr, *s = nullptr;
 };
 
-inline size_t pad32(size_t c) { return (c + 31) & ~(size_t)31; }      // 256-byte alignment of every vector
-inline size_t driver_doubles(int n, int m, int p) {
-    const size_t NT = (size_t)n + p + 2 * (size_t)m;
-    return 9 * pad32(NT) + pad32(n) + pad32(m) + pad32(p) + 5 * pad32(m) + 2 * pad32(n) + pad32(m) + pad32(p) + 32;
-}
-
-// every vector of the loop, carved out of h->drv in a fixed order
+// every vector of the loop, carved out of h->drv in a fixed order, each 256-byte aligned
 struct Vectors {
     double *c_d, *b_d, *d_d;
     Vec4 z, r0, rleft, r, daff, dz, dzr, rIr, rkkt;
     double *e, *lam, *mb1, *mb2, *mb3, *Qy, *pinf, *Ays, *Gy;
-    void carve(double *base, int n, int m, int p) {
-        double *next = base;
-        auto dalloc = [&](size_t count) { double *ptr = next; next += pad32(count); return ptr; };
+    size_t carve(double *base, int n, int m, int p) {          // returns the bytes of the layout (base == NULL: sizing only)
+        CipLayout L(base);
         const size_t NT = (size_t)n + p + 2 * (size_t)m;
-        auto vec4 = [&]() { Vec4 v; v.base = dalloc(NT); v.y = v.base; v.w = v.y + n; v.v = v.w + p; v.s = v.v + m; return v; };
-        c_d = dalloc(n); b_d = dalloc(m); d_d = dalloc(p);
+        auto vec4 = [&]() { Vec4 v; if ((v.base = v.y = L.take<double>(NT))) { v.w = v.y + n; v.v = v.w + p; v.s = v.v + m; } return v; };
+        c_d = L.take<double>(n); b_d = L.take<double>(m); d_d = L.take<double>(p);
         z = vec4(); r0 = vec4(); rleft = vec4(); r = vec4(); daff = vec4(); dz = vec4(); dzr = vec4(); rIr = vec4(); rkkt = vec4();
-        e = dalloc(m); lam = dalloc(m); mb1 = dalloc(m); mb2 = dalloc(m); mb3 = dalloc(m);
-        Qy = dalloc(n); pinf = dalloc(n); Ays = dalloc(m); Gy = dalloc(p);
+        e = L.take<double>(m); lam = L.take<double>(m); mb1 = L.take<double>(m); mb2 = L.take<double>(m); mb3 = L.take<double>(m);
+        Qy = L.take<double>(n); pinf = L.take<double>(n); Ays = L.take<double>(m); Gy = L.take<double>(p);
+        L.take<double>(32);               // tail: part of h->drv's size, which the lock-step arena's stride is built from
+        return L.bytes();
     }
 };
 

@@ -13,6 +13,7 @@ struct cip_handle {
     // Device memory of the handle.  Normally one hipMalloc per buffer; a handle of a lock-step batch carves its buffers,
     // in creation order, out of its slab of the batch's arena (api.hip: cip_handle_alloc) so that problem z's buffers
     // sit at problem 0's addresses + z * stride.  alloc_bytes counts what creation asked for (256-byte granules).
+    std::vector<void *> owned;      // every pointer cip_handle_alloc got from hipMalloc, first-use buffers included: what destruction frees
     char *arena = nullptr;
     size_t arena_cap = 0, arena_used = 0, alloc_bytes = 0;
     bool arena_overflow = false;

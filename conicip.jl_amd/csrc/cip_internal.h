@@ -22,6 +22,21 @@ void cip_set_error(const char *fmt, ...);
         }                                                                         \
     } while (0)
 
+// ---------------------------------------------------------------- device workspaces: one walk sizes and carves
+// The layout of a workspace is ONE function that takes its members from a CipLayout, in order.  Over the allocation the walk carves;
+// over a null base take() returns null and only counts, and bytes() is what to allocate -- sizing and carve cannot disagree.  An offset
+// is tracked, not a moving pointer: no arithmetic on null.  A member's size is rounded up to `granule` bytes (api.hip: packed layouts, 8).
+struct CipLayout {
+    char *base; size_t off = 0;
+    CipLayout(const void *b) : base((char *)b) {}          // (implicit: a layout function is called with the base pointer, or NULL)
+    template <typename T> T *take(size_t count, size_t granule = 256) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off += (count * sizeof(T) + granule - 1) / granule * granule;
+        return p;
+    }
+    size_t bytes() const { return off; }
+};
+
 // ---------------------------------------------------------------- environment switches (api.hip; INTEGRATION.md section 6 lists them)
 // The value of a CIP_* variable through atoi / atol / atof (garbage reads as 0), `dflt` when it is unset.  Range checks and
 // "read once" (a function-local static) are the call site's; cip_env_set: set to anything at all, "0" included.

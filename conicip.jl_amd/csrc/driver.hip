@@ -18,7 +18,7 @@
 
 using namespace cipdrv;
 
-size_t cip_driver_bytes(const cip_handle *h) { return sizeof(double) * driver_doubles(h->n, h->m, h->p); }
+size_t cip_driver_bytes(const cip_handle *h) { return Vectors().carve(nullptr, h->n, h->m, h->p); }
 
 int cipdrv::Loop::run(const double *const *c, const double *const *b, const double *const *d, const cip_options &o, cip_result *res,
                       double *trace, int trace_cap) {
@@ -33,7 +33,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
     if (cip_host_scratch(&hs)) { cip_set_error("interior-point loop: host scratch"); return CIP_E_HIP; }
     int rc;
 #define CK(x) do { if ((rc = (x)) != 0) return rc; } while (0)
-    CK(cip_zero(s, (long)driver_doubles(n, m, p), h->drv));
+    CK(cip_zero(s, (long)(cip_driver_bytes(h) / sizeof(double)), h->drv));
     std::vector<Norms> nm(B);
     for (int z = 0; z < B; ++z) {                   // problem z's vectors are problem 0's addresses + z * stride
         const size_t off = (size_t)cip_tl_bz.stride * z;

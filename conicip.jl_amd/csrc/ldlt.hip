@@ -157,8 +157,6 @@ int cip_prof_slot_end(int slot, hipStream_t s) {
     return p ? prof_event(p, s) : 0;
 }
 
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // solve block: largest of {1024, 512, 256, 128} that divides the (128-padded) order
 // Upper limit: process-wide knob (cip_set_solve_block_max / CIP_SOLVE_BLOCK, default 1024) or, when set, the calling
 // thread's override (lock-step batches create their handles with 256: in a batch a block step is one launch for all
@@ -205,51 +203,29 @@ static int solve_fused_for(int Npad, int Bs) {
 }
 
 // Layout: everything whose size depends on (Npad, solve block) only, then -- LAST -- the pre-multiplied neighbour blocks MT / PT of the
-// one-launch block steps.  `fused` is decided ONCE by the owner of the workspace and passed to both functions (round-5 advisor: each
-// used to read the process-wide mode for itself, so a cip_set_solve_fused between the two -- or between handle creation's sizing and
-// its carve -- placed MT / PT beyond the allocation).  fused < 0: by the current mode (cip_ldlt_ws_bytes only: the public sizing
-// call reserves MT / PT whenever the order has two solve blocks, whatever the mode, so that a caller-owned workspace fits every mode).
+// one-launch block steps.  Sizing and carve are the same walk (CipLayout); `fused` is decided ONCE by the owner of the workspace and
+// passed to both (round-5 advisor: each used to read the process-wide mode for itself, so a cip_set_solve_fused between the two -- or
+// between handle creation's sizing and its carve -- placed MT / PT beyond the allocation).  fused < 0 (the public sizing call): reserve
+// MT / PT whenever the order has two solve blocks, whatever the mode, so that a caller-owned workspace fits every mode.
 int cip_ldlt_fused_for(int Npad) { return solve_fused_for(Npad, cip_solve_block(Npad)); }
-size_t cip_ldlt_ws_bytes(int Npad, int fused) {
+static size_t ldlt_ws_layout(CipLayout L, int Npad, LdltWorkspace *ws, int fused) {
     const size_t nblk = Npad / CIP_NB;
-    size_t b = 0;
-    b += al256((size_t)Npad * wbuf_cols(Npad) * 8);       // Wbuf
-    b += al256(nblk * CIP_NB * CIP_NB * 8) * 2;          // Linv, LinvT
-    b += al256(nblk * 2048 * 8);                         // Xm
-    const int Bs = cip_solve_block(Npad);
-    const size_t nbk = Npad / Bs;
-    b += al256(nbk * (size_t)Bs * Bs * 8) * 2;           // X, XT
-    b += al256(nbk * (size_t)(Bs / 2) * (Bs / 2) * 8 + 256);   // Tt
-    b += al256((size_t)Npad * 8);                        // zbuf
-    b += al256((size_t)Npad * 8) * 3;                    // dinv, dvec, tmp
-    b += al256(64 + 12 * nblk);                          // info (16 ints) + a `ready`, a `stage` and a tile-queue counter per 128-block (fused panel launches)
-    if (fused < 0 ? nbk >= 2 : fused) b += al256(nbk * (size_t)Bs * Bs * 8) * 2;   // MT, PT
-    return b;
-}
-
-void cip_ldlt_ws_carve(void *base, int Npad, LdltWorkspace *ws, int fused) {
-    const size_t nblk = Npad / CIP_NB;
-    char *p = (char *)base;
-    ws->Wbuf = (double *)p;  p += al256((size_t)Npad * wbuf_cols(Npad) * 8);
-    ws->Linv = (double *)p;  p += al256(nblk * CIP_NB * CIP_NB * 8);
-    ws->LinvT = (double *)p; p += al256(nblk * CIP_NB * CIP_NB * 8);
-    ws->Xm = (double *)p;    p += al256(nblk * 2048 * 8);
     ws->Bs = cip_solve_block(Npad);
-    const size_t nbk = Npad / ws->Bs;
-    ws->X = (double *)p;     p += al256(nbk * (size_t)ws->Bs * ws->Bs * 8);
-    ws->XT = (double *)p;    p += al256(nbk * (size_t)ws->Bs * ws->Bs * 8);
-    ws->Tt = (double *)p;    p += al256(nbk * (size_t)(ws->Bs / 2) * (ws->Bs / 2) * 8 + 256);
-    ws->zbuf = (double *)p;  p += al256((size_t)Npad * 8);
-    ws->dinv = (double *)p;  p += al256((size_t)Npad * 8);
-    ws->dvec = (double *)p;  p += al256((size_t)Npad * 8);
-    ws->tmp = (double *)p;   p += al256((size_t)Npad * 8);
-    ws->info = (int *)p;     p += al256(64 + 12 * nblk);
-    ws->fused = (fused != 0 && nbk >= 2) ? 1 : 0;
-    ws->MT = ws->PT = nullptr;
-    if (ws->fused) {
-        ws->MT = (double *)p;  p += al256(nbk * (size_t)ws->Bs * ws->Bs * 8);
-        ws->PT = (double *)p;  p += al256(nbk * (size_t)ws->Bs * ws->Bs * 8);
-    }
+    const size_t nbk = Npad / ws->Bs, blk = nbk * (size_t)ws->Bs * ws->Bs, half = ws->Bs / 2;
+    ws->Wbuf = L.take<double>((size_t)Npad * wbuf_cols(Npad));
+    ws->Linv = L.take<double>(nblk * CIP_NB * CIP_NB); ws->LinvT = L.take<double>(nblk * CIP_NB * CIP_NB);
+    ws->Xm = L.take<double>(nblk * 2048);
+    ws->X = L.take<double>(blk); ws->XT = L.take<double>(blk);
+    ws->Tt = L.take<double>(nbk * half * half + 32);
+    ws->zbuf = L.take<double>(Npad); ws->dinv = L.take<double>(Npad); ws->dvec = L.take<double>(Npad); ws->tmp = L.take<double>(Npad);
+    ws->info = L.take<int>(16 + 3 * nblk);      // info (16 ints) + a `ready`, a `stage` and a tile-queue counter per 128-block (fused panel launches)
+    ws->fused = (fused != 0 && nbk >= 2) ? 1 : 0;     // (cip_ldlt_fused_for is 0 at one solve block)
+    ws->MT = ws->fused ? L.take<double>(blk) : nullptr; ws->PT = ws->fused ? L.take<double>(blk) : nullptr;
+    return L.bytes();
+}
+size_t cip_ldlt_ws_bytes(int Npad, int fused) { LdltWorkspace ws; return ldlt_ws_layout(nullptr, Npad, &ws, fused); }
+void cip_ldlt_ws_carve(void *base, int Npad, LdltWorkspace *ws, int fused) {
+    ldlt_ws_layout(base, Npad, ws, fused);
     ws->prof = nullptr;
     ws->lazyC = nullptr; ws->lazy_ld = 0; ws->lazy_diag = nullptr;
     ws->signs = PivotSigns{-1, 0, 0};

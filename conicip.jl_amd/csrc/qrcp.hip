@@ -231,19 +231,13 @@ struct QrWs {
     double *tau, *rdiag;        // min(len, cnt) each
     int *piv;                   // cnt
 };
-static size_t qr_up(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t qr_ws_bytes(int len, int cnt) {
+static size_t qr_ws_layout(CipLayout L, int len, int cnt, QrWs *w) {
     const size_t k = (size_t)(len < cnt ? len : cnt);
-    return qr_up(sizeof(int) * QR_FLAGS) + qr_up(sizeof(double) * (size_t)cnt) + 2 * qr_up(sizeof(double) * k) + qr_up(sizeof(int) * (size_t)cnt);
-}
-static char *qr_ws_carve(char *p, int len, int cnt, QrWs *w) {
-    const size_t k = (size_t)(len < cnt ? len : cnt);
-    w->flags = (int *)p; p += qr_up(sizeof(int) * QR_FLAGS);
-    w->norms = (double *)p; p += qr_up(sizeof(double) * (size_t)cnt);
-    w->tau = (double *)p; p += qr_up(sizeof(double) * k);
-    w->rdiag = (double *)p; p += qr_up(sizeof(double) * k);
-    w->piv = (int *)p; p += qr_up(sizeof(int) * (size_t)cnt);
-    return p;
+    w->flags = L.take<int>(QR_FLAGS);
+    w->norms = L.take<double>(cnt);
+    w->tau = L.take<double>(k); w->rdiag = L.take<double>(k);
+    w->piv = L.take<int>(cnt);
+    return L.bytes();
 }
 
 // The factorisation (len, cnt > 0).  tau: device, min(len, cnt) entries.  *k = steps done; *status != 0: non-finite entry.
@@ -274,7 +268,8 @@ static bool qr_dims_ok(int len, int cnt, int ld) { return len >= 0 && cnt >= 0 &
 
 extern "C" int cip_qrcp_workspace_bytes(int len, int cnt, size_t *bytes) {
     if (len < 0 || cnt < 0 || !bytes) { cip_set_error("cip_qrcp_workspace_bytes: len, cnt >= 0 and bytes non-NULL"); return CIP_E_INVALID; }
-    *bytes = qr_ws_bytes(len, cnt);
+    QrWs w;
+    *bytes = qr_ws_layout(nullptr, len, cnt, &w);
     return 0;
 }
 
@@ -293,7 +288,7 @@ extern "C" int cip_qrcp_dev(void *stream, double *M, int len, int cnt, int ld, d
     }
     hipStream_t s = (hipStream_t)stream;
     QrWs w;
-    qr_ws_carve((char *)workspace, len, cnt, &w);
+    qr_ws_layout(workspace, len, cnt, &w);
     int k = 0, status = 0;
     const int rc = qr_run(s, M, len, cnt, ld, stop, w, tau_dev ? tau_dev : w.tau, &k, &status);
     if (rc) return rc;
@@ -391,27 +386,22 @@ __global__ __launch_bounds__(1024) void k_im_absmax(const double *res, int cnt, 
 
 struct ImWs { QrWs qr; double *W; long ldw; double *bs, *y, *x, *z, *res, *scal; };
 static long im_ldw(int len) { return ((long)len + 1) & ~1L; }     // even: the working copy always takes the 16-byte accesses
-static size_t im_ws_bytes(int len, int cnt) {
+static size_t im_ws_layout(CipLayout L, int len, int cnt, ImWs *w) {
     const size_t k = (size_t)(len < cnt ? len : cnt);
-    return qr_ws_bytes(len, cnt) + qr_up(sizeof(double) * (size_t)im_ldw(len) * (size_t)cnt) + 2 * qr_up(sizeof(double) * (size_t)cnt) +
-           qr_up(sizeof(double) * k) + 2 * qr_up(sizeof(double) * (size_t)len) + qr_up(sizeof(double) * 8);
-}
-static void im_ws_carve(char *p, int len, int cnt, ImWs *w) {
-    const size_t k = (size_t)(len < cnt ? len : cnt);
-    p = qr_ws_carve(p, len, cnt, &w->qr);
+    L.take<char>(qr_ws_layout(L.base, len, cnt, &w->qr));          // the factorisation's workspace comes first
     w->ldw = im_ldw(len);
-    w->W = (double *)p; p += qr_up(sizeof(double) * (size_t)w->ldw * (size_t)cnt);
-    w->bs = (double *)p; p += qr_up(sizeof(double) * (size_t)cnt);
-    w->res = (double *)p; p += qr_up(sizeof(double) * (size_t)cnt);
-    w->y = (double *)p; p += qr_up(sizeof(double) * k);
-    w->x = (double *)p; p += qr_up(sizeof(double) * (size_t)len);
-    w->z = (double *)p; p += qr_up(sizeof(double) * (size_t)len);
-    w->scal = (double *)p;
+    w->W = L.take<double>((size_t)w->ldw * (size_t)cnt);
+    w->bs = L.take<double>(cnt); w->res = L.take<double>(cnt);
+    w->y = L.take<double>(k);
+    w->x = L.take<double>(len); w->z = L.take<double>(len);
+    w->scal = L.take<double>(8);
+    return L.bytes();
 }
 
 extern "C" int cip_imcols_workspace_bytes(int len, int cnt, size_t *bytes) {
     if (len < 0 || cnt < 0 || !bytes) { cip_set_error("cip_imcols_workspace_bytes: len, cnt >= 0 and bytes non-NULL"); return CIP_E_INVALID; }
-    *bytes = im_ws_bytes(len, cnt);
+    ImWs w;
+    *bytes = im_ws_layout(nullptr, len, cnt, &w);
     return 0;
 }
 
@@ -430,7 +420,7 @@ extern "C" int cip_imcols_dev(void *stream, const double *M, int len, int cnt, i
     if (empty) return 0;
     hipStream_t s = (hipStream_t)stream;
     ImWs w;
-    im_ws_carve((char *)workspace, len, cnt, &w);
+    im_ws_layout(workspace, len, cnt, &w);
     // scale = ||A||_F (src/preprocessor.jl:14)
     double fro = 0.0;
     hipLaunchKernelGGL(k_qr_init, dim3((unsigned)cnt), dim3(256), 0, s, M, len, (long)ld, w.qr.norms, (int *)nullptr);

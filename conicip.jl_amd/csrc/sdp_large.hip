@@ -39,20 +39,42 @@
 
 __device__ int g_lz_hist[40];           // k_lg_lanczos1: histogram of step counts (bins of 8)
 #define LG_NPAD 4
+// Who owns which words of LargeWs::vec (slots of rp doubles) and LargeWs::ctr (words): the one table; what it does not list is free.
+// Both regions are cleared whole: vec at creation, ctr by every NT scaling and every cooperative tridiagonalisation.
+enum {                                 // LG_V_SLOTS slots of rp doubles
+    LG_V_LAM = 0,                      // the singular values of the NT scaling
+    LG_V_DG = 1, LG_V_OF = 2,          // the tridiagonal of side 0: both tridiagonalisations and the side-0 certificate fallback
+    LG_V_XBUF = 3, LG_V_PBUF = 5,      // two slots each: xbuf (cooperative tridiagonalisation) / vbuf (stepped form), pbuf of both
+    LG_V_SCAL = 7,                     // the stepped form's scalars
+    LG_V_UNUSED = 8,
+    LG_V_DG1 = 9, LG_V_OF1 = 10,       // the tridiagonal of side 1: its certificate fallback
+    LG_V_CERT = 11, LG_V_SLOTS = 12    // doubles 2 side, 2 side + 1: the certificate pair of `side`; double 8, as unsigned: fallbacks taken
+};
+enum {                                 // LG_C_WORDS words
+    LG_C_BARRIER = 0,                  // words 0-7: grid-barrier counters (k_lg_tridiag counts in word 0)
+    LG_C_SWEEP = 8,                    // words 8-47: the Jacobi's sweep flags, one per sweep
+    LG_C_GIVEUP = 128,                 // the cooperative tridiagonalisation's give-up word
+    LG_C_STAT = 200, LG_C_GATE = 210, LG_C_WORDS = 256     // + side: stat of the Lanczos max-step, gate of its certificate's fallback
+};
 struct LargeWs {
     int rp = 0;                    // padded order (256 or 512)
     int chunk = 64;                // columns of A per batched congruence
     double *base = nullptr;        // one allocation
     double *Kz, *Ks, *Tz, *Ts, *G, *M1, *M2, *M3;      // rp x rp
     double *Rip;                   // nlarge x LG_NPAD x rp x rp: Rinv, Rinv', R, R' of every large cone, zero padded
-    double *vec;                   // 12 x rp: lam, dg, of, xbuf[2], pbuf, ...
+    double *vec;                   // LG_V_SLOTS x rp, addressed through the accessors below
+    double *slot(int v) const { return vec + (size_t)v * rp; }
+    double *dg(int side = 0) const { return slot(side ? LG_V_DG1 : LG_V_DG); }
+    double *of(int side = 0) const { return slot(side ? LG_V_OF1 : LG_V_OF); }
+    double *cert(int side) const { return slot(LG_V_CERT) + 2 * side; }
+    unsigned *fallbacks() const { return (unsigned *)(slot(LG_V_CERT) + 8); }
     double *batchX, *batchT;       // chunk x rp x rp each
     // mat(a_i) of every column of A, per large cone, built once per upload (A does not change between the factorisations of a
     // problem): round 4 -- the strided pass over A' was 0.38 ms of every factorisation at order 256, n = 1024
     double *amat = nullptr;        // nlarge x ncols x rp x rp (null when that exceeds 4 GB or the columns do not fit one batch)
     int ncols = 0;
     const double *amat_src[CIP_MAX_LARGE_S] = {};   // the A' the images were built from (null: not built)
-    unsigned *ctr;                 // barrier counters / sweep flags (256 words)
+    unsigned *ctr;                 // LG_C_WORDS words: barrier counters, sweep flags, gates (table above)
     // round 5: warm start of the one-sided Jacobi (see cip_sdp_large_nt): the right singular vectors of the previous NT scaling of
     // every large cone, and three work matrices
     double *Vw = nullptr;          // nlarge x rp x rp
@@ -61,7 +83,6 @@ struct LargeWs {
     unsigned long long *vstate = nullptr;   // device, 2 words per large cone: [0] = 1: the stored V may be used; [1]: max |V'V - I| (bit pattern) of the current call
     int *hflag = nullptr, *hflag_dev = nullptr;   // host-mapped: {sweep flag, Cholesky flags, sequence number} of the Jacobi's read-backs
     int hseq = 0;
-    void *ldl_z = nullptr, *ldl_s = nullptr;
     LdltWorkspace wz, ws;
     int xz_z = 0, xz_s = 0;        // the upper triangles of their block inverses have been zeroed (they stay zero)
     hipStream_t s2 = nullptr;      // the s-side max-step of a pair runs here, beside the v-side one on the handle's stream
@@ -287,7 +308,7 @@ __global__ __launch_bounds__(NT) void k_lg_jacobi(double *G, int rp, int bflags,
     const int ld = lg_pitch(rp);
     const int tpp = NT / b;                              // lanes per column pair (32 or 64); rp == EPL * tpp
     const int part = tid % tpp, pair = tid / tpp;
-    unsigned *sweepflag = ctr + 8;
+    unsigned *sweepflag = ctr + LG_C_SWEEP;
     // the host enqueues sweeps ahead of reading their flags; a sweep behind one that found nothing to rotate is a no-op
     if (step_sweep > 0 && __hip_atomic_load(sweepflag + step_sweep - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
     // rotation of LDS columns p, q; returns 0 / 1 (rotated, small) / 2 (rotated, cos^2 >= 1e-16)
@@ -569,14 +590,28 @@ __global__ __launch_bounds__(LG_T) void k_lg_sturm(const double *dgg, const doub
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 int cip_sdp_large_padded(int r) { return r <= 256 ? 256 : (r <= 512 ? 512 : (r <= 1024 ? 1024 : 2048)); }
+
+// The one device allocation, in order; sizing is the same walk over a null base.  The two LDL' workspaces come last.
+static size_t lg_ws_layout(CipLayout L, LargeWs *w, int nlarge, bool cache_mat) {
+    const size_t n2 = (size_t)w->rp * w->rp;
+    for (double **m : {&w->Kz, &w->Ks, &w->Tz, &w->Ts, &w->G, &w->M1, &w->M2, &w->M3, &w->G0, &w->W1, &w->W2}) *m = L.take<double>(n2);
+    w->Vw = L.take<double>(nlarge * n2);
+    w->Rip = L.take<double>(LG_NPAD * nlarge * n2);
+    w->vec = L.take<double>(LG_V_SLOTS * (size_t)w->rp);
+    w->batchX = L.take<double>(w->chunk * n2); w->batchT = L.take<double>(w->chunk * n2);
+    w->amat = cache_mat ? L.take<double>((size_t)nlarge * w->ncols * n2) : nullptr;
+    w->ctr = L.take<unsigned>(LG_C_WORDS);
+    w->vstate = L.take<unsigned long long>(2 * (size_t)nlarge);
+    for (LdltWorkspace *x : {&w->wz, &w->ws}) cip_ldlt_ws_carve(L.take<char>(cip_ldlt_ws_bytes(w->rp, 0)), w->rp, x, 0);
+    return L.bytes();
+}
 
 int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out) {
     LargeWs *w = new LargeWs();
     const int rp = cip_sdp_large_padded(rmax_large);
     w->rp = rp;
-    const size_t m2 = al256((size_t)rp * rp * 8);
+    const size_t m2 = (size_t)rp * rp * 8;
     // columns of A per batched congruence: all n of them when the two images fit 2 GB each (round 4: at order 256, n = 1024 the
     // 16 chunks of 64 columns were 64 launches of 512 tiles -- two workgroups per CU, 40 TFLOP/s -- now two launches), at least 16
     {
@@ -589,8 +624,6 @@ int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out) {
     }
     w->ncols = ncols;
     const bool cache_mat = ncols > 0 && w->chunk >= ncols && (size_t)nlarge * ncols * m2 <= ((size_t)4 << 30);
-    size_t bytes = (cache_mat ? (size_t)nlarge * ncols * m2 : 0) + 8 * m2 + (3 + (size_t)nlarge) * m2 + LG_NPAD * (size_t)nlarge * m2 + al256(12 * (size_t)rp * 8) + 2 * (size_t)w->chunk * m2 + al256(1024) +
-                   al256(16 * (size_t)nlarge);
     // the two LDL' workspaces: solve block = the whole padded matrix (X = inv(L_unit) in one piece: the "triangular solves" here are
     // GEMMs with it), also at order 2048 (the calling thread's solve-block limit for the sizing and the carve)
     struct SolveBlockOverride {          // restores the thread's limit on every way out
@@ -598,32 +631,17 @@ int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out) {
         explicit SolveBlockOverride(int b) : saved(cip_tl_solve_block_max) { cip_tl_solve_block_max = b; }
         ~SolveBlockOverride() { cip_tl_solve_block_max = saved; }
     } whole_matrix_block(rp);
-    bytes += 2 * al256(cip_ldlt_ws_bytes(rp, 0));
+    const size_t bytes = lg_ws_layout(nullptr, w, nlarge, cache_mat);
     if (hipMalloc((void **)&w->base, bytes) != hipSuccess) { cip_set_error("large S cone workspace: hipMalloc of %zu bytes failed", bytes); delete w; return -3; }
-    char *p = (char *)w->base;
-    double **mats[8] = {&w->Kz, &w->Ks, &w->Tz, &w->Ts, &w->G, &w->M1, &w->M2, &w->M3};
-    for (auto m : mats) { *m = (double *)p; p += m2; }
-    w->G0 = (double *)p; p += m2; w->W1 = (double *)p; p += m2; w->W2 = (double *)p; p += m2;
-    w->Vw = (double *)p; p += (size_t)nlarge * m2;
-    w->Rip = (double *)p; p += LG_NPAD * (size_t)nlarge * m2;
-    w->vec = (double *)p; p += al256(12 * (size_t)rp * 8);
-    w->batchX = (double *)p; p += (size_t)w->chunk * m2;
-    w->batchT = (double *)p; p += (size_t)w->chunk * m2;
-    if (cache_mat) { w->amat = (double *)p; p += (size_t)nlarge * ncols * m2; }
-    w->ctr = (unsigned *)p; p += al256(1024);
-    CIP_HIP_CHECK(hipMemset(w->ctr, 0, 1024));
-    w->vstate = (unsigned long long *)p; p += al256(16 * (size_t)nlarge);
+    lg_ws_layout(w->base, w, nlarge, cache_mat);
+    CIP_HIP_CHECK(hipMemset(w->ctr, 0, LG_C_WORDS * sizeof(unsigned)));
     CIP_HIP_CHECK(hipMemset(w->vstate, 0, 16 * (size_t)nlarge));
     if (hipHostMalloc((void **)&w->hflag, 8 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&w->hflag_dev, w->hflag, 0) != hipSuccess) {
         cip_set_error("large S cone workspace: host-mapped flag words"); if (w->hflag) (void)hipHostFree(w->hflag); (void)hipFree(w->base); delete w; return -3;
     }
     memset(w->hflag, 0, 8 * sizeof(int));
-    CIP_HIP_CHECK(hipMemset(w->vec, 0, 12 * (size_t)rp * 8));
-    w->ldl_z = p; p += al256(cip_ldlt_ws_bytes(rp, 0));
-    w->ldl_s = p;
-    cip_ldlt_ws_carve(w->ldl_z, rp, &w->wz, 0);
-    cip_ldlt_ws_carve(w->ldl_s, rp, &w->ws, 0);
+    CIP_HIP_CHECK(hipMemset(w->vec, 0, LG_V_SLOTS * (size_t)rp * sizeof(double)));
     w->wz.signs = w->ws.signs = PivotSigns{0, rp, rp};       // a Cholesky in disguise: every pivot must be positive
     w->wz.x_zeroed = &w->xz_z; w->ws.x_zeroed = &w->xz_s;
     // the three-launch panel chain: no in-launch wait that could give up (the consumers of these factors -- NT scaling, inertia
@@ -1267,7 +1285,7 @@ __global__ __launch_bounds__(256) void k_tg_rank2(double *A, int lda, int r, int
 }
 static int lg_tridiag_stepped(hipStream_t s, LargeWs *w, const double *M, const double *dscale, int r, double *work) {
     const int rp = w->rp;
-    double *dg = w->vec + 1 * rp, *of = w->vec + 2 * rp, *vbuf = w->vec + 3 * rp, *pbuf = w->vec + 5 * rp, *scal = w->vec + 7 * rp;
+    double *dg = w->dg(), *of = w->of(), *vbuf = w->slot(LG_V_XBUF), *pbuf = w->slot(LG_V_PBUF), *scal = w->slot(LG_V_SCAL);
     hipLaunchKernelGGL(k_tg_init, lg_grid((long)r * r), dim3(256), 0, s, M, rp, dscale, r, work, rp);
     for (int k = 0; k + 1 < r; ++k) {
         const int m = r - k - 1;
@@ -1287,7 +1305,7 @@ static int lg_tridiag(hipStream_t s, LargeWs *w, const double *M, const double *
     if (r <= 256) {
         const size_t shm1 = T1_LDS_DOUBLES * sizeof(double);
         if ((rc = lg_set_attr((const void *)k_lg_tridiag1, shm1))) return rc;
-        hipLaunchKernelGGL(k_lg_tridiag1, dim3(1), dim3(512), shm1, s, M, w->rp, dscale, r, w->vec + 1 * w->rp, w->vec + 2 * w->rp, (const int *)nullptr);
+        hipLaunchKernelGGL(k_lg_tridiag1, dim3(1), dim3(512), shm1, s, M, w->rp, dscale, r, w->dg(), w->of(), (const int *)nullptr);
         CIP_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -1296,10 +1314,10 @@ static int lg_tridiag(hipStream_t s, LargeWs *w, const double *M, const double *
     const int nwg = (r + slab - 1) / slab;
     const size_t shm = ((size_t)slab * (r | 1) + 3 * (size_t)r + 64) * sizeof(double);
     if ((rc = lg_set_attr((const void *)k_lg_tridiag, shm))) return rc;
-    CIP_HIP_CHECK(hipMemsetAsync(w->ctr, 0, 1024, s));
-    double *dg = w->vec + 1 * w->rp, *of = w->vec + 2 * w->rp, *xbuf = w->vec + 3 * w->rp, *pbuf = w->vec + 5 * w->rp;   // 2 x rp each
-    hipLaunchKernelGGL(k_lg_tridiag, dim3(nwg), dim3(LG_T), shm, s, M, w->rp, dscale, r, dg, of, xbuf, pbuf, w->ctr,
-                       (int *)(w->ctr + 128), slab);
+    CIP_HIP_CHECK(hipMemsetAsync(w->ctr, 0, LG_C_WORDS * sizeof(unsigned), s));
+    double *xbuf = w->slot(LG_V_XBUF), *pbuf = w->slot(LG_V_PBUF);   // 2 x rp each
+    hipLaunchKernelGGL(k_lg_tridiag, dim3(nwg), dim3(LG_T), shm, s, M, w->rp, dscale, r, w->dg(), w->of(), xbuf, pbuf, w->ctr + LG_C_BARRIER,
+                       (int *)(w->ctr + LG_C_GIVEUP), slab);
     CIP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1408,7 +1426,7 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
         // L2 + launch boundary) and their number doubles as the blocks halve), 16 at order 512 (16 workgroups), 8 at order 1024.
         const int b = rp > 1024 ? 4 : rp > 512 ? 8 : rp > 256 ? 16 : 8;       // order 2048: two blocks of 4 columns are a CU's LDS
         const size_t shm = (size_t)2 * b * lg_pitch(rp) * sizeof(double);
-        CIP_HIP_CHECK(hipMemsetAsync(w->ctr, 0, 1024, s));
+        CIP_HIP_CHECK(hipMemsetAsync(w->ctr, 0, LG_C_WORDS * sizeof(unsigned), s));
         if ((rc = cip_prof_slot_begin(CIP_PROF_JACOBI, s, 0.0))) return rc;
         // ONE LAUNCH PER PHASE (round 5, second session; the only form since round 6): the pairs inside the blocks, then each round of
         // the tournament over blocks, the launch boundary in place of a grid barrier.  0 differing results in 11 500 repeated scalings
@@ -1427,7 +1445,7 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
                     hipLaunchKernelGGL(kern, dim3(m / 2), dim3(nthreads), lds, s, w->G, rp, bb | (sweep << 16) | (step << 22), w->ctr);
                 if (sweep < first_check) continue;
                 w->hseq = (w->hseq == 0x7fffffff) ? 1 : w->hseq + 1;
-                hipLaunchKernelGGL(k_lg_pubflag, dim3(1), dim3(64), 0, s, (const unsigned *)(w->ctr + 8 + sweep), (const int *)w->wz.info, (const int *)w->ws.info, w->hflag_dev, w->hseq);
+                hipLaunchKernelGGL(k_lg_pubflag, dim3(1), dim3(64), 0, s, (const unsigned *)(w->ctr + LG_C_SWEEP + sweep), (const int *)w->wz.info, (const int *)w->ws.info, w->hflag_dev, w->hseq);
                 CIP_HIP_CHECK(hipGetLastError());
                 volatile int *seqp = w->hflag + 2;
                 for (long spin = 0; __atomic_load_n(seqp, __ATOMIC_ACQUIRE) != w->hseq; ++spin) {
@@ -1464,10 +1482,10 @@ int cip_sdp_large_nt(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, cons
         CIP_HIP_CHECK(hipMemcpyAsync(hc, w->ctr, sizeof(hc), hipMemcpyDeviceToHost, s));
         CIP_HIP_CHECK(hipStreamSynchronize(s));
         int sweeps = 0;
-        for (int q = 8; q < 48; ++q) if (hc[q]) ++sweeps;
+        for (int q = LG_C_SWEEP; q < LG_C_SWEEP + 40; ++q) if (hc[q]) ++sweeps;
         fprintf(stderr, "[lg] jacobi: %d sweeps with a rotation above cos^2 = 1e-16%s\n", sweeps, left_cone ? " (iterate outside the cone)" : "");
     }
-    double *lam = w->vec;
+    double *lam = w->slot(LG_V_LAM);
     hipLaunchKernelGGL(k_lg_colnorm, dim3((rp + 3) / 4), dim3(256), 0, s, w->G, lam, rp);
     {                                                                                                                       // V = G0' (A_f Sigma^-2) for the next call
         hipLaunchKernelGGL(k_lg_transpose, tg, dim3(256), 0, s, (const double *)w->G, w->W1, rp, (const double *)lam);        // (A_f Sigma^-2)'
@@ -1524,7 +1542,9 @@ int cip_sdp_large_lanczos(int on) {
 }
 // The two max-steps of a pair (v side, s side: src/ConicIP.jl:708-709, :881-882, :927-928) are independent: side 1 works in the
 // NT scaling's s-side buffers (Ks, its LDL' workspace, Tz / Ts / G as M1 / M2 / M3 -- all idle between scalings) on a second
-// stream.  Orders <= 256 only (the cooperative tridiagonalisation above that shares `vec` and `ctr`).
+// stream.  Orders <= 256 with the Lanczos form only: there each side has its own stat / gate words, certificate pair and fallback dg / of.
+// The tridiagonalisations that serve every other case have ONE set of vec slots 1-7 (dg, of, xbuf / vbuf, pbuf, scal), and the cooperative
+// one of orders 257 ... 1024 clears all of ctr and counts its barrier in word 0: two of them side by side would overwrite each other.
 bool cip_sdp_large_pairable(const LargeWs *w) { return w && w->rp <= 256 && cip_sdp_large_lanczos(-1); }
 int cip_sdp_large_fork(hipStream_t s, LargeWs *w, hipStream_t *s2) {
     if (!w->s2) {
@@ -1579,15 +1599,15 @@ static int lg_certify(hipStream_t s, LargeWs *w, const double *M3, const double 
     const int rp = w->rp;
     const long n2 = (long)rp * rp;
     int rc;
-    const double *cert = w->vec + 11 * rp + 2 * side;
-    int *gate = (int *)(w->ctr + 210 + side);
+    const double *cert = w->cert(side);
+    int *gate = (int *)(w->ctr + LG_C_GATE + side);
     hipLaunchKernelGGL(k_lg_cert_build, lg_grid(n2), dim3(256), 0, s, M3, rp, dscale, r, rp, want_max, cert, M2, M1);
     LdltWorkspace wc = wx;
     wc.no_prep = 1; wc.lazyC = nullptr; wc.prof = nullptr;
     if ((rc = cip_ldlt_factor(s, M2, rp, rp, wc))) return rc;
-    hipLaunchKernelGGL(k_lg_cert_check, dim3(1), dim3(64), 0, s, (const int *)wc.info, gate, (unsigned *)(w->vec + 11 * rp + 8));      // (w->ctr is cleared by every NT scaling)
+    hipLaunchKernelGGL(k_lg_cert_check, dim3(1), dim3(64), 0, s, (const int *)wc.info, gate, w->fallbacks());      // (w->ctr is cleared by every NT scaling)
     // the fallback (one workgroup each, at once back unless the gate is up): side 1 of a pair has its own d / e vectors
-    double *dg = w->vec + (side ? 9 : 1) * rp, *of = w->vec + (side ? 10 : 2) * rp;
+    double *dg = w->dg(side), *of = w->of(side);
     const size_t shm1 = T1_LDS_DOUBLES * sizeof(double);
     if ((rc = lg_set_attr((const void *)k_lg_tridiag1, shm1))) return rc;
     hipLaunchKernelGGL(k_lg_tridiag1, dim3(1), dim3(512), shm1, s, (const double *)M1, rp, (const double *)nullptr, r, dg, of, (const int *)gate);
@@ -1597,7 +1617,7 @@ static int lg_certify(hipStream_t s, LargeWs *w, const double *M3, const double 
 }
 int cip_sdp_large_cert_stats(hipStream_t s, LargeWs *w, int *out2) {
     unsigned c = 0;
-    if (w) { CIP_HIP_CHECK(hipMemcpyAsync(&c, w->vec + 11 * w->rp + 8, sizeof(c), hipMemcpyDeviceToHost, s)); CIP_HIP_CHECK(hipStreamSynchronize(s)); }
+    if (w) { CIP_HIP_CHECK(hipMemcpyAsync(&c, w->fallbacks(), sizeof(c), hipMemcpyDeviceToHost, s)); CIP_HIP_CHECK(hipStreamSynchronize(s)); }
     out2[0] = (int)c; out2[1] = 0;
     return 0;
 }
@@ -1607,14 +1627,14 @@ int cip_sdp_large_maxstep(hipStream_t s, LargeWs *w, const ConeDesc &cd, const d
     const int r = cd.r, rp = w->rp;
     const long n2 = (long)rp * rp;
     int rc;
-    double *dg = w->vec + 1 * rp, *of = w->vec + 2 * rp;
+    double *dg = w->dg(), *of = w->of();      // (side 0's also for side 1: no pair without the Lanczos form)
     double *const Kx = side ? w->Ks : w->Kz, *const M1 = side ? w->Tz : w->M1, *const M2 = side ? w->Ts : w->M2, *const M3 = side ? w->G : w->M3;
     LdltWorkspace &wx = side ? w->ws : w->wz;
-    int *const stat = (int *)(w->ctr + 200 + side);
+    int *const stat = (int *)(w->ctr + LG_C_STAT + side);
     // CIP_LG_LANCZOS=0: the full tridiagonalisation + Sturm multisection at every order (A/B runs, tests)
     const int lzmode = cip_sdp_large_lanczos(-1);
     const bool lz = lzmode && r <= 256;
-    double *const cert = (lz && lzmode >= 2) ? w->vec + 11 * rp + 2 * side : nullptr;          // mode 2: + inertia certificate
+    double *const cert = (lz && lzmode >= 2) ? w->cert(side) : nullptr;          // mode 2: + inertia certificate
     const double cert_tol = lzmode == 3 ? -1e-3 : 1e-9;      // mode 3 (self-test): the bound on the WRONG side of theta -- every certificate fails, every verdict comes from the fallback
     if (lz && (rc = lg_set_attr((const void *)k_lg_lanczos1, LZ_LDS_DOUBLES * sizeof(double)))) return rc;
     if (!d) {                                                                       // maxstep_sdc(x, nothing) :295-303

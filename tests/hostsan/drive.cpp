@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE: drives the product's host control plane (libcipkkt built host-only under ASan + UBSan or TSan, linked against
 // tests/hostsan/fake_hip.cpp) through the C ABI of include/cipkkt.h:
-//   1. the plugin levels on one handle (create, identity scaling, factor, check, host-pointer solves, packed scaling, destroy), dense
-//      and CSR A, p = 0 and p > 0, both routes;
+//   1. the plugin levels on one handle (create, identity scaling, factor, check, host-pointer solves, 65 right-hand sides at once, the
+//      refined solves of a regularised factor, packed scaling, destroy), dense and CSR A, p = 0 and p > 0, both routes;
 //   2. the native loop (cip_conicip) on a handle, with a trace buffer;
 //   3. cip_conicip_mixed on a batch built to hit every branch of the binning: 65 problems of one shape (a lock-step group of 64 and a
 //      group of ONE -- round 4's NULL write lived there), CSR problems of equal shape but different nnz, problems with p > 0, a
@@ -90,6 +90,18 @@ static void plugin_levels(const Prob &P) {
     REQUIRE(cip_solve3x3(h, x.data(), y.data(), z.data(), dx.data(), dy.data(), dz.data()) == CIP_OK);
     if (P.route == CIP_ROUTE_SCHUR) REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_OK);
     else REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_E_UNSUPPORTED);
+    {   // 65 right-hand sides: a full chunk and a chunk of one through the handle's many-column buffers and their host staging
+        const int k = 65;
+        std::vector<double> X((size_t)P.n * k, 1.0), Y(y.size() * k, 0.5), Z((size_t)P.m * k, 0.25), DX(X.size()), DY(Y.size()), DZ(Z.size());
+        REQUIRE(cip_solve3x3_many(h, k, X.data(), Y.data(), Z.data(), DX.data(), DY.data(), DZ.data()) == CIP_OK);
+    }
+    // a regularised factor: the refined solves carve the handle's refinement buffers on first use
+    REQUIRE(cip_set_regularization(h, 1e-13, 0) == CIP_OK);
+    REQUIRE(cip_factor(h) == CIP_OK);
+    REQUIRE(cip_solve3x3(h, x.data(), y.data(), z.data(), dx.data(), dy.data(), dz.data()) == CIP_OK);
+    if (P.route == CIP_ROUTE_SCHUR) REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_OK);
+    REQUIRE(cip_set_regularization(h, 0.0, 1) == CIP_OK);
+    REQUIRE(cip_factor(h) == CIP_OK);
     const size_t len = cip_scaling_packed_len(h);
     std::vector<double> F(len ? len : 1);
     REQUIRE(cip_get_scaling_packed(h, F.data()) == CIP_OK);

@@ -204,6 +204,43 @@ def test_ldlt_standalone_at_every_leading_dimension(lib, N, quasi):
             assert torch.equal(_bits(x), first[1]), "ld=%d: another solution than at ld=N" % ld
 
 
+@pytest.mark.parametrize("mode", [0, 2], ids=["two_launches_per_step", "one_launch_per_step"])
+@pytest.mark.parametrize("N", [256, 384])
+def test_ldlt_standalone_stays_inside_the_advertised_workspace(lib, N, mode):
+    """cip_ldlt_factor_dev / cip_ldlt_solve_dev on one buffer of exactly cip_ldlt_workspace_bytes plus a 4096-byte tail of 0xA5, at one
+    solve block (256) and at three blocks of 128 (384: MT / PT are part of the layout, and in use under cip_set_solve_fused(2)): the
+    tail keeps its bytes -- no member of the layout lies beyond the advertised size -- and factor and solve meet the bounds of
+    test_ldlt_standalone_at_every_leading_dimension."""
+    from cipkkt import _lib as L
+    Kmat = _sym_dev(N, 900 + N, N // 5)
+    nbytes = C.c_size_t()
+    L.check(lib.cip_ldlt_workspace_bytes(N, C.byref(nbytes)))
+    ws = torch.zeros(nbytes.value + 4096, dtype=torch.uint8, device="cuda")
+    ws[nbytes.value:] = 0xA5
+    g = torch.Generator(device="cuda")
+    g.manual_seed(N + 2)
+    rhs0 = torch.randn(N, generator=g, dtype=torch.float64, device="cuda")
+    buf, x, info = Kmat.clone(), rhs0.clone(), C.c_int(-1)         # symmetric: its row-major image is column-major K
+    prev = lib.cip_set_solve_fused(mode)
+    try:
+        L.check(lib.cip_ldlt_factor_dev(None, buf.data_ptr(), N, N, ws.data_ptr(), C.byref(info)))
+        L.check(lib.cip_ldlt_solve_dev(None, buf.data_ptr(), N, N, ws.data_ptr(), x.data_ptr()))
+        torch.cuda.synchronize()
+    finally:
+        lib.cip_set_solve_fused(prev)
+    assert info.value == 0
+    assert bool((ws[nbytes.value:] == 0xA5).all()), "a write beyond the advertised workspace"
+    F = buf.t()
+    Lf = torch.tril(F, -1) + torch.eye(N, dtype=torch.float64, device="cuda")
+    D = torch.diagonal(F)
+    err = float(torch.tril((Lf * D[None, :]) @ Lf.t() - Kmat).abs().max() / Kmat.abs().max())
+    assert err < 1e-13, "||L D L' - K|| / ||K|| = %g" % err
+    n = N - N // 5
+    assert bool((D[:n] > 0).all()) and bool((D[n:] < 0).all())
+    res = float(torch.linalg.norm(Kmat @ x - rhs0) / (torch.linalg.matrix_norm(Kmat, 2) * torch.linalg.norm(x)))
+    assert res < 1e-14, "normwise backward error of the solve = %g" % res
+
+
 @pytest.mark.parametrize("alpha", [0.5, -3.0])
 @pytest.mark.parametrize("lower", [0, 1])
 def test_gemm_nt_at_wider_leading_dimensions(lib, alpha, lower):

@@ -188,6 +188,50 @@ def test_padding_rows_are_never_touched_and_do_not_change_the_bits(shape):
     assert np.array_equal(piv0, piv1)
 
 
+@pytest.mark.parametrize("ln,cnt", [(5, 3), (3, 5)])
+def test_the_entry_points_stay_inside_their_advertised_workspaces(ln, cnt):
+    """cip_qrcp_dev and cip_imcols_dev on one buffer of exactly cip_*_workspace_bytes plus a 4096-byte tail of 0xA5 (the workspace
+    itself starts as 0xA5 too): the tail keeps its bytes -- no member of either layout lies beyond the advertised size, at len > cnt
+    and at len < cnt (min(len, cnt) sizes tau / rdiag / y) -- and the results pass the checks of test_reconstruction and
+    test_imcols_hip_properties."""
+    import torch
+    import cipkkt
+    from cipkkt import _lib as L
+    lib = L.load()
+    kmax = min(ln, cnt)
+    M0 = lowrank(ln, cnt, kmax)
+
+    def guarded(size_fn):
+        nb = C.c_size_t()
+        assert size_fn(ln, cnt, C.byref(nb)) == 0
+        return torch.full((nb.value + 4096,), 0xA5, dtype=torch.uint8, device="cuda"), nb.value
+
+    ws, nb = guarded(lib.cip_qrcp_workspace_bytes)
+    dev = torch.from_numpy(np.ascontiguousarray(M0.T)).cuda()
+    tau = torch.zeros(kmax, dtype=torch.float64, device="cuda")
+    piv, rdiag, k = np.full(cnt, -1, dtype=np.int32), np.zeros(kmax), C.c_int(-1)
+    rc = lib.cip_qrcp_dev(None, dev.data_ptr(), ln, cnt, ln, 0.0, ws.data_ptr(), tau.data_ptr(), piv.ctypes.data_as(L.c_int_p),
+                          rdiag.ctypes.data_as(L.c_double_p), C.byref(k))
+    torch.cuda.synchronize()
+    assert rc == 0 and bool((ws[nb:] == 0xA5).all())
+    assert k.value == kmax and sorted(piv) == list(range(cnt))
+    assert recon_error(dev.cpu().numpy().T, tau.cpu().numpy(), kmax, M0, piv) <= 8 * max(scipy_error(M0), U)
+
+    A = np.ascontiguousarray(M0.T)                                 # cnt rows of length len, rank min(len, cnt)
+    b = A @ np.random.default_rng(ln).standard_normal(ln)
+    ws, nb = guarded(lib.cip_imcols_workspace_bytes)
+    rows, nrows, ok = np.zeros(cnt, dtype=np.int32), C.c_int(0), C.c_int(0)
+    Ad, bd = torch.from_numpy(A).cuda(), torch.from_numpy(b).cuda()
+    rc = lib.cip_imcols_dev(None, Ad.data_ptr(), ln, cnt, ln, bd.data_ptr(), 1e-8, ws.data_ptr(), rows.ctypes.data_as(L.c_int_p),
+                            C.byref(nrows), C.byref(ok), None)
+    torch.cuda.synchronize()
+    assert rc == 0 and bool((ws[nb:] == 0xA5).all())
+    got = [int(i) for i in rows[:nrows.value]]
+    assert ok.value == 1 and len(got) == kmax == np.linalg.matrix_rank(A[got]) and got == sorted(set(got))
+    want = cipkkt.imcols(A, b)
+    assert (len(got), True) == (len(want[0]), want[1])
+
+
 @pytest.mark.parametrize("shape", [(517, 130, 70), (130, 1100, 130)], ids=IDS)
 def test_two_runs_give_identical_bits(shape):
     M0 = lowrank(*shape)
