@@ -65,14 +65,9 @@ static int debug_poison(void *p, size_t bytes) {
     CIP_HIP_CHECK(hipDeviceSynchronize());
     return 0;
 }
+// A device allocation of the handle's own: its block (create_impl), or a buffer of first use
 int cip_handle_alloc(cip_handle *h, void **out, size_t bytes) {
     if (bytes == 0) bytes = 256;
-    const size_t b = (bytes + 255) & ~(size_t)255;
-    h->alloc_bytes += b;
-    if (h->arena) {
-        if (h->arena_used + b <= h->arena_cap) { *out = h->arena + h->arena_used; h->arena_used += b; return debug_poison(*out, b); }
-        h->arena_overflow = true;                  // falls back to its own allocation: the slab layout is broken
-    }
     hipError_t e = hipMalloc(out, bytes);
     if (e == hipErrorOutOfMemory) {
         // the lock-step arena of an earlier batch (several GB, kept for the next one) may be what is in the way: give it back, once
@@ -81,7 +76,7 @@ int cip_handle_alloc(cip_handle *h, void **out, size_t bytes) {
         e = hipMalloc(out, bytes);
     }
     CIP_HIP_CHECK(e);
-    h->owned.push_back(*out);                      // (a piece of the arena is not the handle's to free)
+    h->owned.push_back(*out);
     return debug_poison(*out, bytes);
 }
 #define DMALLOC(ptr, bytes)                                                        \
@@ -107,6 +102,13 @@ struct RefView { Vec3 rhs, res, cor; };
 static size_t ref_layout(CipLayout L, const cip_handle *h, RefView *v) {
     for (Vec3 *b : {&v->rhs, &v->res, &v->cor}) { *b = take3(L, h); L.take<double>(8, 8); }
     return L.bytes();
+}
+// what the refined solves of a regularised factor allocate on first use; a lock-step group that may regularise has them in its
+// handles' slabs instead (handle_layout: CIP_EXTRA_REFINE)
+static int alloc_refine_buffers(cip_handle *h) {
+    if (!h->ref) { RefView v; DMALLOC(h->ref, ref_layout(nullptr, h, &v)); }
+    if (!h->c2x2 && h->m > 0 && h->route == CIP_ROUTE_SCHUR) DMALLOC(h->c2x2, sizeof(double) * h->m);
+    return 0;
 }
 // h->many, CIP_MANY_CHUNK columns each: the Npad-row right-hand sides R, the m-row blocks T and U of the Schur route, the sweeps' scratch S
 struct ManyView { double *R, *T, *U, *S; };
@@ -337,7 +339,11 @@ static int upload_problem(cip_handle *h, const cip_problem *pr) {
     return 0;
 }
 
-static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = true) {
+// ---- level 1 in three parts: the plan (host), the layout of the device block (one walk sizes it, one carves it), the fill
+// Plan: argument checks, the cone and work-item tables and their index lists, padded sizes, what the problem's form selects (route,
+// dense / CSR Q and A, split-K images) and the counts the layout needs.  Nothing is allocated on the device; the one thing read from
+// it is the nnz of a CSR A whose row pointers live there.
+static int handle_plan(const cip_problem *pr, cip_handle *h) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         cip_set_error("no HIP device available (libcipkkt has no CPU fallback)");
@@ -360,13 +366,12 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
     }
     h->n = n; h->m = m; h->p = p; h->ncones = pr->ncones; h->route = pr->route;
     const bool dev = (pr->flags & CIP_FLAG_DEVICE_PTRS) != 0;
-    hipStream_t s = h->stream;   // default (null) stream until cip_set_stream
 
     // ---- cones
     int off = 0, nq = 0;
     size_t soff = 0;
     bool has_S = false;
-    std::vector<int> sidx;
+    std::vector<int> &sidx = h->st_sidx;
     int rmax = 0, kmax = 0;
     for (int c = 0; c < pr->ncones; ++c) {
         ConeDesc cd = {};
@@ -425,74 +430,28 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
         h->mS = ao; h->mSpad = rup(ao, CIP_KT);
     }
     h->nq = nq; h->nqpad = rup(nq > 0 ? nq : 1, CIP_KT);
-    h->cs.nbigq = 0; h->cs.d_bigq = nullptr;
-    h->st_bigq.clear();
-    for (size_t it = 0; it < h->h_items.size(); ++it) {
-        const ConeDesc &cd = h->h_cones[h->h_items[it].cone];
-        if (cd.type == CIP_CONE_Q && h->h_items[it].width == 0) h->st_bigq.push_back((int)it);
+    for (size_t it = 0; it < h->h_items.size(); ++it) {       // index lists: R items, large Q cones (one item each), packs of small Q cones
+        const int type = h->h_cones[h->h_items[it].cone].type;
+        if (type == CIP_CONE_R) h->st_ritems.push_back((int)it);
+        else if (type == CIP_CONE_Q) (h->h_items[it].width == 0 ? h->st_bigq : h->st_packq).push_back((int)it);
     }
-    h->cs.nbigq = (int)h->st_bigq.size();
-    h->st_ritems.clear();
-    for (size_t it = 0; it < h->h_items.size(); ++it)
-        if (h->h_cones[h->h_items[it].cone].type == CIP_CONE_R) h->st_ritems.push_back((int)it);
-    h->cs.nritems = (int)h->st_ritems.size(); h->cs.d_ritems = nullptr;
-    h->st_packq.clear();
-    for (size_t it = 0; it < h->h_items.size(); ++it)
-        if (h->h_cones[h->h_items[it].cone].type == CIP_CONE_Q && h->h_items[it].width != 0) h->st_packq.push_back((int)it);
-    h->cs.npackq = (int)h->st_packq.size(); h->cs.d_packq = nullptr;
-    if (h->cs.npackq > 0) {
-        DMALLOC(h->cs.d_packq, sizeof(int) * h->st_packq.size());
-        CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_packq, h->st_packq.data(), sizeof(int) * h->st_packq.size(), hipMemcpyHostToDevice, s));
-    }
-    if (h->cs.nritems > 0) {
-        DMALLOC(h->cs.d_ritems, sizeof(int) * h->st_ritems.size());
-        CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_ritems, h->st_ritems.data(), sizeof(int) * h->st_ritems.size(), hipMemcpyHostToDevice, s));
-    }
-    if (h->cs.nbigq > 0) {
-        DMALLOC(h->cs.d_bigq, sizeof(int) * h->st_bigq.size());
-        CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_bigq, h->st_bigq.data(), sizeof(int) * h->st_bigq.size(), hipMemcpyHostToDevice, s));
-    }
+    h->cs.nbigq = (int)h->st_bigq.size(); h->cs.nritems = (int)h->st_ritems.size(); h->cs.npackq = (int)h->st_packq.size();
     h->cs.ncones = pr->ncones; h->cs.nitems = (int)h->h_items.size(); h->cs.nslots = nslots; h->cs.m = m; h->cs.scal_len = soff; h->cs.has_S = has_S;
-    DMALLOC(h->cs.d_cones, sizeof(ConeDesc) * h->h_cones.size());
-    DMALLOC(h->cs.d_items, sizeof(WorkItem) * h->h_items.size());
-    DMALLOC(h->cs.d_scal, sizeof(double) * soff);
-    DMALLOC(h->cs.d_partial, sizeof(double) * 2 * (nslots + 1));      // two sets: the pair of max-steps (cip_cones_maxstep2)
-    DMALLOC(h->cs.d_scalar, sizeof(double) * 8);
     h->cs.ns = (int)sidx.size(); h->cs.rmax = rmax; h->cs.kmax = kmax;
-    h->cs.ns_small = 0; h->cs.nlarge = 0; h->cs.lg = nullptr; h->cs.d_sidx_small = nullptr;
+    h->cs.ns_small = 0; h->cs.nlarge = 0;
     h->cs.h_cones = h->h_cones.data();
     if (has_S) {
         std::vector<int> &small = h->st_small;
-        small.clear();
-        int rmax_large = 0;
         for (int c : sidx) {
             if (h->h_cones[c].r >= CIP_LARGE_S_MIN) {
                 if (h->cs.nlarge == CIP_MAX_LARGE_S) { cip_set_error("more than %d S cones of order >= %d", CIP_MAX_LARGE_S, CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
                 h->cs.large_cone[h->cs.nlarge++] = c;
-                if (h->h_cones[c].r > rmax_large) rmax_large = h->h_cones[c].r;
             } else small.push_back(c);
         }
         h->cs.ns_small = (int)small.size();
-        DMALLOC(h->cs.d_sidx_small, sizeof(int) * (small.size() + 1));
-        if (!small.empty()) CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_sidx_small, small.data(), sizeof(int) * small.size(), hipMemcpyHostToDevice, s));
-        if (h->cs.nlarge > 0) { int rcl = cip_sdp_large_create(rmax_large, h->cs.nlarge, n, &h->cs.lg); if (rcl) return rcl; }
-    }
-    if (has_S) {
         const int per = n < 64 ? n : 64;
         h->cs.sdp_slots = h->cs.ns * (per > 0 ? per : 1);
-        DMALLOC(h->cs.d_sidx, sizeof(int) * sidx.size());
-        h->st_sidx = sidx;
-        CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_sidx, h->st_sidx.data(), sizeof(int) * sidx.size(), hipMemcpyHostToDevice, s));
-        DMALLOC(h->cs.d_sdpws, sizeof(double) * (size_t)h->cs.sdp_slots * 6 * rmax * rmax);
-        DMALLOC(h->cs.d_sdpvec, sizeof(double) * (size_t)h->cs.sdp_slots * 2 * kmax);
-        const size_t nflag = (size_t)rup(4 + (h->cs.nlarge > 12 ? h->cs.nlarge : 12), 16);   // [0]: an iterate left the cone; [4 + li]: gate of large cone li's general division (li < nlarge <= CIP_MAX_LARGE_S)
-        DMALLOC(h->cs.d_sdpflag, sizeof(int) * nflag);
-        CIP_HIP_CHECK(hipMemsetAsync(h->cs.d_sdpflag, 0, sizeof(int) * nflag, s));
     }
-    if (!h->h_cones.empty())
-        CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_cones, h->h_cones.data(), sizeof(ConeDesc) * h->h_cones.size(), hipMemcpyHostToDevice, s));
-    if (!h->h_items.empty())
-        CIP_HIP_CHECK(hipMemcpyAsync(h->cs.d_items, h->h_items.data(), sizeof(WorkItem) * h->h_items.size(), hipMemcpyHostToDevice, s));
 
     // ---- sizes
     h->npad = rup(n, CIP_NB);
@@ -501,74 +460,131 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
     h->Npad = rup(h->N, CIP_NB);
     h->ldk = h->Npad;
 
-    // ---- Q, G, A: buffers here, contents by upload_problem (also used by cip_update_problem)
-    if (h->Q_sparse) {                                    // O(nnz): neither the dense image nor the symv tables
-        DMALLOC(h->Q_rp, sizeof(int) * (n + 1)); DMALLOC(h->Q_ci, sizeof(int) * h->Q_nnz); DMALLOC(h->Q_v, sizeof(double) * h->Q_nnz);
-    } else {
-        DMALLOC(h->Q, sizeof(double) * (size_t)n * n);
-        if (n >= 2048 && n % 128 == 0) DMALLOC(h->symv_ws, sizeof(double) * 2 * (size_t)(n / 128) * n);
-    }
-    DMALLOC(h->G, sizeof(double) * (size_t)p * n);
-    DMALLOC(h->Gt, sizeof(double) * (size_t)p * n);
+    // ---- the forms of A
     h->A_sparse = (pr->A == NULL && m > 0);
-    int rc;
     if (!h->A_sparse) {
-        DMALLOC(h->A, sizeof(double) * (size_t)m * n);
-        DMALLOC(h->At, sizeof(double) * (size_t)h->npad * h->mpad);
-        CIP_HIP_CHECK(hipMemsetAsync(h->At, 0, sizeof(double) * (size_t)h->npad * h->mpad, s));
-        if (h->route == CIP_ROUTE_SCHUR) {
-            DMALLOC(h->Wt, sizeof(double) * (size_t)h->npad * h->mpad);
-            CIP_HIP_CHECK(hipMemsetAsync(h->Wt, 0, sizeof(double) * (size_t)h->npad * h->mpad, s));
-            h->syrk_n = cip_syrk_split(h->npad, h->mpad, &h->syrk_len);
-            if (h->syrk_n > 1) DMALLOC(h->syrk_ws, sizeof(double) * (size_t)h->syrk_n * h->npad * h->npad);
-        }
+        if (h->route == CIP_ROUTE_SCHUR) h->syrk_n = cip_syrk_split(h->npad, h->mpad, &h->syrk_len);
     } else {
         int nnz = 0;
         if (dev && !(pr->flags & CIP_FLAG_CSR_HOST)) CIP_HIP_CHECK(hipMemcpy(&nnz, pr->A_rowptr + m, sizeof(int), hipMemcpyDeviceToHost));
         else nnz = pr->A_rowptr[m];
         if (nnz < 0) { cip_set_error("bad CSR row pointer"); return CIP_E_INVALID; }
         h->A_nnz = nnz;
-        DMALLOC(h->A_rp, sizeof(int) * (m + 1)); DMALLOC(h->A_ci, sizeof(int) * nnz); DMALLOC(h->A_v, sizeof(double) * nnz);
-        DMALLOC(h->T_rp, sizeof(int) * (n + 1)); DMALLOC(h->T_ci, sizeof(int) * nnz); DMALLOC(h->T_v, sizeof(double) * nnz);
-        DMALLOC(h->kdiag, sizeof(double) * (n > 0 ? n : 1));
         std::vector<int> &rc_ = h->st_rowcone;
         rc_.assign(m > 0 ? m : 1, 0);
         for (size_t c = 0; c < h->h_cones.size(); ++c)
             for (int e = 0; e < h->h_cones[c].dim; ++e) rc_[h->h_cones[c].off + e] = (int)c;
-        DMALLOC(h->row_cone, sizeof(int) * m);
-        if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(h->row_cone, rc_.data(), sizeof(int) * m, hipMemcpyHostToDevice, s));
-        if (h->mS > 0 && h->route == CIP_ROUTE_SCHUR) {
-            DMALLOC(h->AtS, sizeof(double) * (size_t)h->npad * h->mSpad);
-            DMALLOC(h->WtS, sizeof(double) * (size_t)h->npad * h->mSpad);
+    }
+    h->ldlt_fused = cip_ldlt_fused_for(h->Npad);          // read ONCE: sizing and carve must agree
+    return 0;
+}
+
+// [0]: an iterate left the cone; [4 + li]: gate of large cone li's general division (li < nlarge <= CIP_MAX_LARGE_S)
+static size_t sdp_flag_words(const ConeSet &cs) { return (size_t)rup(4 + (cs.nlarge > 12 ? cs.nlarge : 12), 16); }
+
+// Layout: every creation-time buffer of a planned handle, in order, each rounded up to 256 bytes; a member of length zero still takes
+// a granule (distinct non-null pointers).  Over a null base the walk sizes the handle's device block, over the block it carves: an
+// ordinary handle's own allocation, or its slab of a lock-step group's arena -- problem z's walk is problem 0's, so its buffers sit
+// at problem 0's addresses + z * stride.  `extras`: what an ordinary handle allocates on first use and a lock-step handle must hold
+// at a fixed offset.  The workspace of chip-wide S cones is not part of it (cip_sdp_large_create: an allocation of its own).
+template <typename T> static void take(CipLayout &L, T *&ptr, size_t count) { ptr = L.take<T>(count ? count : 1); }
+size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras) {
+    ConeSet &cs = h->cs;
+    const size_t n = h->n, m = h->m, p = h->p, npad = h->npad, nnz = h->A_nnz;
+    if (cs.npackq > 0) take(L, cs.d_packq, cs.npackq);
+    if (cs.nritems > 0) take(L, cs.d_ritems, cs.nritems);
+    if (cs.nbigq > 0) take(L, cs.d_bigq, cs.nbigq);
+    take(L, cs.d_cones, cs.ncones); take(L, cs.d_items, cs.nitems); take(L, cs.d_scal, cs.scal_len);
+    take(L, cs.d_partial, 2 * ((size_t)cs.nslots + 1));            // two sets: the pair of max-steps (cip_cones_maxstep2)
+    take(L, cs.d_scalar, 8);
+    if (cs.has_S) {
+        take(L, cs.d_sidx_small, (size_t)cs.ns_small + 1); take(L, cs.d_sidx, cs.ns);
+        take(L, cs.d_sdpws, (size_t)cs.sdp_slots * 6 * cs.rmax * cs.rmax); take(L, cs.d_sdpvec, (size_t)cs.sdp_slots * 2 * cs.kmax);
+        take(L, cs.d_sdpflag, sdp_flag_words(cs));
+    }
+    // Q, G, A: contents by upload_problem (also used by cip_update_problem)
+    if (h->Q_sparse) {                                    // O(nnz): neither the dense image nor the symv tables
+        take(L, h->Q_rp, n + 1); take(L, h->Q_ci, h->Q_nnz); take(L, h->Q_v, h->Q_nnz);
+    } else {
+        take(L, h->Q, n * n);
+        if (n >= 2048 && n % 128 == 0) take(L, h->symv_ws, 2 * (n / 128) * n);
+    }
+    take(L, h->G, p * n); take(L, h->Gt, p * n);
+    if (!h->A_sparse) {
+        take(L, h->A, m * n); take(L, h->At, npad * h->mpad);
+        if (h->route == CIP_ROUTE_SCHUR) {
+            take(L, h->Wt, npad * h->mpad);
+            if (h->syrk_n > 1) take(L, h->syrk_ws, h->syrk_n * npad * npad);
+        }
+    } else {
+        take(L, h->A_rp, m + 1); take(L, h->A_ci, nnz); take(L, h->A_v, nnz);
+        take(L, h->T_rp, n + 1); take(L, h->T_ci, nnz); take(L, h->T_v, nnz);
+        take(L, h->kdiag, n); take(L, h->row_cone, m);
+        if (h->mS > 0 && h->route == CIP_ROUTE_SCHUR) { take(L, h->AtS, npad * h->mSpad); take(L, h->WtS, npad * h->mSpad); }
+        if (h->route == CIP_ROUTE_SCHUR) take(L, h->Gm, npad * h->nqpad);
+    }
+    // KKT matrix, LDL' workspace, scratch
+    take(L, h->K, (size_t)h->ldk * h->Npad);
+    h->ws_base = L.take<char>(cip_ldlt_ws_bytes(h->Npad, h->ldlt_fused));
+    cip_ldlt_ws_carve(h->ws_base, h->Npad, &h->ws, h->ldlt_fused);
+    take(L, h->rhs, h->Npad);
+    take(L, h->mt1, m); take(L, h->mt2, m); take(L, h->mt3, m); take(L, h->nt1, n); take(L, h->pt1, p);
+    take(L, h->dot_scratch, 32 * 32 + 32);
+    { StageView v; h->stage = (double *)L.take<char>(stage_layout(nullptr, h, 1, 1, &v)); }
+    if (extras & CIP_EXTRA_DRIVER) h->drv = (double *)L.take<char>(cip_driver_bytes(h));
+    if (extras & CIP_EXTRA_REFINE) {
+        RefView v;
+        h->ref = (double *)L.take<char>(ref_layout(nullptr, h, &v));
+        if (m > 0 && h->route == CIP_ROUTE_SCHUR) take(L, h->c2x2, m);
+    }
+    return L.bytes();
+}
+
+// Fill: the small tables, the zero padding, the problem's matrices and the identity scaling into a carved handle, on its stream
+static int handle_fill(const cip_problem *pr, cip_handle *h, bool final_sync) {
+    ConeSet &cs = h->cs;
+    const int n = h->n, m = h->m, p = h->p;
+    hipStream_t s = h->stream;   // default (null) stream until cip_set_stream
+    int rc;
+    auto upload = [s](auto *dst, const auto &src, size_t count) {
+        return count ? hipMemcpyAsync(dst, src.data(), sizeof(*dst) * count, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    if (cs.npackq > 0) CIP_HIP_CHECK(upload(cs.d_packq, h->st_packq, cs.npackq));
+    if (cs.nritems > 0) CIP_HIP_CHECK(upload(cs.d_ritems, h->st_ritems, cs.nritems));
+    if (cs.nbigq > 0) CIP_HIP_CHECK(upload(cs.d_bigq, h->st_bigq, cs.nbigq));
+    if (cs.has_S) {
+        CIP_HIP_CHECK(upload(cs.d_sidx_small, h->st_small, cs.ns_small));
+        if (cs.nlarge > 0) {
+            int rmax_large = 0;
+            for (int li = 0; li < cs.nlarge; ++li) if (h->h_cones[cs.large_cone[li]].r > rmax_large) rmax_large = h->h_cones[cs.large_cone[li]].r;
+            if ((rc = cip_sdp_large_create(rmax_large, cs.nlarge, n, &cs.lg))) return rc;
+        }
+        CIP_HIP_CHECK(upload(cs.d_sidx, h->st_sidx, cs.ns));
+        CIP_HIP_CHECK(hipMemsetAsync(cs.d_sdpflag, 0, sizeof(int) * sdp_flag_words(cs), s));
+    }
+    CIP_HIP_CHECK(upload(cs.d_cones, h->h_cones, cs.ncones));
+    CIP_HIP_CHECK(upload(cs.d_items, h->h_items, cs.nitems));
+    if (!h->A_sparse) {
+        CIP_HIP_CHECK(hipMemsetAsync(h->At, 0, sizeof(double) * (size_t)h->npad * h->mpad, s));
+        if (h->Wt) CIP_HIP_CHECK(hipMemsetAsync(h->Wt, 0, sizeof(double) * (size_t)h->npad * h->mpad, s));
+    } else {
+        CIP_HIP_CHECK(upload(h->row_cone, h->st_rowcone, m));
+        if (h->AtS) {
             CIP_HIP_CHECK(hipMemsetAsync(h->AtS, 0, sizeof(double) * (size_t)h->npad * h->mSpad, s));
             CIP_HIP_CHECK(hipMemsetAsync(h->WtS, 0, sizeof(double) * (size_t)h->npad * h->mSpad, s));
         }
-        if (h->route == CIP_ROUTE_SCHUR) DMALLOC(h->Gm, sizeof(double) * (size_t)h->npad * h->nqpad);
     }
     if ((rc = upload_problem(h, pr))) return rc;
-
-    // ---- KKT matrix, workspace, scratch
-    DMALLOC(h->K, sizeof(double) * (size_t)h->ldk * h->Npad);
-    {
-        const int fz = cip_ldlt_fused_for(h->Npad);             // read ONCE: sizing and carve must agree
-        DMALLOC(h->ws_base, cip_ldlt_ws_bytes(h->Npad, fz));
-        cip_ldlt_ws_carve(h->ws_base, h->Npad, &h->ws, fz);
-    }
     h->ws.x_zeroed = &h->x_zeroed;
-    h->ws.side = h->arena ? nullptr : &h->ldlt_side;      // (handles of a lock-step arena factor inside batched launches)
+    h->ws.side = h->in_slab ? nullptr : &h->ldlt_side;    // (handles of a lock-step arena factor inside batched launches)
     // pivot signs of the quasi-definite order: Schur route [S G'; G 0] = n positive, p negative; literal 3x3 in the
     // order (3,1,2) = m negative (-F'F), n positive, p negative
     h->ws.signs = (h->route == CIP_ROUTE_SCHUR) ? PivotSigns{0, n, n + p} : PivotSigns{m, m + n, m + n + p};
-    DMALLOC(h->rhs, sizeof(double) * h->Npad);
-    DMALLOC(h->mt1, sizeof(double) * m); DMALLOC(h->mt2, sizeof(double) * m); DMALLOC(h->mt3, sizeof(double) * m);
-    DMALLOC(h->nt1, sizeof(double) * n); DMALLOC(h->pt1, sizeof(double) * p);
-    DMALLOC(h->dot_scratch, sizeof(double) * (32 * 32 + 32));
-    { StageView v; DMALLOC(h->stage, stage_layout(nullptr, h, 1, 1, &v)); }
     CIP_HIP_CHECK(hipEventCreate(&h->ev0)); CIP_HIP_CHECK(hipEventCreate(&h->ev1)); CIP_HIP_CHECK(hipEventCreate(&h->ev2));
     // (the pinned pivot-flag words are allocated by the first factorisation: pinned allocations cost ~0.1 ms each, and the
     //  64 handles of a lock-step group never use theirs)
-    if ((rc = cip_cones_identity_scaling(s, h->cs))) return rc;
-    if ((rc = cip_sdp_scaling_changed(s, h->cs))) return rc;
+    if ((rc = cip_cones_identity_scaling(s, cs))) return rc;
+    if ((rc = cip_sdp_scaling_changed(s, cs))) return rc;
     // the caller's Q / A / G may go away as soon as a public create returns: wait for the uploads.  A lock-step group
     // keeps its problems alive for the whole call and creates its 64 handles without a single host wait.
     if (final_sync) CIP_HIP_CHECK(hipStreamSynchronize(s));
@@ -578,26 +594,37 @@ static int create_impl(const cip_problem *pr, cip_handle *h, bool final_sync = t
 extern "C" int cip_create_ex(const cip_problem *prob, cip_handle **out) {
     if (!prob || !out) { cip_set_error("NULL argument"); return CIP_E_INVALID; }
     *out = NULL;
-    cip_handle *h = new (std::nothrow) cip_handle();
-    if (!h) { cip_set_error("out of host memory"); return CIP_E_INVALID; }
-    const int rc = create_impl(prob, h);
-    if (rc) { free_all(h); delete h; return rc; }
+    cip_handle *h = nullptr;
+    int rc = cip_plan(prob, nullptr, &h);
+    void *block = nullptr;
+    if (!rc) rc = cip_handle_alloc(h, &block, cip_handle_layout(nullptr, h, 0));      // ONE device allocation (poisoned under CIP_DEBUG_POISON)
+    if (!rc) { cip_handle_layout(block, h, 0); rc = handle_fill(prob, h, true); }
+    if (rc) { if (h) { free_all(h); delete h; } return rc; }
     *out = h;
     return 0;
 }
 
-// A handle whose creation-time buffers are carved out of `slab` (lock-step batches, driver.hip); the slab belongs to the
-// caller and outlives the handle.
-int cip_create_in_arena(const cip_problem *pr, char *slab, size_t cap, hipStream_t stream, cip_handle **out) {
+// A planned handle: the host half of level 1 on `stream`, nothing on the device yet (cip_destroy takes it back as it is)
+int cip_plan(const cip_problem *pr, hipStream_t stream, cip_handle **out) {
     *out = nullptr;
     cip_handle *h = new (std::nothrow) cip_handle();
     if (!h) { cip_set_error("out of host memory"); return CIP_E_INVALID; }
-    h->arena = slab; h->arena_cap = cap; h->arena_used = 0;
     h->stream = stream;
-    const int rc = create_impl(pr, h, false);
-    if (rc) { free_all(h); delete h; return rc; }
+    const int rc = handle_plan(pr, h);
+    if (rc) { delete h; return rc; }
     *out = h;
     return 0;
+}
+
+// The device half for a handle of a lock-step group: carved out of `slab` (cap bytes; it belongs to the caller and outlives the
+// handle) and filled without a host wait.
+int cip_create_in_slab(cip_handle *h, const cip_problem *pr, char *slab, size_t cap, unsigned extras) {
+    const size_t bytes = cip_handle_layout(nullptr, h, extras);
+    if (bytes > cap) { cip_set_error("lock-step batch: a handle of %zu bytes in a slab of %zu", bytes, cap); return CIP_E_UNSUPPORTED; }
+    h->in_slab = true;
+    cip_handle_layout(slab, h, extras);
+    const int rc = debug_poison(slab, bytes);
+    return rc ? rc : handle_fill(pr, h, false);
 }
 
 extern "C" int cip_create(int n, int m, int p, int ncones, const int *cone_type, const int *cone_dim, const double *Q,
@@ -1049,7 +1076,7 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
     hipStream_t s = h->stream;
     if (!h->ref) {
         if (batch) { cip_set_error("cip_solve3x3: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
-        if ((rc = cip_alloc_refine_buffers(h))) return rc;
+        if ((rc = alloc_refine_buffers(h))) return rc;
     }
     RefView v;
     ref_layout(h->ref, h, &v);
@@ -1085,12 +1112,6 @@ extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y,
     }
     return 0;
 }
-int cip_alloc_refine_buffers(cip_handle *h) {
-    if (!h->ref) { RefView v; DMALLOC(h->ref, ref_layout(nullptr, h, &v)); }
-    if (!h->c2x2 && h->m > 0 && h->route == CIP_ROUTE_SCHUR) DMALLOC(h->c2x2, sizeof(double) * h->m);
-    return 0;
-}
-
 extern "C" int cip_solve3x3(cip_handle *h, const double *x, const double *y, const double *z, double *a, double *b,
                             double *c) {
     if (!h) return CIP_E_INVALID;
@@ -1131,7 +1152,7 @@ extern "C" int cip_solve2x2_dev(cip_handle *h, const double *y, const double *w,
         { int rcc = cip_zero(h->stream, h->m, h->mt1); if (rcc) return rcc; }
         if (!h->c2x2) {
             if (batch) { cip_set_error("cip_solve2x2: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
-            if ((rc = cip_alloc_refine_buffers(h))) return rc;
+            if ((rc = alloc_refine_buffers(h))) return rc;
         }
         if ((rc = cip_solve3x3_dev(h, y, w, h->mt1, dy, dw, h->c2x2))) return rc;
         if (!batch || regd == mask0) return 0;

@@ -10,13 +10,14 @@ struct cip_handle {
     int nq = 0, nqpad = 0;          // number of Q cones, rounded up to 16 (>= 16)
     hipStream_t stream = nullptr;
     int device = 0;
-    // Device memory of the handle.  Normally one hipMalloc per buffer; a handle of a lock-step batch carves its buffers,
-    // in creation order, out of its slab of the batch's arena (api.hip: cip_handle_alloc) so that problem z's buffers
-    // sit at problem 0's addresses + z * stride.  alloc_bytes counts what creation asked for (256-byte granules).
-    std::vector<void *> owned;      // every pointer cip_handle_alloc got from hipMalloc, first-use buffers included: what destruction frees
-    char *arena = nullptr;
-    size_t arena_cap = 0, arena_used = 0, alloc_bytes = 0;
-    bool arena_overflow = false;
+    // Device memory of the handle.  Every creation-time buffer is a member of ONE block, laid out by one function (api.hip:
+    // cip_handle_layout) that is walked twice: over a null base it sizes the block, over the block it carves.  An ordinary handle
+    // allocates its block; a handle of a lock-step batch borrows its slab of the batch's arena, where the same walk puts problem
+    // z's buffers at problem 0's addresses + z * stride.  Buffers of first use (ref, c2x2, many, many_stage, drv) are allocations
+    // of their own -- except in a slab, whose layout holds those the group needs (CIP_EXTRA_*).
+    std::vector<void *> owned;      // every pointer cip_handle_alloc got from hipMalloc (the block, first-use buffers): what destruction frees
+    bool in_slab = false;           // the block is a slab of a lock-step arena: not the handle's to free
+    int ldlt_fused = 0;             // cip_ldlt_fused_for(Npad) when the handle was planned: both walks lay out the same LDL' workspace
 
     // ---- problem data, device resident for the lifetime of the handle (level 1)
     double *Q = nullptr;            // n x n, ld n            (dense Q only)
@@ -121,12 +122,16 @@ int cip_assemble(cip_handle *h, bool lazy_ok = false);     // assemble.hip; lazy
 // assemble.hip: the assembled K of every problem of the thread's mask becomes K + E, E_ii = +-rel * max_j |K_ij| (what cip_assemble does
 // behind the assembly while h->reg_rel > 0; a lock-step group calls it under the mask of its regularised problems)
 int cip_regularize(cip_handle *h, double rel);
-// api.hip: the buffers the refined solves of a regularised factor allocate on first use (h->ref, h->c2x2), now -- in a lock-step arena
-// every buffer of problem z must sit at problem 0's offset, so a group that may regularise creates them with its handles
-int cip_alloc_refine_buffers(cip_handle *h);
 int cip_mul_Q(cip_handle *h, double alpha, const double *x, double beta, double *y, bool symv = true);   // api.hip: y = alpha Q x + beta y, dense or CSR Q
-int cip_handle_alloc(cip_handle *h, void **out, size_t bytes);      // api.hip
-int cip_create_in_arena(const struct cip_problem *pr, char *slab, size_t cap, hipStream_t stream, cip_handle **out);   // api.hip
+int cip_handle_alloc(cip_handle *h, void **out, size_t bytes);      // api.hip: an allocation of the handle's own
+// api.hip, level 1 in parts (a lock-step group sizes its slabs from problem 0's plan before anything exists on the device):
+// the host half; the layout of the device block (null base: its size); the device half inside a slab.
+// extras: what an ordinary handle allocates on first use and a lock-step handle holds in its slab, in this order
+#define CIP_EXTRA_DRIVER 1u         // h->drv: the vectors of the interior-point loop (cip_driver_bytes)
+#define CIP_EXTRA_REFINE 2u         // h->ref, h->c2x2: the refined solves of a regularised factor
+int cip_plan(const struct cip_problem *pr, hipStream_t stream, cip_handle **out);
+size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras);
+int cip_create_in_slab(cip_handle *h, const struct cip_problem *pr, char *slab, size_t cap, unsigned extras);
 size_t cip_driver_bytes(const cip_handle *h);                        // driver.hip: vectors of the interior-point loop
 // api.hip: resolve the pivot flag of the last factorisation (wait = 0: only if its read-back has already landed)
 int cip_factor_resolve(cip_handle *h, int wait);

@@ -9,8 +9,8 @@
 // the diagonal kernel of 64 problems is one launch of 64 workgroups, the TRSM one launch of 64 x 30, and the host pays
 // one launch and one read-back per step for all of them.
 //
-// How: every device buffer of problem z is carved, in creation order, out of slab z of one arena, so that problem z's
-// pointers are problem 0's + z * stride (cip_handle_alloc).  The library's host code then runs ONCE, on problem 0's
+// How: the device block of problem z's handle is slab z of one arena, carved by the walk that sized it (api.hip: cip_handle_layout),
+// so that problem z's pointers are problem 0's + z * stride.  The library's host code then runs ONCE, on problem 0's
 // handle, under a thread-local batch context (cip_internal.h: cip_launch_b appends {stride, mask} to every launch and
 // multiplies grid.z by B; kernels shift their pointer arguments and drop out when their problem's mask bit is clear).
 // The iteration is cip_conicip's own (driver.hip: Loop::run); the kernels, their grids in x / y and their arithmetic are
@@ -90,8 +90,6 @@ struct ArenaCache {
     std::mutex mu;
     struct Slot { char *ptr; size_t bytes; int device; };
     std::vector<Slot> slots;
-    // last probe: shape signature -> slab bytes
-    std::vector<long> sig; size_t slab = 0;
 } g_cache;
 // *cap: the allocation's true size (a recycled arena may be larger than asked for; it goes back into the cache with that size)
 int arena_acquire(size_t bytes, char **out, size_t *cap) {
@@ -129,13 +127,6 @@ void arena_release(char *ptr, size_t bytes) {
     }
     g_cache.slots.push_back({ptr, bytes, dev});
 }
-// (keep_reg: the handles carry the refinement buffers of the regularised factorisation -- another slab)
-std::vector<long> shape_signature(const cip_problem &pr, int solve_block, bool keep_reg) {
-    std::vector<long> sg = {pr.n, pr.m, pr.p, pr.ncones, pr.route, pr.A == nullptr, solve_block, cip_ldlt_outer_block(), (pr.flags & CIP_FLAG_Q_CSR) != 0, keep_reg};
-    for (int c = 0; c < pr.ncones; ++c) { sg.push_back(pr.cone_type[c]); sg.push_back(pr.cone_dim[c]); }
-    return sg;
-}
-
 struct Group {
     int B = 0;
     char *arena = nullptr; size_t arena_bytes = 0;
@@ -281,7 +272,7 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     const auto t_start = std::chrono::steady_clock::now();
     static const bool timing = cip_env_set("CIP_LOCKSTEP_TIMING");
     auto since = [&]() { return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-    double t_probe = 0, t_arena = 0, t_create = 0, t_loop = 0;
+    double t_plan = 0, t_arena = 0, t_create = 0, t_loop = 0;
     const cip_options o = resolve_options(opt_in);
     const int n = probs[0].n, m = probs[0].m, p = probs[0].p;
     struct ExitTimer {            // reports what the destructors behind it (handles, arena) cost
@@ -299,35 +290,15 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
         explicit SolveBlockScope(int B_) : saved(cip_tl_solve_block_max) { cip_tl_solve_block_max = cip_lockstep_solve_block_for(B_); }
         ~SolveBlockScope() { cip_tl_solve_block_max = saved; }
     } solve_block_scope(call_count);
-    // ---- slab size: create problem 0 once with ordinary allocations and count what it asked for
-    size_t slab = 0;
-    // CSR: the slab depends on the number of non-zeros -- part of the signature when the row pointers are host memory
-    // (the probe is a full handle creation: 0.9 ms per call, 4 % of an 8-problem pass), else always probe
-    const bool csr = probs[0].A == nullptr && m > 0;
-    const bool csr_host = csr && probs[0].A_rowptr && ((probs[0].flags & CIP_FLAG_CSR_HOST) || !(probs[0].flags & CIP_FLAG_DEVICE_PTRS));
+    // ---- slab size: the walk that will carve problem 0's slab, over a null base (under the group's solve-block limit, like the carve)
     const bool keep_reg = g_keep_regularized.load() != 0;            // (read once: the group's slab and its policy must agree)
-    std::vector<long> sig = shape_signature(probs[0], cip_tl_solve_block_max, keep_reg);
-    if (csr_host) sig.push_back((long)probs[0].A_rowptr[m]);
-    // the same for a CSR Q (its slab share is O(nnz)): a count that cannot be read here means "always probe"
-    const bool qcsr = (probs[0].flags & CIP_FLAG_Q_CSR) != 0;
-    const bool qcsr_host = qcsr && probs[0].Q_rowptr && ((probs[0].flags & CIP_FLAG_CSR_HOST) || !(probs[0].flags & CIP_FLAG_DEVICE_PTRS));
-    if (qcsr_host) sig.push_back(-1L - (long)probs[0].Q_rowptr[n]);
-    if ((!csr || csr_host) && (!qcsr || qcsr_host)) {
-        std::lock_guard<std::mutex> lk(g_cache.mu);
-        if (g_cache.sig == sig) slab = g_cache.slab;
-    }
-    if (slab == 0) {
-        cip_handle *probe = nullptr;
-        if ((rc = cip_create_ex(&probs[0], &probe))) return rc;
-        if (keep_reg && (rc = cip_alloc_refine_buffers(probe))) { cip_destroy(probe); return rc; }
-        slab = probe->alloc_bytes + ((cip_driver_bytes(probe) + 255) & ~(size_t)255);
-        const bool large_S = probe->cs.nlarge > 0;
-        cip_destroy(probe);
-        if (large_S) { cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
-        std::lock_guard<std::mutex> lk(g_cache.mu);
-        g_cache.sig = sig; g_cache.slab = slab;
-    }
-    t_probe = since();
+    // the loop's vectors, and what a regularised factor's refined solves would allocate on first use: part of every slab
+    const unsigned extras = CIP_EXTRA_DRIVER | (keep_reg ? CIP_EXTRA_REFINE : 0u);
+    G.h.assign(B, nullptr);
+    if ((rc = cip_plan(&probs[0], G.stream, &G.h[0]))) return rc;
+    if (G.h[0]->cs.nlarge > 0) { cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
+    const size_t slab = cip_handle_layout(nullptr, G.h[0], extras);
+    t_plan = since();
     // odd number of 256-byte granules: the same buffer of consecutive problems does not land on the same HBM channel
     size_t gran = (slab + 255) / 256;
     if ((gran & 1) == 0) ++gran;
@@ -337,20 +308,16 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     if ((rc = arena_acquire(G.arena_bytes, &G.arena, &G.arena_bytes))) return rc;
     G.gather_dev = (double *)(G.arena + G.stride * (size_t)B);
     CIP_HIP_CHECK(hipHostMalloc((void **)&G.gather_host, gather_bytes, hipHostMallocDefault));
-    G.h.assign(B, nullptr);
     t_arena = since();
     for (int z = 0; z < B; ++z) {
-        if ((rc = cip_create_in_arena(&probs[z], G.arena + G.stride * (size_t)z, G.stride, G.stream, &G.h[z]))) return rc;
+        if (z > 0 && (rc = cip_plan(&probs[z], G.stream, &G.h[z]))) return rc;
         cip_handle *hz = G.h[z];
-        void *drv = nullptr;
-        if ((rc = cip_handle_alloc(hz, &drv, cip_driver_bytes(hz)))) return rc;
-        hz->drv = (double *)drv;
-        // what a regularised factor's refined solves would allocate on first use: in a slab every problem's buffer sits at problem 0's offset
-        if (keep_reg && (rc = cip_alloc_refine_buffers(hz))) return rc;
-        if (hz->arena_overflow || (z > 0 && hz->arena_used != G.h[0]->arena_used)) {
+        // (device-resident CSR arrays with another number of non-zeros: same_shape could not look)
+        if (cip_handle_layout(nullptr, hz, extras) != slab) {
             cip_set_error("lock-step batch: problem %d does not fit problem 0's slab layout", z);
             return CIP_E_UNSUPPORTED;
         }
+        if ((rc = cip_create_in_slab(hz, &probs[z], G.arena + G.stride * (size_t)z, G.stride, extras))) return rc;
         // the group's launches are problem 0's: a CSR Q whose longest row asks for the other mat-vec form (other bits) cannot follow
         if (hz->Q_wave != G.h[0]->Q_wave) {
             cip_set_error("lock-step batch: the CSR Q of problem %d takes another mat-vec form than problem 0's", z);
@@ -376,8 +343,8 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     CIP_HIP_CHECK(hipStreamSynchronize(s));
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     if (timing)
-        fprintf(stderr, "lockstep group B=%d n=%d: probe %.2f ms, arena %.2f, create %.2f, loop %.2f (%d iterations), download %.2f; slab %.1f MB\n",
-                B, n, t_probe, t_arena - t_probe, t_create - t_arena, t_loop - t_create, L.iters, 1e3 * wall - t_loop, G.stride / 1048576.0);
+        fprintf(stderr, "lockstep group B=%d n=%d: plan %.2f ms, arena %.2f, create %.2f, loop %.2f (%d iterations), download %.2f; slab %.1f MB\n",
+                B, n, t_plan, t_arena - t_plan, t_create - t_arena, t_loop - t_create, L.iters, 1e3 * wall - t_loop, G.stride / 1048576.0);
     for (int z = 0; z < B; ++z) {
         if (L.ejected[z]) continue;
         apply_certificate(L.outcome[z], n, m, p, y[z], p > 0 ? w[z] : nullptr, m > 0 ? v[z] : nullptr);

@@ -79,6 +79,13 @@ def build(kind="asan", verbose=False):
 
 def run(kind="asan", verbose=True, threads=3):
     exe, env = build(kind, verbose=verbose)
+    # the lock-step slab sizes pinned in drive.cpp, a fresh process each (`drive slab` prints how many); the first failure is the result
+    for k in range(int(subprocess.run([exe, "slab"], env=env, capture_output=True, text=True, timeout=60).stdout)):
+        r = subprocess.run([exe, "slab", str(k)], env=env, capture_output=True, text=True, timeout=600)
+        if verbose:
+            print(r.stdout[-300:], r.stderr[-3000:])
+        if r.returncode != 0:
+            return r
     r = subprocess.run([exe, str(threads)], env=env, capture_output=True, text=True, timeout=1500)
     if verbose:
         print(r.stdout[-3000:], r.stderr[-6000:])

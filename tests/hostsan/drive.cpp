@@ -8,7 +8,9 @@
 //      problem with a chip-wide S cone (lock-step refuses it: thread pool), and a batch holding an S cone beyond the envelope
 //      (refused at level 1: the call must fail cleanly and free everything);
 //   4. the same entry points from several caller threads at once (thread-local batch contexts, the cached arena, the pool);
-//   5. the stand-alone LDL' entry points with a caller-owned workspace in both solve modes, and their refusals of bad arguments.
+//   5. the stand-alone LDL' entry points with a caller-owned workspace in both solve modes, and their refusals of bad arguments;
+//   6. the handle's device block: one "device" allocation per handle (two with a chip-wide S cone), lock-step calls of one shape
+//      under changing solve modes, and -- `drive slab K`, a fresh process per case -- the slab sizes of every branch of the layout.
 // At the end every "device" allocation must have been returned (the fake runtime counts them).
 #include "cipkkt.h"
 #include <cstdio>
@@ -18,6 +20,7 @@
 #include <vector>
 
 extern "C" void fake_hip_stats(long *launches, long *emulated, long *live_bytes, long *live_allocs);
+extern "C" long fake_hip_device_allocs(void);
 
 #define REQUIRE(cond) do { if (!(cond)) { fprintf(stderr, "drive: %s:%d: %s failed (last error: %s)\n", __FILE__, __LINE__, #cond, cip_last_error()); exit(2); } } while (0)
 
@@ -25,8 +28,9 @@ struct Prob {
     int n, m, p;
     std::vector<int> ctype, cdim;
     std::vector<double> Q, A, G, c, b, d, Av;
-    std::vector<int> rp, ci;
-    bool csr = false;
+    std::vector<int> rp, ci, qrp, qci;
+    std::vector<double> qv;
+    bool csr = false, qcsr = false;
     int route = CIP_ROUTE_SCHUR;
     cip_problem desc() const {
         cip_problem pr;
@@ -38,6 +42,7 @@ struct Prob {
         else { pr.A = A.data(); pr.lda = m; }
         pr.G = p > 0 ? G.data() : nullptr; pr.ldg = p > 0 ? p : 1;
         pr.route = route; pr.flags = 0;
+        if (qcsr) { pr.Q = nullptr; pr.Q_rowptr = qrp.data(); pr.Q_colind = qci.data(); pr.Q_val = qv.data(); pr.flags |= CIP_FLAG_Q_CSR; }
         return pr;
     }
 };
@@ -248,8 +253,107 @@ static void standalone_ldlt(void) {
     REQUIRE(cip_gemm_nt_dev(nullptr, M, Nn, Kk, 1.0, A, M + 16, B, Nn + 2, C, M + 128, 0) == CIP_OK);
 }
 
+// ---- the handle's device block and the lock-step slab (api.hip: handle_layout; lockstep.hip: lockstep_group)
+static int lockstep(Batch &B, int max_iters) {
+    cip_options o = opts();
+    o.maxIters = max_iters;
+    return cip_conicip_lockstep((int)B.P.size(), B.desc.data(), B.c.data(), B.b.data(), B.d.data(), &o, B.yp.data(), B.wp.data(), B.vp.data(), B.res.data());
+}
+static Batch pair_of(const Prob &a, const Prob &b) { Batch B; B.P = {a, b}; B.finish(); return B; }
+
+// A cip_set_solve_fused between two lock-step calls of one shape changes what the handles' LDL' workspace holds (two solve blocks: the
+// pre-multiplied neighbour blocks), hence the slab: every call must size its slabs for the mode it runs under.
+static void knob_sequence(void) {
+    const int pb = cip_set_solve_block_max(128), ps = cip_set_lockstep_split(1), pf = cip_set_solve_fused(-1);
+    for (int mode : {0, 2, 0}) {
+        cip_set_solve_fused(mode);
+        Batch B = pair_of(make(200, 0, {{CIP_CONE_R, 200}}, 1.0), make(200, 0, {{CIP_CONE_R, 200}}, 1.0));
+        REQUIRE(lockstep(B, 1) == CIP_OK);
+        for (auto &y : B.y) REQUIRE(y[0] != 777.0);
+    }
+    cip_set_solve_fused(pf); cip_set_lockstep_split(ps); cip_set_solve_block_max(pb);
+}
+
+// One device allocation per handle (two with a chip-wide S cone, whose workspace keeps its own), none after destruction.
+static void allocation_count(const Prob &P, long expect) {
+    cip_problem pr = P.desc();
+    cip_handle *h = nullptr;
+    const long before = fake_hip_device_allocs();
+    REQUIRE(cip_create_ex(&pr, &h) == CIP_OK && h);
+    const long held = fake_hip_device_allocs() - before;
+    if (held != expect) fprintf(stderr, "drive: the handle holds %ld device allocations, expected %ld\n", held, expect);
+    REQUIRE(held == expect);
+    REQUIRE(cip_destroy(h) == CIP_OK);
+    REQUIRE(fake_hip_device_allocs() == before);
+}
+
+// `drive slab K`, a fresh process per case: what is live right after the first two-problem lock-step call (split 1) -- the arena of two
+// slabs and the gather rows, the group's pinned gather rows and the thread's 4-KB pinned scratch.  The expected figures were recorded
+// with this program from the library as it stood when every handle was created twice, once to be measured and once in its slab: a
+// slab is sized by the walk that carves it now, and must come out at the same number of bytes.
+struct SlabCase { const char *what; long expect; };
+static const SlabCase slab_cases[] = {
+    {"dense A, R cone, n = m = 200, solve block 128", 10722816},
+    {"dense A, R cone, n = m = 1024", 124857856},
+    {"dense A, R cone, n = m = 1152: nine solve blocks", 136332800},
+    {"p > 0, R + Q + S cones, Schur route", 3651072},
+    {"p > 0, R + Q + S cones, literal 3x3 route", 3618304},
+    {"CSR A, R + Q cones", 3597824},
+    {"CSR A, R + S cones, Schur route", 3682816},
+    {"CSR Q", 3626496},
+    {"p > 0, R + Q cones, regularised problems stay in their group", 3630592},
+    {"dense A, n = 2048: symv tables", 217748992},
+    {"dense A, n = 128, m = 4096: split-K images of the Schur formation", 35229184},
+    {"dense A, R cone, n = m = 1152, one-launch block steps", 141051392},
+};
+static Batch slab_batch(int k) {
+    auto two = [](int n, int p, std::vector<std::pair<int, int>> cones, double density, int route = CIP_ROUTE_SCHUR) {
+        Prob a = make(n, p, cones, density, route);
+        return pair_of(a, a);                                    // (one CSR pattern: equal nnz)
+    };
+    switch (k) {
+    case 0: cip_set_solve_block_max(128); return two(200, 0, {{CIP_CONE_R, 200}}, 1.0);
+    case 1: return two(1024, 0, {{CIP_CONE_R, 1024}}, 1.0);
+    case 2: return two(1152, 0, {{CIP_CONE_R, 1152}}, 1.0);
+    case 3: return two(12, 3, {{CIP_CONE_R, 5}, {CIP_CONE_Q, 5}, {CIP_CONE_S, 6}}, 1.0);
+    case 4: return two(12, 3, {{CIP_CONE_R, 5}, {CIP_CONE_Q, 5}, {CIP_CONE_S, 6}}, 1.0, CIP_ROUTE_FULL3X3);
+    case 5: return two(10, 0, {{CIP_CONE_R, 6}, {CIP_CONE_Q, 4}}, 0.4);
+    case 6: return two(12, 0, {{CIP_CONE_R, 5}, {CIP_CONE_S, 6}}, 0.4);
+    case 7: {
+        Prob a = make(9, 0, {{CIP_CONE_R, 9}}, 1.0);
+        a.qcsr = true;
+        for (int i = 0; i < a.n; ++i) { a.qrp.push_back(i); a.qci.push_back(i); a.qv.push_back(a.Q[i + (size_t)i * a.n]); }
+        a.qrp.push_back(a.n);
+        return pair_of(a, a);
+    }
+    case 8: cip_set_lockstep_regularize(1); return two(10, 2, {{CIP_CONE_R, 4}, {CIP_CONE_Q, 6}}, 1.0);
+    case 9: return two(2048, 0, {{CIP_CONE_R, 16}}, 1.0);
+    case 10: return two(128, 0, {{CIP_CONE_R, 4096}}, 1.0);
+    default: cip_set_solve_fused(2); return two(1152, 0, {{CIP_CONE_R, 1152}}, 1.0);
+    }
+}
+static int slab_main(int k) {
+    cip_set_lockstep_split(1);
+    Batch B = slab_batch(k);
+    REQUIRE(lockstep(B, 1) == CIP_OK);
+    long launches, emulated, live_bytes, live_allocs;
+    fake_hip_stats(&launches, &emulated, &live_bytes, &live_allocs);
+    printf("drive: slab case %d (%s): %ld bytes live, expected %ld\n", k, slab_cases[k].what, live_bytes, slab_cases[k].expect);
+    return live_bytes == slab_cases[k].expect ? 0 : 3;
+}
+
 int main(int argc, char **argv) {
+    const int ncases = (int)(sizeof(slab_cases) / sizeof(slab_cases[0]));
+    if (argc > 1 && !strcmp(argv[1], "slab")) {
+        if (argc < 3) { printf("%d\n", ncases); return 0; }
+        const int k = atoi(argv[2]);
+        return k >= 0 && k < ncases ? slab_main(k) : 2;
+    }
     const int nthreads = argc > 1 ? atoi(argv[1]) : 3;
+    allocation_count(make(200, 0, {{CIP_CONE_R, 200}}, 1.0), 1);
+    allocation_count(make(10, 2, {{CIP_CONE_R, 4}, {CIP_CONE_Q, 6}}, 0.4), 1);
+    allocation_count(make(4, 0, {{CIP_CONE_S, 133 * 134 / 2}}, 1.0), 2);
+    knob_sequence();
     plugin_levels(make(8, 0, {{CIP_CONE_R, 8}}, 1.0));
     plugin_levels(make(10, 2, {{CIP_CONE_R, 4}, {CIP_CONE_Q, 6}}, 0.4));
     plugin_levels(make(12, 3, {{CIP_CONE_R, 5}, {CIP_CONE_Q, 5}, {CIP_CONE_S, 6}}, 1.0, CIP_ROUTE_FULL3X3));

@@ -172,4 +172,8 @@ void fake_hip_stats(long *launches, long *emulated, long *live_bytes, long *live
     std::lock_guard<std::mutex> lk(g_mu);
     *live_allocs = (long)allocs().size();
 }
+long fake_hip_device_allocs(void) {                 // live hipMalloc'ed blocks alone (pinned host memory not counted)
+    std::lock_guard<std::mutex> lk(g_mu);
+    return (long)device_ranges().size();
+}
 }  // extern "C"

@@ -462,3 +462,28 @@ def test_csr_group_with_more_than_16_q_cones():
     lock = _solve(prs, "lockstep")
     assert all(s.status == "Optimal" for s in one), [s.status for s in one]
     _assert_identical(lock, one)
+
+
+def test_solve_fused_mode_changes_between_lockstep_calls_of_one_shape():
+    """cip_set_solve_fused between lock-step calls of one shape: with two solve blocks (order 256, block limit 128) the handles'
+    LDL' workspace holds the pre-multiplied neighbour blocks under mode 2 only, so the slab differs from call to call.  Every call
+    sizes its slabs by the walk that carves them, under the mode it runs under: each succeeds, bit-identical with the one-problem
+    loop under the same mode and limit (a slab size remembered from the first call used to refuse the second)."""
+    from cipkkt import _lib as L
+    from cipkkt.workloads import c5_batch
+    lib = L.load()
+    prs = c5_batch(count=2, n=200, seed=4100)
+    for pr in prs:
+        pr["A"] = pr["A"].toarray()                # dense R-cone QPs, n = m = 200
+    block, split, fused = lib.cip_set_solve_block_max(128), lib.cip_set_lockstep_split(1), lib.cip_set_solve_fused(-1)
+    try:
+        for mode in (0, 2, 0):
+            lib.cip_set_solve_fused(mode)
+            lock = _solve(prs, "lockstep")
+            one = _solve(prs, "threads", in_flight=1)
+            assert all(s.status == "Optimal" for s in one), [s.status for s in one]
+            _assert_identical(lock, one)
+    finally:
+        lib.cip_set_solve_fused(fused)
+        lib.cip_set_lockstep_split(split)
+        lib.cip_set_solve_block_max(block)
