@@ -438,7 +438,7 @@ static int handle_plan(const cip_problem *pr, cip_handle *h) {
     h->cs.nbigq = (int)h->st_bigq.size(); h->cs.nritems = (int)h->st_ritems.size(); h->cs.npackq = (int)h->st_packq.size();
     h->cs.ncones = pr->ncones; h->cs.nitems = (int)h->h_items.size(); h->cs.nslots = nslots; h->cs.m = m; h->cs.scal_len = soff; h->cs.has_S = has_S;
     h->cs.ns = (int)sidx.size(); h->cs.rmax = rmax; h->cs.kmax = kmax;
-    h->cs.ns_small = 0; h->cs.nlarge = 0;
+    h->cs.ns_small = 0; h->cs.rmax_small = 0; h->cs.nlarge = 0;
     h->cs.h_cones = h->h_cones.data();
     if (has_S) {
         std::vector<int> &small = h->st_small;
@@ -446,7 +446,10 @@ static int handle_plan(const cip_problem *pr, cip_handle *h) {
             if (h->h_cones[c].r >= CIP_LARGE_S_MIN) {
                 if (h->cs.nlarge == CIP_MAX_LARGE_S) { cip_set_error("more than %d S cones of order >= %d", CIP_MAX_LARGE_S, CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
                 h->cs.large_cone[h->cs.nlarge++] = c;
-            } else small.push_back(c);
+            } else {
+                small.push_back(c);
+                if (h->h_cones[c].r > h->cs.rmax_small) h->cs.rmax_small = h->h_cones[c].r;
+            }
         }
         h->cs.ns_small = (int)small.size();
         const int per = n < 64 ? n : 64;
@@ -499,7 +502,7 @@ size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras) {
     take(L, cs.d_scalar, 8);
     if (cs.has_S) {
         take(L, cs.d_sidx_small, (size_t)cs.ns_small + 1); take(L, cs.d_sidx, cs.ns);
-        take(L, cs.d_sdpws, (size_t)cs.sdp_slots * 6 * cs.rmax * cs.rmax); take(L, cs.d_sdpvec, (size_t)cs.sdp_slots * 2 * cs.kmax);
+        take(L, cs.d_sdpws, (size_t)cs.sdp_slots * CIP_SDP_WS_MATS * cs.rmax * cs.rmax); take(L, cs.d_sdpvec, (size_t)cs.sdp_slots * 2 * cs.kmax);
         take(L, cs.d_sdpflag, sdp_flag_words(cs));
     }
     // Q, G, A: contents by upload_problem (also used by cip_update_problem)

@@ -272,11 +272,12 @@ struct ConeSet {
     int ns, rmax, kmax;       // number of S cones, largest matrix order / vectorised length
     int *d_sidx;              // device: cone index of every S cone
     int sdp_slots;            // workgroup workspace slots
-    double *d_sdpws;          // sdp_slots x 6 x rmax^2
+    double *d_sdpws;          // sdp_slots x CIP_SDP_WS_MATS x rmax^2
     double *d_sdpvec;         // sdp_slots x 2 x kmax
     int *d_sdpflag;           // device int: Cholesky failure (iterate left the cone)
     // S cones of order >= 133 (sdp_large.hip): NT scaling, max-step and the Schur scaling take a multi-workgroup path
     int ns_small;             // number of S cones below that order, listed in d_sidx_small
+    int rmax_small;           // the largest matrix order among them (0: none)
     int *d_sidx_small;
     int nlarge;               // the others (at most CIP_MAX_LARGE_S)
     int large_cone[1024];     // their cone indices (CIP_MAX_LARGE_S entries)
@@ -286,6 +287,7 @@ struct ConeSet {
 #define CIP_MAX_LARGE_S 1024            // rounds 1-4: 8, round 5: 64, then 1024 -- every large cone costs 5 padded matrices (Rinv, Rinv', R, R', V) + its mat(a_i) images when they fit;
                                         // the cones' scalings are computed one after the other
 #define CIP_LARGE_S_MIN 133
+#define CIP_SDP_WS_MATS 6                 // r x r work matrices per workspace slot (one slot per workgroup of sdp.hip)
 struct LargeWs;
 int cip_sdp_large_create(int rmax_large, int nlarge, int ncols, LargeWs **out);
 void cip_sdp_large_invalidate(LargeWs *w);      // the problem's A was replaced: drop the cached mat(a_i) images

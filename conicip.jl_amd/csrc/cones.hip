@@ -16,6 +16,7 @@
 // Packed scaling storage per cone (== what the Julia shim reads off the Block elements):
 //   R: diag(F) (k)      Q: beta, w (1+k) with F = diag(-beta,beta,..) + w w'      S: R, inv(R)
 #include "cip_internal.h"
+#include "cip_sdp_numerics.h"
 #include "../../include/cipkkt.h"
 #include <math.h>
 
@@ -368,7 +369,7 @@ __global__ __launch_bounds__(256) void k_maxstep(const ConeDesc *cones, const Wo
         }
         mn = block_min(mn, sh);
         if (__syncthreads_or(nan_seen)) mn = __builtin_nan("");
-        if (!d) mn = (mn > 0) ? 0.0 : -1.0 + mn;
+        if (!d) mn = cip_maxstep_nothing(mn);
         if (tid == 0) partial[it.slot] = mn;
     } else if (cd.type == CIP_CONE_Q) {
         const QTeam tm = q_team(cones, it, cd);

@@ -15,13 +15,13 @@
 //                 multisection on the Sturm count (one shift per thread)
 //   dsdc!         element-wise when the divisor is diagonal (every division of the interior-point loop), two-sided
 //                 Jacobi with vectors otherwise (sd_jacobi_core below -- the only user left of the two-sided routine)
-// Orders 133 .. 512 take the chip-wide path of sdp_large.hip for NT scaling, max-step, congruences, Jordan products and
+// Orders 133 .. 2048 take the chip-wide path of sdp_large.hip for NT scaling, max-step, congruences, Jordan products and
 // the Schur scaling; the launchers at the end of this file split the S cones of a problem between the two.
 // R is determined only up to a signed permutation of its columns; F'F, F'(F x) and every norm the driver forms
 // are invariant under it.
 #include "cip_internal.h"
+#include "cip_sdp_numerics.h"
 #include "../../include/cipkkt.h"
-#include <math.h>
 
 // Threads per workgroup: 1024 (16 waves) for cones of order > 48, 256 otherwise.  The serial chains below are
 // instruction-issue bound with one wave per SIMD (a wave issues ~1 instruction per 4-5 cycles; measured 11 k cycles
@@ -29,52 +29,15 @@
 // waves per SIMD.  Device code uses the launch's own block size.
 #define SD_T ((int)blockDim.x)
 #define SD_TMAX 1024
-#define SD_NW (SD_T / 64)
-#ifdef SD_PROFILE
-#include <stdio.h>
-// development timers: s_memtime stamps collected in LDS, printed once at the end of the kernel
-#define SD_TICK_INIT __shared__ long sd_ts[16]; int sd_nt = 0; \
-    if (threadIdx.x == 0) sd_ts[0] = __builtin_amdgcn_s_memtime()
-#define SD_TICK(name) do { __syncthreads(); ++sd_nt; if (threadIdx.x == 0) sd_ts[sd_nt] = __builtin_amdgcn_s_memtime(); } while (0)
-#define SD_TICK_DUMP do { if (threadIdx.x == 0 && blockIdx.x == 0) { for (int i_ = 1; i_ <= sd_nt; ++i_) \
-    printf("[sd] phase %d: %ld ticks\n", i_, (long)(sd_ts[i_] - sd_ts[i_ - 1])); printf("[sd] total %ld\n", (long)(sd_ts[sd_nt] - sd_ts[0])); } } while (0)
-#else
-#define SD_TICK(name)
-#define SD_TICK_INIT
-#define SD_TICK_DUMP
-#endif
-#define SQRT2 1.4142135623730951
-#define SQRT1_2 0.7071067811865476
 
-// Workgroup barrier.  lds_only: the data exchanged lives in LDS, so only lgkmcnt has to drain -- __syncthreads() also
-// waits for every outstanding global access (vmcnt(0)), which would expose the latency of prefetched global loads at
-// every step of the serial chains below.  The argument is a compile-time constant after inlining.
-__device__ __forceinline__ void sd_sync(bool lds_only) {
-    if (lds_only) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else __syncthreads();
-}
-// Newton-refined hardware reciprocal / reciprocal square root (v_rcp_f64, v_rsq_f64 give ~2^-26; two steps reach
-// the last bits): a handful of instructions where the IEEE division / sqrt expansions cost 30-40 each.  Used where the
-// value feeds a rotation or a multiplier of a serial chain that every lane recomputes (the chains are issue-bound).
-__device__ __forceinline__ double sd_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(r, fma(-d, r, 1.0), r);
-    r = fma(r, fma(-d, r, 1.0), r);
-    return r;
-}
-__device__ __forceinline__ double sd_rsqrt(double x) {
-    double r = __builtin_amdgcn_rsq(x);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    return r;
-}
+// Workgroup barrier of the serial chains on the LDS-resident matrix (cip_sdp_numerics.h: SdSyncLds -- lgkmcnt only)
+__device__ __forceinline__ void sd_sync() { SdSyncLds()(); }
 // guarded load without a branch: the address is clamped into range (so the load can be issued unconditionally and
 // the unrolled loops below stay straight-line code), the value is masked afterwards
 __device__ __forceinline__ double sd_ld(const double *p, long stride, int i, int n) {
     const double x = p[(long)(i < n ? i : n - 1) * stride];
     return i < n ? x : 0.0;
 }
-__device__ __forceinline__ int vidx(int i, int j, int r) { return i * r - i * (i - 1) / 2 + (j - i); }   // i <= j
 
 // X (r x r, col-major) = mat(x)
 __device__ __forceinline__ void sd_mat(const double *x, long xs, double *X, int r, int ld = 0) {
@@ -145,36 +108,24 @@ __device__ void sd_gemm(double *C, const double *A, bool ta, const double *B, bo
     __syncthreads();
 }
 // in-place lower Cholesky (strict upper zeroed); *flag <- (column+1) of a non-positive pivot (left untouched otherwise)
-__device__ __forceinline__ void sd_chol(double *A, int r, int *flag, int ld = 0, bool lds = false) {
-    if (!ld) ld = r;
+// (A in LDS, pitch ld)
+__device__ __forceinline__ void sd_chol(double *A, int r, int *flag, int ld) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int j = 0; j < r; ++j) {
         const double d = A[j + j * ld];
         if (!(d > 0.0)) { if (threadIdx.x == 0) *flag = j + 1; }
         const double l = sqrt(d);
-        sd_sync(lds);
+        sd_sync();
         for (int i = j + threadIdx.x; i < r; i += SD_T) A[i + j * ld] = (i == j) ? l : A[i + j * ld] / l;
-        sd_sync(lds);
+        sd_sync();
         for (int k = j + 1 + wave; k < r; k += SD_T / 64) {                 // one wave per trailing column
             const double akj = A[k + j * ld];
             for (int i = k + lane; i < r; i += 64) A[i + k * ld] -= A[i + j * ld] * akj;
         }
-        sd_sync(lds);
+        sd_sync();
     }
     for (int e = threadIdx.x; e < r * r; e += SD_T) if (e % r < e / r) A[e % r + (e / r) * ld] = 0.0;
-    sd_sync(lds);
-}
-// X <- L^-T X  (L lower), column per thread
-__device__ void sd_solve_LT(const double *L, double *X, int r) {
-    for (int c = threadIdx.x; c < r; c += SD_T) {
-        double *x = X + c * r;
-        for (int i = r - 1; i >= 0; --i) {
-            double s = x[i];
-            for (int k = i + 1; k < r; ++k) s -= L[k + i * r] * x[k];
-            x[i] = s / L[i + i * r];
-        }
-    }
-    __syncthreads();
+    sd_sync();
 }
 // Two-sided Jacobi, parallel (round-robin) ordering.  A (symmetric) is destroyed: eigenvalues end on its
 // diagonal; V (may be NULL) receives the eigenvectors as columns: A_in = V diag V'.
@@ -202,7 +153,7 @@ __device__ void sd_jacobi_core(double *A, double *V, int r, double *sh /* >= 4*(
         if ((tid & 63) == 0) { red[tid >> 6] = off; red[16 + (tid >> 6)] = tot; }
         __syncthreads();
         off = 0.0; tot = 0.0;
-        for (int q = 0; q < SD_NW; ++q) { off += red[q]; tot += red[16 + q]; }
+        for (int q = 0; q < SD_T / 64; ++q) { off += red[q]; tot += red[16 + q]; }
         if (off <= 1e-30 * tot || tot == 0.0) break;
         for (int t = 0; t < m - 1; ++t) {
             for (int k = tid; k < np; k += SD_T) {
@@ -278,10 +229,8 @@ __device__ void sd_jacobi(double *A, double *V, int r, double *sh, int cap) {
 // B <- L^-1 B  (L lower r x r pitch ldl, B r x r pitch ldb): right-looking by rows.  Lanes own rows, waves own
 // columns: a lane fetches its entries of column j of L once per step (L may sit in global memory while B is in LDS)
 // and reuses them for every column of B; the next step's entries are fetched before the barrier.
-#define SD_RPL 8                                             // rows per lane kept in registers: r <= 512
-__device__ __forceinline__ void sd_trsm_l(const double *L, double *B, int r, int ldl = 0, int ldb = 0, bool lds = false) {
-    if (!ldl) ldl = r;
-    if (!ldb) ldb = r;
+#define SD_RPL 8                                             // rows per lane kept in registers: 64 lanes x 8 cover every small cone (r <= 132)
+__device__ __forceinline__ void sd_trsm_l(const double *L, double *B, int r, int ldl, int ldb) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double lcol[SD_RPL];
 #pragma unroll
@@ -320,14 +269,12 @@ __device__ __forceinline__ void sd_trsm_l(const double *L, double *B, int r, int
                 for (int u = 0; u < 4; ++u) if (c0 + u < r) B[j + (long)(c0 + u) * ldb] = bj[u];
             }
         }
-        sd_sync(lds);
+        sd_sync();
     }
 }
 // B <- L^-T B: the same from the last row upwards; row j of L' is column j of L, so a lane's multipliers L[j][i]
 // (i < j) are a strided row of L: fetched once per step as well
-__device__ __forceinline__ void sd_trsm_lt(const double *L, double *B, int r, int ldl = 0, int ldb = 0, bool lds = false) {
-    if (!ldl) ldl = r;
-    if (!ldb) ldb = r;
+__device__ __forceinline__ void sd_trsm_lt(const double *L, double *B, int r, int ldl, int ldb) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double lrow[SD_RPL];
 #pragma unroll
@@ -366,33 +313,23 @@ __device__ __forceinline__ void sd_trsm_lt(const double *L, double *B, int r, in
                 for (int u = 0; u < 4; ++u) if (c0 + u < r) B[j + (long)(c0 + u) * ldb] = bj[u];
             }
         }
-        sd_sync(lds);
+        sd_sync();
     }
 }
-__device__ __forceinline__ void sd_transpose(double *A, int r, int ld = 0, bool lds = false) {
-    if (!ld) ld = r;
+__device__ __forceinline__ void sd_transpose(double *A, int r, int ld) {
     for (int e = threadIdx.x; e < r * r; e += SD_T) {
         const int i = e % r, j = e / r;
         if (i < j) { const double a = A[i + j * ld], b = A[j + i * ld]; A[i + j * ld] = b; A[j + i * ld] = a; }
     }
-    sd_sync(lds);
+    sd_sync();
 }
 
 // ---- extreme eigenvalue of a symmetric matrix: Householder tridiagonalisation + multisection on the Sturm count.
 // maxstep_sdc needs only the largest eigenvalue of X^-1/2 D X^-1/2 (or the smallest of X) (:272-303): r^3 4/3 flops
 // and r barrier-separated steps instead of ~10 Jacobi sweeps of 3 (r - 1) steps each.
 #define SD_SCRATCH_TRI(r) (4 * (r) + SD_TMAX + 48)
-__device__ __forceinline__ double sd_block_sum(double x, double *red) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    sd_sync(true);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    sd_sync(true);
-    double sum = 0.0;
-    for (int q = 0; q < SD_NW; ++q) sum += red[q];
-    return sum;
-}
-// A (full symmetric storage, pitch ld, destroyed).  sc: SD_SCRATCH_TRI(r) doubles of LDS.  Result returned to all threads.
-__device__ __forceinline__ double sd_extreme_eig(double *A, int r, int ld, double *sc, bool want_max, bool lds = false) {
+// A (full symmetric storage in LDS, pitch ld, destroyed).  sc: SD_SCRATCH_TRI(r) doubles of LDS.  Result returned to all threads.
+__device__ __forceinline__ double sd_extreme_eig(double *A, int r, int ld, double *sc, bool want_max) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double *dg = sc, *of = sc + r, *v = sc + 2 * r, *w = sc + 3 * r, *pb = sc + 4 * r, *red = sc + 4 * r + SD_TMAX;
     for (int k = 0; k + 1 < r; ++k) {
@@ -401,19 +338,19 @@ __device__ __forceinline__ double sd_extreme_eig(double *A, int r, int ld, doubl
         double *A22 = A + (k + 1) + (long)(k + 1) * ld;
         double part = 0.0;
         for (int i = tid; i < m; i += SD_T) part += x[i] * x[i];
-        const double sigma = sd_block_sum(part, red);
+        const double sigma = sd_block_sum(part, red, SD_T / 64, SdSyncLds());
         const double x0 = x[0];
         if (tid == 0) dg[k] = A[k + (long)k * ld];
-        if (m == 1 || !(sigma - x0 * x0 > 0.0)) {               // already tridiagonal in this column (uniform branch)
+        const SdReflector h = sd_reflector(sigma, x0, m == 1);
+        if (h.flat) {                                           // already tridiagonal in this column (uniform branch)
             if (tid == 0) of[k] = x0;
-            sd_sync(lds);
+            sd_sync();
             continue;
         }
-        const double alpha = -copysign(sqrt(sigma), x0);
-        const double beta = 1.0 / (sigma - x0 * alpha);        // 2 / ||v||^2 with v = x - alpha e1
+        const double alpha = h.alpha, beta = h.beta;           // v = x - alpha e1
         for (int i = tid; i < m; i += SD_T) v[i] = x[i] - (i == 0 ? alpha : 0.0);
         if (tid == 0) of[k] = alpha;
-        sd_sync(lds);
+        sd_sync();
         // p = beta A22 v, as a sum of columns (rows on consecutive lanes); the column range is split over the
         // workgroup's spare threads and combined through pb
         int mp = 64;
@@ -432,19 +369,19 @@ __device__ __forceinline__ double sd_extreme_eig(double *A, int r, int ld, doubl
                 }
             }
             pb[tid] = acc;
-            sd_sync(lds);
+            sd_sync();
             if (tid < mp && i < m) {
                 double sum = 0.0;
                 for (int q = 0; q < nparts; ++q) sum += pb[q * mp + tid];
                 w[i] = beta * sum;
             }
-            sd_sync(lds);
+            sd_sync();
         }
         part = 0.0;
         for (int i = tid; i < m; i += SD_T) part += v[i] * w[i];
-        const double kk = 0.5 * beta * sd_block_sum(part, red);
+        const double kk = 0.5 * beta * sd_block_sum(part, red, SD_T / 64, SdSyncLds());
         for (int i = tid; i < m; i += SD_T) w[i] -= kk * v[i];
-        sd_sync(lds);
+        sd_sync();
         {                                                       // A22 -= v w' + w v': lanes own rows, four columns per pass
             double vi[SD_RPL], wi[SD_RPL];
 #pragma unroll
@@ -466,63 +403,22 @@ __device__ __forceinline__ double sd_extreme_eig(double *A, int r, int ld, doubl
                 }
             }
         }
-        sd_sync(lds);
+        sd_sync();
     }
     if (tid == 0) { dg[r - 1] = A[(r - 1) + (long)(r - 1) * ld]; of[r - 1] = 0.0; }
-    sd_sync(lds);
-    // Gershgorin interval
-    double lo = __builtin_inf(), hi = -__builtin_inf();
-    for (int i = tid; i < r; i += SD_T) {
-        const double rad = (i > 0 ? fabs(of[i - 1]) : 0.0) + (i + 1 < r ? fabs(of[i]) : 0.0);
-        lo = fmin(lo, dg[i] - rad);
-        hi = fmax(hi, dg[i] + rad);
-    }
-    for (int o = 32; o > 0; o >>= 1) { lo = fmin(lo, __shfl_xor(lo, o)); hi = fmax(hi, __shfl_xor(hi, o)); }
-    sd_sync(lds);
-    if (lane == 0) { red[wave] = lo; red[16 + wave] = hi; }
-    sd_sync(lds);
-    lo = red[0]; hi = red[16];
-    for (int q = 1; q < SD_NW; ++q) { lo = fmin(lo, red[q]); hi = fmax(hi, red[16 + q]); }
-    const double span = fmax(fabs(lo), fabs(hi));
-    hi += 1e-15 * span + 1e-300;                               // the count at hi must be r, at lo 0
-    lo -= 1e-15 * span + 1e-300;
-    int *first = (int *)(red + 40);
-    for (int round = 0; round < 12; ++round) {
-        if (!(hi - lo > 4.4e-16 * fmax(fabs(lo), fabs(hi)))) break;
-        const double step = (hi - lo) / (SD_T + 1);
-        const double xs = lo + step * (tid + 1);
-        // Sturm count: number of eigenvalues below xs
-        int cnt = 0;
-        double q = dg[0] - xs;
-        if (q < 0.0) ++cnt;
-        for (int i = 1; i < r; ++i) {
-            if (q == 0.0) q = 1e-300;
-            q = (dg[i] - xs) - of[i - 1] * of[i - 1] / q;
-            if (q < 0.0) ++cnt;
-        }
-        const bool hit = want_max ? (cnt >= r) : (cnt >= 1);   // monotone in tid
-        if (tid == 0) *first = SD_T;
-        sd_sync(lds);
-        if (hit) atomicMin(first, tid);
-        sd_sync(lds);
-        const int f = *first;
-        sd_sync(lds);
-        const double nlo = (f == 0) ? lo : lo + step * f;       // x_{f-1}
-        const double nhi = (f == SD_T) ? hi : lo + step * (f + 1);
-        lo = nlo; hi = nhi;
-    }
-    return 0.5 * (lo + hi);
+    sd_sync();
+    return sd_tridiag_extreme(dg, of, r, want_max, SD_T, red, (int *)(red + 40), SdSyncLds());
 }
 
 // LDS pitch of the one-sided Jacobi's matrix: == 4 (mod 32) doubles, so that the 8 column pairs x 4 row-interleaved
 // lanes of a half-wave (columns p, p+1, ... of consecutive pairs) fall on 32 different 8-byte bank pairs
-__host__ __device__ __forceinline__ int sd_pitch(int r) { return r + ((4 - r % 32) + 32) % 32; }
+__host__ __device__ constexpr int sd_pitch(int r) { return r + ((4 - r % 32) + 32) % 32; }
 // One-sided (Hestenes) Jacobi: right rotations until the columns of G (r x r, ld) are mutually orthogonal:
 // G_in V = U diag(sigma), i.e. column i ends as sigma_i u_i -- the left singular vectors and singular values of
 // G_in, which is all nestod_sdc needs of svd(Lz' Ls) (src/ConicIP.jl:204-208).  Only ONE matrix is live, so r = 128
 // (padded pitch 129: the 64 column pairs of a round then fall on different LDS banks) stays LDS-resident.  A round
 // rotates r/2 disjoint column pairs at once, `tpp` lanes per pair, one barrier per round.
-__device__ __forceinline__ void sd_jacobi_onesided(double *G, int r, int ld, int *sflag, bool lds = false) {
+__device__ __forceinline__ void sd_jacobi_onesided(double *G, int r, int ld, int *sflag) {
     const int tid = threadIdx.x;
     const int m = (r + 1) & ~1, np = m / 2;
     int tpp = 1;
@@ -531,7 +427,7 @@ __device__ __forceinline__ void sd_jacobi_onesided(double *G, int r, int ld, int
     const int part = tid % tpp;
     for (int sweep = 0; sweep < 40; ++sweep) {
         if (tid == 0) *sflag = 0;
-        sd_sync(lds);
+        sd_sync();
         for (int t = 0; t < m - 1; ++t) {
             for (int k = tid / tpp; k < np; k += ngroups) {
                 int p, q;
@@ -594,46 +490,49 @@ __device__ __forceinline__ void sd_jacobi_onesided(double *G, int r, int ld, int
                     if (part == 0) *sflag = 1;
                 }
             }
-            sd_sync(lds);
+            sd_sync();
         }
         const int again = *sflag;
-        sd_sync(lds);
+        sd_sync();
         if (!again) break;
     }
 }
 
-// workspace of one workgroup: NW r x r matrices
-#define SD_NW 6
+// workspace of one workgroup: CIP_SDP_WS_MATS r x r matrices
 __device__ __forceinline__ double *sd_ws(double *base, int slot, int r, int which) {
-    return base + ((size_t)slot * SD_NW + which) * (size_t)r * r;
+    return base + ((size_t)slot * CIP_SDP_WS_MATS + which) * (size_t)r * r;
 }
 
 // ---------------------------------------------------------------------------------- NT scaling
-// The body is inlined twice (live matrix W in LDS / in global memory) so that the LDS instance is compiled to ds_*
-// instructions: a pointer selected at run time between the two address spaces makes every access a FLAT one
-// (measured: 6.6 ms instead of sub-millisecond for the one-sided Jacobi at r = 128).
-__device__ __forceinline__ void sd_nt_body(const ConeDesc &cd, const double *v, const double *s, double *R, double *Ri,
-                                           double *lambda, double *Z, double *S, double *T, double *U, double *W, int ld,
-                                           int *flag, int *sflagp, bool lds) {
-    const int r = cd.r;
-    SD_TICK_INIT;
+// Every O(r^3) stage with a serial chain works on ONE matrix at a time: W, LDS-resident at pitch sd_pitch(r) (the launcher
+// sizes the dynamic LDS for the largest cone this kernel is launched on); the finished factor is parked in global memory for
+// the next stage.  (W must be LDS by type, not by a run-time choice: a pointer selected between the two address spaces makes
+// every access a FLAT one -- measured: 6.6 ms instead of sub-millisecond for the one-sided Jacobi at r = 128.)
+__global__ __launch_bounds__(SD_TMAX) void k_sdp_nt_scaling(const ConeDesc *cones, const int *sidx, const double *v,
+                                                          const double *s, double *scal, double *lambda, double *wsb,
+                                                          int *flag, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO6(cb, v, s, scal, lambda, wsb, flag);
+    extern __shared__ double sh[];
+    __shared__ int sflag;
+    const ConeDesc cd = cones[sidx[blockIdx.x]];
+    const int r = cd.r, ld = sd_pitch(r);
+    double *Z = sd_ws(wsb, blockIdx.x, r, 0), *S = sd_ws(wsb, blockIdx.x, r, 1), *T = sd_ws(wsb, blockIdx.x, r, 2),
+           *U = sd_ws(wsb, blockIdx.x, r, 4);
+    double *R = scal + cd.soff, *Ri = R + (size_t)r * r;
+    double *W = sh;
     sd_mat(v + cd.off, 1, W, r, ld);
-    SD_TICK("nt mat");
-    sd_chol(W, r, flag, ld, lds);                                       // Lz     (src/ConicIP.jl:202-203)
-    SD_TICK("nt chol");
+    sd_chol(W, r, flag, ld);                                    // Lz     (src/ConicIP.jl:202-203)
     for (int e = threadIdx.x; e < r * r; e += SD_T) Z[e] = W[e % r + (e / r) * ld];
     __syncthreads();
     sd_mat(s + cd.off, 1, W, r, ld);
-    sd_chol(W, r, flag, ld, lds);                                       // Ls
+    sd_chol(W, r, flag, ld);                                    // Ls
     for (int e = threadIdx.x; e < r * r; e += SD_T) S[e] = W[e % r + (e / r) * ld];
     __syncthreads();
-    SD_TICK("nt chol2+copy");
     sd_gemm(U, Z, true, S, false, r);                              // G = Lz' Ls = U Lambda V'   (:204)
-    SD_TICK("nt gemm");
     for (int e = threadIdx.x; e < r * r; e += SD_T) W[e % r + (e / r) * ld] = U[e];
     __syncthreads();
-    sd_jacobi_onesided(W, r, ld, sflagp, lds);                          // column i = Lambda_i u_i
-    SD_TICK("nt jacobi1");
+    sd_jacobi_onesided(W, r, ld, &sflag);                     // column i = Lambda_i u_i
     double *lam = S;                                               // Ls is no longer needed: first r entries hold Lambda
     for (int i = threadIdx.x; i < r; i += SD_T) {
         double n2 = 0.0;
@@ -649,38 +548,17 @@ __device__ __forceinline__ void sd_nt_body(const ConeDesc &cd, const double *v, 
     }
     __syncthreads();
     // R = Lz^-T U Lambda^(1/2) (:206-208);  Rinv = Lambda^(-1/2) U' Lz'
-    SD_TICK("nt lam/U");
-    sd_trsm_lt(Z, W, r, r, ld, lds);                                    // Lz^-T U
-    SD_TICK("nt trsm_lt");
+    sd_trsm_lt(Z, W, r, r, ld);                                 // Lz^-T U
     for (int e = threadIdx.x; e < r * r; e += SD_T) R[e] = W[e % r + (e / r) * ld] * sqrt(lam[e / r]);
     __syncthreads();
     sd_gemm(T, U, true, Z, true, r);                               // U' Lz'
     for (int e = threadIdx.x; e < r * r; e += SD_T) Ri[e] = T[e] / sqrt(lam[e % r]);
-    SD_TICK("nt gemm2+Ri");
-    SD_TICK_DUMP;
     if (lambda) {
         // lambda = F v = vecm(R' Z R) = vecm(diag(Lambda))
         for (int e = threadIdx.x; e < cd.dim; e += SD_T) lambda[cd.off + e] = 0.0;
         __syncthreads();
         for (int i = threadIdx.x; i < r; i += SD_T) lambda[cd.off + vidx(i, i, r)] = lam[i];
     }
-}
-__global__ __launch_bounds__(SD_TMAX) void k_sdp_nt_scaling(const ConeDesc *cones, const int *sidx, const double *v,
-                                                          const double *s, double *scal, double *lambda, double *wsb,
-                                                          int *flag, int cap, CipBatch cb) {
-    CIP_BATCH_GUARD(cb);
-    CIP_BO6(cb, v, s, scal, lambda, wsb, flag);
-    extern __shared__ double sh[];
-    __shared__ int sflag;
-    const ConeDesc cd = cones[sidx[blockIdx.x]];
-    const int r = cd.r;
-    double *Z = sd_ws(wsb, blockIdx.x, r, 0), *S = sd_ws(wsb, blockIdx.x, r, 1), *T = sd_ws(wsb, blockIdx.x, r, 2),
-           *U = sd_ws(wsb, blockIdx.x, r, 4);
-    double *R = scal + cd.soff, *Ri = R + (size_t)r * r;
-    // Every O(r^3) stage with a serial chain works on ONE matrix at a time, LDS-resident (pitch r + 1) when
-    // r (r + 1) doubles fit; the finished factor is parked in global memory for the next stage.
-    if (r * sd_pitch(r) <= cap) sd_nt_body(cd, v, s, R, Ri, lambda, Z, S, T, U, sh, sd_pitch(r), flag, &sflag, true);
-    else sd_nt_body(cd, v, s, R, Ri, lambda, Z, S, T, U, T, r, flag, &sflag, false);
 }
 
 // out = vecm(P' X P) with P = R (F), R' (F'), Rinv (F^-1), Rinv' (F^-T); x / out strided (xs, os)
@@ -809,62 +687,60 @@ __global__ __launch_bounds__(SD_TMAX) void k_sdp_div(const ConeDesc *cones, cons
 // ---------------------------------------------------------------------------------- max step
 // eigvals(X^-1/2 D X^-1/2) (:272-293) are the eigenvalues of L^-1 D L^-T with X = L L' (the two matrices are
 // similar through the orthogonal X^-1/2 L), and only the largest is used: one Cholesky, two triangular solves, one
-// tridiagonalisation + bisection -- with the ONE live matrix LDS-resident (pitch r + 1) up to r = 139 -- instead of
+// tridiagonalisation + bisection -- with the ONE live matrix M LDS-resident (pitch r + 1) behind the tridiagonalisation's
+// scratch (the launcher sizes the dynamic LDS for the largest cone this kernel is launched on) -- instead of
 // an eigendecomposition with vectors, three GEMMs and a second Jacobi, all in global memory at r = 128 (80 ms per
-// call -> see DESIGN.md).  `cap` = doubles of dynamic LDS behind the scratch.
-__device__ __forceinline__ void sd_maxstep_body(const ConeDesc &cd, const double *x, const double *d, double scale,
-                                                double *partial, double *Lg, double *M, int ld, double *sc, int *sflagp, bool lds) {
-    const int r = cd.r;
-    const double INF = __builtin_inf();
-    SD_TICK_INIT;
-    sd_mat(x + cd.off, 1, M, r, ld);
-    if (!d) {                                                // maxstep_sdc(x, nothing) :295-303
-        const double mn = sd_extreme_eig(M, r, ld, sc, false, lds);
-        if (threadIdx.x == 0) partial[cd.item] = (mn > 0.0) ? 0.0 : -1.0 + mn;
-        return;
-    }
-    if (threadIdx.x == 0) *sflagp = 0;
-    __syncthreads();
-    sd_chol(M, r, sflagp, ld, lds);                               // M <- L
-    if (*sflagp) {                                           // X not PD -> Inf (:277-280)
-        if (threadIdx.x == 0) partial[cd.item] = INF;
-        return;
-    }
-    for (int e = threadIdx.x; e < r * r; e += SD_T) Lg[e] = M[e % r + (e / r) * ld];
-    __syncthreads();
-    sd_mat(d + cd.off, 1, M, r, ld);
-    SD_TICK("ms chol+copy+mat");
-    sd_trsm_l(Lg, M, r, r, ld, lds);                              // L^-1 D
-    SD_TICK("ms trsm1");
-    sd_transpose(M, r, ld, lds);                                  // D L^-T
-    sd_trsm_l(Lg, M, r, r, ld, lds);                              // L^-1 D L^-T
-    SD_TICK("ms trsm2");
-    for (int e = threadIdx.x; e < r * r; e += SD_T) {
-        const int i = e % r, j = e / r;
-        if (i > j) { const double a = 0.5 * (M[i + j * ld] + M[j + i * ld]); M[i + j * ld] = a; M[j + i * ld] = a; }
-    }
-    __syncthreads();
-    const double mx = sd_extreme_eig(M, r, ld, sc, true, lds) * scale;
-    SD_TICK("ms tridiag+bis");
-    SD_TICK_DUMP;
-    if (threadIdx.x == 0) partial[cd.item] = (mx < 0.0) ? INF : 1.0 / mx;
-}
+// call -> see DESIGN.md).
 __global__ __launch_bounds__(SD_TMAX) void k_sdp_maxstep(const ConeDesc *cones, const int *sidx, const double *x, const double *d,
-                                                       double scale, double *partial, double *wsb, int cap, CipBatch cb) {
+                                                       double scale, double *partial, double *wsb, CipBatch cb) {
     CIP_BATCH_GUARD(cb);
     CIP_BO4(cb, x, d, partial, wsb);
     extern __shared__ double sh[];
     __shared__ int sflag;
     const ConeDesc cd = cones[sidx[blockIdx.x]];
-    const int r = cd.r;
+    const int r = cd.r, ld = r + 1;
     double *Lg = sd_ws(wsb, blockIdx.x, r, 0);               // L in global memory (pitch r)
-    if (r * (r + 1) <= cap) sd_maxstep_body(cd, x, d, scale, partial, Lg, sh + SD_SCRATCH_TRI(r), r + 1, sh, &sflag, true);
-    else sd_maxstep_body(cd, x, d, scale, partial, Lg, sd_ws(wsb, blockIdx.x, r, 2), r, sh, &sflag, false);
+    double *sc = sh, *M = sh + SD_SCRATCH_TRI(r);
+    sd_mat(x + cd.off, 1, M, r, ld);
+    if (!d) {                                                // maxstep_sdc(x, nothing) :295-303
+        const double mn = sd_extreme_eig(M, r, ld, sc, false);
+        if (threadIdx.x == 0) partial[cd.item] = sd_maxstep_verdict(false, mn, 1.0);
+        return;
+    }
+    if (threadIdx.x == 0) sflag = 0;
+    __syncthreads();
+    sd_chol(M, r, &sflag, ld);                               // M <- L
+    if (sflag) {                                             // X not PD -> Inf (:277-280)
+        if (threadIdx.x == 0) partial[cd.item] = __builtin_inf();
+        return;
+    }
+    for (int e = threadIdx.x; e < r * r; e += SD_T) Lg[e] = M[e % r + (e / r) * ld];
+    __syncthreads();
+    sd_mat(d + cd.off, 1, M, r, ld);
+    sd_trsm_l(Lg, M, r, r, ld);                              // L^-1 D
+    sd_transpose(M, r, ld);                                  // D L^-T
+    sd_trsm_l(Lg, M, r, r, ld);                              // L^-1 D L^-T
+    for (int e = threadIdx.x; e < r * r; e += SD_T) {
+        const int i = e % r, j = e / r;
+        if (i > j) { const double a = 0.5 * (M[i + j * ld] + M[j + i * ld]); M[i + j * ld] = a; M[j + i * ld] = a; }
+    }
+    __syncthreads();
+    const double mx = sd_extreme_eig(M, r, ld, sc, true);
+    if (threadIdx.x == 0) partial[cd.item] = sd_maxstep_verdict(true, mx, scale);
 }
 
 // ---------------------------------------------------------------------------------- host launchers
+// (by the handle's largest S cone, a large one included: the thread count sets the shifts per multisection round and the
+//  lanes per rotation, and so the bits)
 static int sd_threads(int rmax) { return rmax > 48 ? 1024 : 256; }
-// dynamic LDS: rotation scratch + up to `nmat` matrices of the largest cone (pitch r+1 allowed for), capped
+// Dynamic LDS of the two kernels that keep a small cone's live matrix resident, for the largest SMALL cone of the handle (a
+// large neighbour has no say in it): the matrix at its pitch, for the max-step behind the tridiagonalisation's scratch.
+// Every order below CIP_LARGE_S_MIN fits.
+static size_t sd_nt_lds(int r) { return (size_t)r * sd_pitch(r) * sizeof(double); }
+static size_t sd_maxstep_lds(int r) { return ((size_t)SD_SCRATCH_TRI(r) + (size_t)r * (r + 1)) * sizeof(double); }
+static_assert((CIP_LARGE_S_MIN - 1) * sd_pitch(CIP_LARGE_S_MIN - 1) <= SD_LDS_CAPMAX &&
+              SD_SCRATCH_TRI(CIP_LARGE_S_MIN - 1) + (CIP_LARGE_S_MIN - 1) * CIP_LARGE_S_MIN <= SD_LDS_CAPMAX, "a small cone's matrix must fit the LDS");
+// k_sdp_div (cones of every order): rotation scratch + up to `nmat` matrices of the largest cone (pitch r+1 allowed for), capped
 static int sd_cap(int rmax, int nmat) {
     const int pitch = sd_pitch(rmax) > rmax + 1 ? sd_pitch(rmax) : rmax + 1;
     const long want = (long)nmat * rmax * pitch;
@@ -879,12 +755,13 @@ static int sd_set_lds_attr(const void *fn, int rmax, int nmat) {
 
 int cip_sdp_nt_scaling(hipStream_t s, const ConeSet &cs, const double *v, const double *sv, double *lambda) {
     if (cs.ns_small > 0) {
-        if (sd_set_lds_attr((const void *)k_sdp_nt_scaling, cs.rmax, 1)) return -3;
-        cip_launch_b(k_sdp_nt_scaling, dim3(cs.ns_small), dim3(sd_threads(cs.rmax)), sd_shmem(cs.rmax, 1), s, cs.d_cones,
-                           cs.d_sidx_small, v, sv, cs.d_scal, lambda, cs.d_sdpws, cs.d_sdpflag, sd_cap(cs.rmax, 1) + SD_SCRATCH(cs.rmax));
+        const size_t shm = sd_nt_lds(cs.rmax_small);
+        CIP_HIP_CHECK(hipFuncSetAttribute((const void *)k_sdp_nt_scaling, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+        cip_launch_b(k_sdp_nt_scaling, dim3(cs.ns_small), dim3(sd_threads(cs.rmax)), shm, s, cs.d_cones,
+                           cs.d_sidx_small, v, sv, cs.d_scal, lambda, cs.d_sdpws, cs.d_sdpflag);
         CIP_HIP_CHECK(hipGetLastError());
     }
-    for (int li = 0; li < cs.nlarge; ++li) {                 // orders 133 .. 512: chip-wide pieces (sdp_large.hip)
+    for (int li = 0; li < cs.nlarge; ++li) {                 // orders 133 .. 2048: chip-wide pieces (sdp_large.hip)
         const int rc = cip_sdp_large_nt(s, cs.lg, cs.h_cones[cs.large_cone[li]], li, v, sv, cs.d_scal, lambda, cs.d_sdpflag);
         if (rc) return rc;
     }
@@ -948,14 +825,11 @@ int cip_sdp_div(hipStream_t s, const ConeSet &cs, const double *x, const double 
     return 0;
 }
 int cip_sdp_maxstep(hipStream_t s, const ConeSet &cs, const double *x, const double *d, double scale, double *partial) {
-    // scratch of the tridiagonalisation + one matrix of pitch r + 1 when it fits
-    const long want = (long)cs.rmax * (cs.rmax + 1), room = SD_LDS_CAPMAX - SD_SCRATCH_TRI(cs.rmax);
-    const int cap = (int)(want < room ? want : (room > 0 ? room : 0));
-    const size_t shm = ((size_t)SD_SCRATCH_TRI(cs.rmax) + cap) * sizeof(double);
     if (cs.ns_small > 0) {
+        const size_t shm = sd_maxstep_lds(cs.rmax_small);
         CIP_HIP_CHECK(hipFuncSetAttribute((const void *)k_sdp_maxstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
         cip_launch_b(k_sdp_maxstep, dim3(cs.ns_small), dim3(sd_threads(cs.rmax)), shm, s, cs.d_cones, cs.d_sidx_small, x, d, scale,
-                           partial, cs.d_sdpws, cap);
+                           partial, cs.d_sdpws);
         CIP_HIP_CHECK(hipGetLastError());
     }
     for (int li = 0; li < cs.nlarge; ++li) {

@@ -1,4 +1,4 @@
-// S cones of matrix order 133 .. 512: the stages that do not fit one workgroup's LDS.
+// S cones of matrix order 133 .. 2048: the stages that do not fit one workgroup's LDS.
 //
 // The workgroup-per-cone kernels of sdp.hip keep ONE r x r matrix LDS-resident up to r = 132; above that they ran the
 // same serial chains from global memory (BASELINE config 4 at its literal size, r = 256: 67 ms per NT scaling, 10.9 ms
@@ -6,36 +6,40 @@
 //
 //   nestod_sdc  (src/ConicIP.jl:196-210)
 //       chol(mat(z)), chol(mat(s))        the library's own blocked LDL' (ldlt.hip: MFMA trailing updates) on the matrix
-//                                         padded to 256 / 512 with an identity block; L_chol = L D^1/2
-//       G = Lz' Ls                        one fp64-MFMA GEMM (64x64 tiles over the chip)
-//       svd(G): U, Lambda                 BLOCK one-sided Jacobi: column blocks of 32 (16 above r = 256), disjoint block
-//                                         pairs on different workgroups (a pair = 128 KB of LDS), a full inner sweep per
-//                                         pair, rounds separated by a grid barrier inside ONE persistent launch
+//                                         padded to 256 / 512 / 1024 / 2048 with an identity block; L_chol = L D^1/2
+//       G = Lz' Ls                        one fp64-MFMA GEMM (64x64 tiles over the chip; 16x16 split-k tiles at order 256)
+//       svd(G): U, Lambda                 BLOCK one-sided Jacobi (k_lg_jacobi): column blocks of 8 / 16 / 8 / 4 at the four
+//                                         padded orders, disjoint block pairs on different workgroups (a pair = 128 KB of
+//                                         LDS), a full inner sweep per pair, ONE LAUNCH PER PHASE: the launch boundary
+//                                         orders the rounds of the tournament over blocks
 //       R = Lz^-T U Lambda^1/2, R^-1      GEMMs with the explicit inverse of the unit-lower factor (the block inverses the
 //                                         LDL' builds for its solves: one block = the whole matrix here)
 //   maxstep_sdc (src/ConicIP.jl:272-303)
-//       lambda_max(L^-1 D L^-T)           LDL' + two GEMMs with inv(L), then a COOPERATIVE Householder tridiagonalisation:
-//                                         each of r/32 workgroups keeps a 32-column slab of the matrix in LDS for the whole
-//                                         reduction; per column two grid barriers and two r-vectors through global memory
-//                                         (coherent 8-byte accesses); Sturm multisection as before
+//       lambda_max(L^-1 D L^-T)           LDL' + two GEMMs with inv(L), then the extreme eigenvalue by
+//                                         order <= 256   Lanczos with the matrix in one workgroup's registers (k_lg_lanczos1)
+//                                                        + an inertia certificate; its fallback, and CIP_LG_LANCZOS=0, is a
+//                                                        Householder tridiagonalisation in registers (k_lg_tridiag1)
+//                                         <= 1024        a COOPERATIVE Householder tridiagonalisation (k_lg_tridiag): each
+//                                                        workgroup keeps a slab of 32 or 16 columns in LDS for the whole
+//                                                        reduction; per column one grid barrier and two r-vectors through
+//                                                        global memory (coherent 8-byte accesses)
+//                                         above          the matrix in global memory, two launches per column (k_tg_*)
+//                                         and, behind every tridiagonalisation, Sturm multisection (k_lg_sturm)
 //   A' F^-1 for the Schur complement (Block * matrix, src/blockmatrices.jl:176-177; src/kktsolvers.jl:289-290)
-//       vecm(Rinv mat(a_i) Rinv') for all columns i: two BATCHED MFMA GEMMs per chunk of 64 columns
+//       vecm(Rinv mat(a_i) Rinv') for all columns i: two BATCHED MFMA GEMMs per chunk of columns
 //
-// apply / product / division stay on the workgroup-per-cone kernels (one or two r^3 GEMMs each, 0.1-0.3 ms at r = 256).
+// apply and product are two and one chip-wide GEMMs, the division by a diagonal element is element-wise; the general
+// division stays on the workgroup-per-cone kernel of sdp.hip.
 #include "cip_handle.h"
 #include "cip_gemm_tile.h"
+#include "cip_sdp_numerics.h"
 #include "../../include/cipkkt.h"
-#include <math.h>
-#include <vector>
 #include <atomic>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 #include <thread>
 
 #define LG_T 1024
-#define LG_SQRT2 1.4142135623730951
-#define LG_SQRT1_2 0.7071067811865476
 
 __device__ int g_lz_hist[40];           // k_lg_lanczos1: histogram of step counts (bins of 8)
 #define LG_NPAD 4
@@ -46,7 +50,6 @@ enum {                                 // LG_V_SLOTS slots of rp doubles
     LG_V_DG = 1, LG_V_OF = 2,          // the tridiagonal of side 0: both tridiagonalisations and the side-0 certificate fallback
     LG_V_XBUF = 3, LG_V_PBUF = 5,      // two slots each: xbuf (cooperative tridiagonalisation) / vbuf (stepped form), pbuf of both
     LG_V_SCAL = 7,                     // the stepped form's scalars
-    LG_V_UNUSED = 8,
     LG_V_DG1 = 9, LG_V_OF1 = 10,       // the tridiagonal of side 1: its certificate fallback
     LG_V_CERT = 11, LG_V_SLOTS = 12    // doubles 2 side, 2 side + 1: the certificate pair of `side`; double 8, as unsigned: fallbacks taken
 };
@@ -57,7 +60,7 @@ enum {                                 // LG_C_WORDS words
     LG_C_STAT = 200, LG_C_GATE = 210, LG_C_WORDS = 256     // + side: stat of the Lanczos max-step, gate of its certificate's fallback
 };
 struct LargeWs {
-    int rp = 0;                    // padded order (256 or 512)
+    int rp = 0;                    // padded order (256, 512, 1024 or 2048)
     int chunk = 64;                // columns of A per batched congruence
     double *base = nullptr;        // one allocation
     double *Kz, *Ks, *Tz, *Ts, *G, *M1, *M2, *M3;      // rp x rp
@@ -89,12 +92,10 @@ struct LargeWs {
     hipEvent_t efork = nullptr, ejoin = nullptr;
 };
 
-__device__ __forceinline__ int lg_vidx(int i, int j, int r) { return i * r - i * (i - 1) / 2 + (j - i); }   // i <= j
-__device__ __forceinline__ long lg_rowoff(int i, int r) { return (long)i * r - (long)i * (i - 1) / 2; }       // vecm offset of (i, i)
 __device__ __forceinline__ double lg_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lg_st(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// grid barrier for the few workgroups of a cooperative launch (all resident: <= 16 workgroups): monotonic counter,
+// grid barrier for the workgroups of a cooperative launch (all resident: at most 64 of them, order 1024 in slabs of 16): monotonic counter,
 // every thread drains its stores, one lane arrives and polls (`sc1` loads).  Bounded spin (cip_bounded_wait) -> *err.
 __device__ __forceinline__ void lg_grid_barrier(unsigned *ctr, unsigned nwg, unsigned &phase, int *err) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -107,15 +108,6 @@ __device__ __forceinline__ void lg_grid_barrier(unsigned *ctr, unsigned nwg, uns
     }
     __syncthreads();
 }
-__device__ __forceinline__ double lg_block_sum(double x, double *red) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double s = 0.0;
-    for (int q = 0; q < LG_T / 64; ++q) s += red[q];
-    return s;
-}
 
 // ------------------------------------------------------------------------------------------ element-wise pieces
 // X[b] (rp x rp) = mat(x_b) in the leading r x r block, pad: `padval` on the diagonal, 0 elsewhere.
@@ -127,8 +119,8 @@ __global__ __launch_bounds__(256) void k_lg_mat(const double *x, long xs, long x
     double v;
     if (i < r && j < r) {
         const int a = i < j ? i : j, b = i < j ? j : i;
-        v = x[(long)blockIdx.y * xb + (long)lg_vidx(a, b, r) * xs];
-        if (a != b) v *= LG_SQRT1_2;
+        v = x[(long)blockIdx.y * xb + (long)vidx(a, b, r) * xs];
+        if (a != b) v *= SQRT1_2;
     } else {
         v = (i == j) ? padval : 0.0;
     }
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(256) void k_lg_vecm(const double *Y, double *out, l
     const int i = (int)(e % r), j = (int)(e / r);
     if (i > j) return;
     const double y = Y[(size_t)blockIdx.y * rp * rp + i + (long)j * rp];
-    out[(long)blockIdx.y * ob + (long)lg_vidx(i, j, r) * os] = (i == j) ? y : y * LG_SQRT2;
+    out[(long)blockIdx.y * ob + (long)vidx(i, j, r) * os] = (i == j) ? y : y * SQRT2;
 }
 // The same for a batch of nb matrices whose vecm images are the COLUMNS i0.. of a matrix with leading dimension `os` (W' = A'F^-1:
 // element e of matrix i goes to out[i + e os]): 64 entries x 64 matrices per workgroup through LDS, so that both sides move whole
@@ -158,10 +150,10 @@ __global__ __launch_bounds__(256) void k_lg_vecm_cols(const double *Y, int nb, d
         const long e = e0 + el;
         if (e < dim) {
             int a = (int)(((double)(2 * r + 1) - sqrt((double)(2 * r + 1) * (2 * r + 1) - 8.0 * (double)e)) * 0.5);
-            while (a > 0 && lg_rowoff(a, r) > e) --a;
-            while (lg_rowoff(a + 1, r) <= e) ++a;
-            const int b = a + (int)(e - lg_rowoff(a, r));
-            const double sc = (a == b) ? 1.0 : LG_SQRT2;
+            while (a > 0 && vrowoff(a, r) > e) --a;
+            while (vrowoff(a + 1, r) <= e) ++a;
+            const int b = a + (int)(e - vrowoff(a, r));
+            const double sc = (a == b) ? 1.0 : SQRT2;
             for (int k = 0; k < 16; ++k) {
                 const int il = cq + 4 * k;
                 if (i0 + il < nb) tile[el][il] = Y[(size_t)(i0 + il) * rp * rp + b + (long)a * rp] * sc;
@@ -185,7 +177,7 @@ __global__ __launch_bounds__(256) void k_lg_vecm_sym(const double *Y, double *ou
     const int i = (int)(e % r), j = (int)(e / r);
     if (i > j) return;
     const double y = Y[i + (long)j * rp] + Y[j + (long)i * rp];
-    out[lg_vidx(i, j, r)] = (i == j) ? y : y * LG_SQRT2;
+    out[vidx(i, j, r)] = (i == j) ? y : y * SQRT2;
 }
 // T = (L D^1/2)' as a dense matrix, from the factored K (unit L strictly below the diagonal, d separately):
 //   T[i, k] = L[k, i] sqrt(d_i)  (k > i),  sqrt(d_i) on the diagonal, 0 below
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(256) void k_lg_store(const double *Rp, const double
 }
 __global__ __launch_bounds__(256) void k_lg_lambda_diag(const double *lam, double *lambda, int r) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < r) lambda[lg_vidx(i, i, r)] = lam[i];
+    if (i < r) lambda[vidx(i, i, r)] = lam[i];
 }
 // the four padded matrices from a packed scaling handed over by the host (cip_set_scaling_packed / identity)
 __global__ __launch_bounds__(256) void k_lg_pad(const double *R, const double *Ri, double *pad, int r, int rp) {
@@ -270,18 +262,6 @@ __device__ __forceinline__ double lg_sum_group(double x, int tpp) {
 }
 // ------------------------------------------------------------------------------------------ block one-sided Jacobi
 __host__ __device__ inline int lg_pitch(int rows) { return rows + ((4 - rows % 32) + 32) % 32; }   // == 4 (mod 32) doubles
-__device__ __forceinline__ double lg_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(r, fma(-d, r, 1.0), r);
-    r = fma(r, fma(-d, r, 1.0), r);
-    return r;
-}
-__device__ __forceinline__ double lg_rsqrt(double x) {
-    double r = __builtin_amdgcn_rsq(x);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    return r;
-}
 // nbk / 2 workgroups, every column pair rotated exactly once per sweep (cyclic Jacobi), ONE PHASE PER LAUNCH:
 //   step 0              workgroup k holds blocks 2k, 2k+1 in LDS: b - 1 rounds of the round-robin tournament inside
 //                       each block (b / 2 + b / 2 disjoint pairs per round)
@@ -321,10 +301,10 @@ __global__ __launch_bounds__(NT) void k_lg_jacobi(double *G, int rp, int bflags,
         for (int u = 0; u < EPL; ++u) { a += xv[u] * xv[u]; bb += yv[u] * yv[u]; c += xv[u] * yv[u]; }
         a = lg_sum_group(a, tpp); bb = lg_sum_group(bb, tpp); c = lg_sum_group(c, tpp);
         if (!(c * c > 1e-30 * (a * bb) && c != 0.0)) return 0;
-        const double zeta = (bb - a) * 0.5 * lg_rcp(c);
+        const double zeta = (bb - a) * 0.5 * sd_rcp(c);
         const double h2 = 1.0 + zeta * zeta;
-        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * lg_rcp(fabs(zeta) + h2 * lg_rsqrt(h2));
-        const double cs = lg_rsqrt(1.0 + tt * tt), sn = cs * tt;
+        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * sd_rcp(fabs(zeta) + h2 * sd_rsqrt(h2));
+        const double cs = sd_rsqrt(1.0 + tt * tt), sn = cs * tt;
 #pragma unroll
         for (int u = 0; u < EPL; ++u) {
             gp[part + u * tpp] = cs * xv[u] - sn * yv[u];
@@ -414,10 +394,10 @@ __global__ __launch_bounds__(NT) void k_lg_jacobi(double *G, int rp, int bflags,
                 c = lg_sum_group(c, tpp);
                 const double bb = s_nrm[qi];
                 if (c * c > 1e-30 * (a * bb) && c != 0.0) {
-                    const double zeta = (bb - a) * 0.5 * lg_rcp(c);
+                    const double zeta = (bb - a) * 0.5 * sd_rcp(c);
                     const double h2 = 1.0 + zeta * zeta;
-                    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * lg_rcp(fabs(zeta) + h2 * lg_rsqrt(h2));
-                    const double cs = lg_rsqrt(1.0 + tt * tt), sn = cs * tt;
+                    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * sd_rcp(fabs(zeta) + h2 * sd_rsqrt(h2));
+                    const double cs = sd_rsqrt(1.0 + tt * tt), sn = cs * tt;
 #pragma unroll
                     for (int u = 0; u < EPL; ++u) {
                         const double x = xv[u];
@@ -459,9 +439,7 @@ __global__ __launch_bounds__(LG_T) void k_lg_tridiag(const double *M, int ldm, c
     unsigned phase = 0;
     for (int e = tid; e < ncol * r; e += LG_T) {
         const int i = e % r, c = e / r, j = c0 + c;
-        double x = 0.5 * (M[i + (long)j * ldm] + M[j + (long)i * ldm]);
-        if (dscale) x *= rsqrt(dscale[i]) * rsqrt(dscale[j]);
-        a[i + c * ld] = x;
+        a[i + c * ld] = sd_scaled_sym_entry(M, ldm, dscale, i, j);
     }
     __syncthreads();
     // column `col` below its diagonal, as it stands in the owner's slab -> xb
@@ -482,15 +460,12 @@ __global__ __launch_bounds__(LG_T) void k_lg_tridiag(const double *M, int ldm, c
         if (w == owner && tid == 0) dg[k] = a[k + kc * ld];
         double part = 0.0;
         for (int i = tid; i < m; i += LG_T) part += v[i] * v[i];
-        const double sigma = lg_block_sum(part, red);
+        const double sigma = sd_block_sum(part, red, LG_T / 64, SdSyncAll());
         const double x0 = v[0];
         if (m == 1) { if (w == owner && tid == 0) of[k] = x0; break; }
-        const bool flat = !(sigma - x0 * x0 > 0.0);          // already tridiagonal in this column (uniform over the grid)
-        double alpha = x0, beta = 0.0;
-        if (!flat) {
-            alpha = -copysign(sqrt(sigma), x0);
-            beta = 1.0 / (sigma - x0 * alpha);               // 2 / ||v||^2 with v = x - alpha e1
-        }
+        const SdReflector h = sd_reflector(sigma, x0);       // flat: already tridiagonal in this column (uniform over the grid)
+        const bool flat = h.flat;
+        const double alpha = h.alpha, beta = h.beta;
         __syncthreads();
         if (tid == 0) { if (!flat) v[0] = x0 - alpha; if (w == owner) of[k] = alpha; }
         __syncthreads();
@@ -514,7 +489,7 @@ __global__ __launch_bounds__(LG_T) void k_lg_tridiag(const double *M, int ldm, c
         }
         part = 0.0;
         for (int i = tid; i < m; i += LG_T) { const double p = lg_ld(pb + i); wv[i] = p; part += p * v[i]; }
-        const double kk = 0.5 * beta * lg_block_sum(part, red);
+        const double kk = 0.5 * beta * sd_block_sum(part, red, LG_T / 64, SdSyncAll());
         for (int i = tid; i < m; i += LG_T) wv[i] -= kk * v[i];
         __syncthreads();
         // A22 -= v w' + w v' on the slab's columns j > k
@@ -537,56 +512,15 @@ __global__ __launch_bounds__(LG_T) void k_lg_sturm(const double *dgg, const doub
     if (gate && !gate[0]) return;
     __shared__ double dg[2048], of[2048], red[64];
     __shared__ int first;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double INF = __builtin_inf();
+    const int tid = threadIdx.x;
     if (info && info[0]) {                                   // X not positive definite -> Inf (:277-280)
-        if (tid == 0) partial[item] = INF;
+        if (tid == 0) partial[item] = __builtin_inf();
         return;
     }
     for (int i = tid; i < r; i += LG_T) { dg[i] = dgg[i]; of[i] = ofg[i]; }
     __syncthreads();
-    double lo = INF, hi = -INF;
-    for (int i = tid; i < r; i += LG_T) {
-        const double rad = (i > 0 ? fabs(of[i - 1]) : 0.0) + (i + 1 < r ? fabs(of[i]) : 0.0);
-        lo = fmin(lo, dg[i] - rad);
-        hi = fmax(hi, dg[i] + rad);
-    }
-    for (int o = 32; o > 0; o >>= 1) { lo = fmin(lo, __shfl_xor(lo, o)); hi = fmax(hi, __shfl_xor(hi, o)); }
-    if (lane == 0) { red[wave] = lo; red[16 + wave] = hi; }
-    __syncthreads();
-    lo = red[0]; hi = red[16];
-    for (int q = 1; q < LG_T / 64; ++q) { lo = fmin(lo, red[q]); hi = fmax(hi, red[16 + q]); }
-    const double span = fmax(fabs(lo), fabs(hi));
-    hi += 1e-15 * span + 1e-300;
-    lo -= 1e-15 * span + 1e-300;
-    for (int round = 0; round < 12; ++round) {
-        if (!(hi - lo > 4.4e-16 * fmax(fabs(lo), fabs(hi)))) break;
-        const double step = (hi - lo) / (LG_T + 1);
-        const double xs = lo + step * (tid + 1);
-        int cnt = 0;
-        double q = dg[0] - xs;
-        if (q < 0.0) ++cnt;
-        for (int i = 1; i < r; ++i) {
-            if (q == 0.0) q = 1e-300;
-            q = (dg[i] - xs) - of[i - 1] * of[i - 1] / q;
-            if (q < 0.0) ++cnt;
-        }
-        const bool hit = want_max ? (cnt >= r) : (cnt >= 1);
-        if (tid == 0) first = LG_T;
-        __syncthreads();
-        if (hit) atomicMin(&first, tid);
-        __syncthreads();
-        const int f = first;
-        __syncthreads();
-        const double nlo = (f == 0) ? lo : lo + step * f;
-        const double nhi = (f == LG_T) ? hi : lo + step * (f + 1);
-        lo = nlo; hi = nhi;
-    }
-    const double ev = 0.5 * (lo + hi);
-    if (tid == 0) {
-        if (want_max) { const double mx = ev * scale; partial[item] = (mx < 0.0) ? INF : 1.0 / mx; }
-        else partial[item] = (ev > 0.0) ? 0.0 : -1.0 + ev;
-    }
+    const double ev = sd_tridiag_extreme(dg, of, r, want_max != 0, LG_T, red, &first, SdSyncAll());
+    if (tid == 0) partial[item] = sd_maxstep_verdict(want_max != 0, ev, scale);
 }
 
 // ------------------------------------------------------------------------------------------ host side
@@ -692,14 +626,14 @@ __global__ __launch_bounds__(256) void k_gemm_nt_small(const double *A, long lda
             double v = 0.0;
             if (jb < r && kk < r) {
                 const int lo = jb < kk ? jb : kk, hi = jb < kk ? kk : jb;
-                v = B[lg_vidx(lo, hi, r)];
-                if (lo != hi) v *= LG_SQRT1_2;
+                v = B[vidx(lo, hi, r)];
+                if (lo != hi) v *= SQRT1_2;
             }
             return v;
         },
         [&](int q, double c) {
             const int i = blockIdx.x * 16 + l15, j = blockIdx.y * 16 + l4 + 4 * q;
-            if (CVEC) { if (i <= j && j < r) C[lg_vidx(i, j, r)] = (i == j) ? c : c * LG_SQRT2; }
+            if (CVEC) { if (i <= j && j < r) C[vidx(i, j, r)] = (i == j) ? c : c * SQRT2; }
             else C[i + (long)j * ldc] = c;
         });
 }
@@ -752,11 +686,7 @@ __global__ __launch_bounds__(512) void k_lg_tridiag1(const double *M, int ldm, c
             if (bj <= 2 * ai + 1) {
                 a[ai][bj] = 0.0;
                 const int i = 32 * ai + tr, j = 16 * bj + tc;
-                if (i < r && j < r) {
-                    double x = 0.5 * (M[i + (long)j * ldm] + M[j + (long)i * ldm]);
-                    if (dscale) x *= rsqrt(dscale[i]) * rsqrt(dscale[j]);
-                    a[ai][bj] = x;
-                }
+                if (i < r && j < r) a[ai][bj] = sd_scaled_sym_entry(M, ldm, dscale, j, i);       // (tc runs along j: the coalesced load of the pair)
             }
         }
     double *ps = vs + 256;                                     // p, read back by everybody
@@ -799,9 +729,9 @@ __global__ __launch_bounds__(512) void k_lg_tridiag1(const double *M, int ldm, c
         const double x0 = xs[k + 1];
         // flat: already tridiagonal in this column (always so for the last one); the reflector is then the identity:
         // beta = 0 makes p, w and the update vanish -- one code path, no divergent loop exits around the register matrix
-        const bool flat = !(sigma - x0 * x0 > 0.0);
-        const double alpha = flat ? x0 : -copysign(sqrt(sigma), x0);
-        const double beta = flat ? 0.0 : 1.0 / (sigma - x0 * alpha);        // 2 / |v|^2 with v = x - alpha e1
+        const SdReflector h = sd_reflector(sigma, x0);
+        const bool flat = h.flat;
+        const double alpha = h.alpha, beta = h.beta;
         if (tid == 0) of[k] = alpha;
         if (tid < 256) vs[tid] = (tid > k && tid < r && !flat) ? (tid == k + 1 ? x0 - alpha : xs[tid]) : 0.0;
         __syncthreads();                                                                        // (3)
@@ -939,12 +869,7 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
             if (bj <= 2 * ai + 1) {
                 a[ai][bj] = 0.0;
                 const int i = 32 * ai + tr, j = 16 * bj + tc;
-                if (i < r && j < r) {
-                    // M[j + i ldm] is the coalesced one of the pair (tc runs along a column); an unscaled M is mat(x): symmetric
-                    double x = M[j + (long)i * ldm];
-                    if (dscale) x = 0.5 * (M[i + (long)j * ldm] + x) * (rsqrt(dscale[i]) * rsqrt(dscale[j]));
-                    a[ai][bj] = x;
-                }
+                if (i < r && j < r) a[ai][bj] = sd_scaled_sym_entry(M, ldm, dscale, j, i);       // (tc runs along j: the coalesced load of the pair)
             }
         }
     // LDS copy of v_k: element i at k 256 + (i ^ 8 (k & 7)) -- the eight vectors a wave reads together in the dot products
@@ -1193,8 +1118,7 @@ __global__ __launch_bounds__(512) void k_lg_lanczos1(const double *M, int ldm, c
     }
     if (tid == 0) {
         const double ev = 0.5 * (th_lo + th_hi);
-        if (want_max) { const double mx = ev * scale; partial[item] = (mx < 0.0) ? INF : 1.0 / mx; }
-        else partial[item] = (ev > 0.0) ? 0.0 : -1.0 + ev;
+        partial[item] = sd_maxstep_verdict(want_max != 0, ev, scale);
         if (stat) stat[0] = m;
         // the bound the inertia certificate checks: no eigenvalue beyond theta by more than 1e-9 |T| (the stop was at 1e-11 |T|)
         if (cert) { const double tol = cert_tol * s_res[1] + 1e-300; cert[0] = want_max ? ev + tol : ev - tol; cert[1] = 0.0; }
@@ -1213,9 +1137,7 @@ __global__ __launch_bounds__(256) void k_tg_init(const double *M, int ldm, const
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long)r * r) return;
     const int i = (int)(e % r), j = (int)(e / r);
-    double x = 0.5 * (M[i + (long)j * ldm] + M[j + (long)i * ldm]);
-    if (dscale) x *= rsqrt(dscale[i]) * rsqrt(dscale[j]);
-    A[i + (long)j * lda] = x;
+    A[i + (long)j * lda] = sd_scaled_sym_entry(M, ldm, dscale, i, j);
 }
 __device__ __forceinline__ double tg_block_sum(double x, double *red) {          // 256 threads; every thread gets the sum
     x = cip_wave_sum(x);
@@ -1234,9 +1156,9 @@ __global__ __launch_bounds__(256) void k_tg_symv(const double *A, int lda, int r
     for (int i = tid; i < m; i += 256) { const double xi = x[i]; vs[i] = xi; part += xi * xi; }
     const double sigma = tg_block_sum(part, red);
     const double x0 = vs[0];
-    const bool flat = (m == 1) || !(sigma - x0 * x0 > 0.0);
-    double alpha = x0, beta = 0.0;
-    if (!flat) { alpha = -copysign(sqrt(sigma), x0); beta = 1.0 / (sigma - x0 * alpha); }
+    const SdReflector h = sd_reflector(sigma, x0, m == 1);
+    const bool flat = h.flat;
+    const double alpha = h.alpha, beta = h.beta;
     if (blockIdx.x == 0 && tid == 0) {
         dg[k] = A[k + (long)k * lda];
         of[k] = alpha;
@@ -1533,7 +1455,6 @@ static int lz_reorth(void) {
 // 2 (default; CIP_LG_LANCZOS changes it): the max-step's extreme eigenvalue by k_lg_lanczos1 at orders <= 256 + the inertia certificate
 // (lg_certify); 1: Lanczos alone; 3: certificate self-test; 0: full
 // tridiagonalisation + Sturm multisection at every order (A/B runs, tests).  on < 0 only reads; returns the previous setting
-#include <atomic>
 int cip_sdp_large_lanczos(int on) {
     static std::atomic<int> mode{[] { const int v = cip_env_int("CIP_LG_LANCZOS", 2); return (v >= 0 && v <= 3) ? v : 2; }()};
     const int prev = mode.load();
@@ -1562,7 +1483,6 @@ int cip_sdp_large_join(hipStream_t s, LargeWs *w) {
     CIP_HIP_CHECK(hipStreamWaitEvent(s, w->ejoin, 0));
     return 0;
 }
-// maxstep_sdc for one large cone: partial[cd.item]
 // ---- inertia certificate of the Lanczos max-step (mode 2; ADVICE r3: a Ritz value can settle on an interior eigenvalue when the
 // fixed start vector has no component along the extreme eigenvector).  With theta' = theta +- 1e-9 |T| from the kernel:
 //   B = theta' I - A (largest eigenvalue wanted)  or  A - theta' I (smallest)  must be positive definite
@@ -1577,8 +1497,7 @@ __global__ __launch_bounds__(256) void k_lg_cert_build(const double *M, int ldm,
     const int i = (int)(e % rp), j = (int)(e / rp);
     double a = 0.0, b = (i == j) ? 1.0 : 0.0;
     if (i < r && j < r) {
-        a = M[j + (long)i * ldm];
-        if (dscale) a = 0.5 * (M[i + (long)j * ldm] + a) * (rsqrt(dscale[i]) * rsqrt(dscale[j]));
+        a = sd_scaled_sym_entry(M, ldm, dscale, j, i);
         if (cert[1] == 0.0) {
             const double th = (i == j) ? cert[0] : 0.0;
             b = want_max ? th - a : a - th;
@@ -1622,6 +1541,7 @@ int cip_sdp_large_cert_stats(hipStream_t s, LargeWs *w, int *out2) {
     return 0;
 }
 
+// maxstep_sdc for one large cone: partial[cd.item]
 int cip_sdp_large_maxstep(hipStream_t s, LargeWs *w, const ConeDesc &cd, const double *x, const double *d, double scale,
                           double *partial, int side) {
     const int r = cd.r, rp = w->rp;
@@ -1742,7 +1662,7 @@ int cip_sdp_large_apply(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, i
 // quotient when it has none; the general kernel (sdp.hip: k_sdp_div) runs behind them and returns at once unless the flag is up.
 __global__ __launch_bounds__(256) void k_lg_div_check(const double *y, int r, int *flag) {
     const int i = blockIdx.x;
-    const double *row = y + lg_rowoff(i, r);
+    const double *row = y + vrowoff(i, r);
     int bad = 0;
     for (int j = 1 + threadIdx.x; j < r - i; j += 256) bad |= (row[j] != 0.0);
     if (threadIdx.x == 0 && !(row[0] == row[0])) bad = 1;                  // NaN on the diagonal: let the general path propagate it
@@ -1751,9 +1671,9 @@ __global__ __launch_bounds__(256) void k_lg_div_check(const double *y, int r, in
 __global__ __launch_bounds__(256) void k_lg_div_diag(const double *x, const double *y, double *out, int r, const int *flag) {
     if (*flag) return;
     const int i = blockIdx.x;
-    const long o = lg_rowoff(i, r);
+    const long o = vrowoff(i, r);
     const double yi = y[o];
-    for (int j = threadIdx.x; j < r - i; j += 256) out[o + j] = x[o + j] / (yi + y[lg_rowoff(i + j, r)]);
+    for (int j = threadIdx.x; j < r - i; j += 256) out[o + j] = x[o + j] / (yi + y[vrowoff(i + j, r)]);
 }
 // returns with flag[0] = 1 when the general path must run for this cone (the caller launches it; it resets the flag)
 int cip_sdp_large_div(hipStream_t s, LargeWs *w, const ConeDesc &cd, const double *x, const double *y, double *out, int *flag) {

@@ -481,3 +481,51 @@ def test_s_cone_ops_at_the_edges(r):
         torch.cuda.synchronize()
     finally:
         ks.close()
+
+
+# ------------------------------------------------------------------------------------------ a small S cone beside a large one
+def _small_cone_beside(r, r_large):
+    """every output of the order-r cone's block from a handle [S(r)] or [S(r), S(r_large)]; the large cone sits at the
+    identity and takes no part in either max-step (zero direction; the identity is inside the cone)"""
+    from cipkkt import OP_F, OP_FINV, OP_FINVT, OP_FT
+    k = r * (r + 1) // 2
+    orders = [r] + ([r_large] if r_large else [])
+    cone_dims = [("S", q * (q + 1) // 2) for q in orders]
+    rest = [CR.vecm(np.eye(q)) for q in orders[1:]]
+    zero = [np.zeros(kk) for _, kk in cone_dims[1:]]
+    rng = np.random.default_rng(132)
+    v, s = CR.s_point(r, 1e4, rng), CR.s_point(r, 1e4, rng)
+    x, d = rng.standard_normal(k), _sym_dir(r, rng)
+    xo = v - (np.linalg.eigvalsh(CR.mat(v)).min() + 0.3) * CR.vecm(np.eye(r))          # lambda_min about -0.3
+    ks = _system(cone_dims, 6)
+    try:
+        m = ks.m
+        lam_d = _dev(np.zeros(m))
+        ks.set_scaling_from_iterate(_dev(np.concatenate([v] + rest)), _dev(np.concatenate([s] + rest)), lam_d)
+        got = {"packed": ks.get_scaling_packed()[:2 * r * r], "lambda": lam_d.cpu().numpy()[:k]}
+        out = _dev(np.zeros(m))
+        for mode in (OP_F, OP_FT, OP_FINV, OP_FINVT):
+            ks.apply_F(mode, _dev(np.concatenate([x] + zero)), out)
+            got["apply %d" % mode] = out.cpu().numpy()[:k]
+        dv = _dev(np.concatenate([v] + rest))
+        for scale in (1.0, 1.0 / 0.99):
+            got["maxstep(v, d) scale %r" % scale] = ks.maxstep(dv, _dev(np.concatenate([d] + zero)), scale)
+        got["maxstep(x, nothing)"] = ks.maxstep(_dev(np.concatenate([xo] + rest)), None)
+    finally:
+        ks.close()
+    assert 0 < got["maxstep(v, d) scale 1.0"] < np.inf and -1.5 < got["maxstep(x, nothing)"] < -1.1, got
+    return got
+
+
+@gpu
+def test_small_s_cone_gives_the_same_bits_beside_a_large_one():
+    """The workgroup-per-cone kernels of sdp.hip keep the one live matrix of a small cone in LDS.  An LDS budget sized
+    from the handle's largest S cone would push the max-step of an order-132 cone out of LDS beside a cone of order
+    >= 432 (r (r + 1) > 19280 - 4 rmax) and not beside one of order 431: its block of the packed scaling, its lambda,
+    apply_F and both forms of maxstep must come out bit for bit as from a handle that holds the small cone alone."""
+    alone = _small_cone_beside(132, 0)
+    for r_large in (431, 432):
+        beside = _small_cone_beside(132, r_large)
+        assert list(beside) == list(alone)
+        for key in alone:
+            assert _bits_equal(beside[key], alone[key]), (r_large, key)
