@@ -175,7 +175,14 @@ int cip_solve2x2_many(cip_handle *h, int nrhs, const double *Y, const double *W,
 int cip_solve2x2_many_dev(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW);  /* device */
 
 /* ---- the 4x4 -> 3x3 reduction of solve4x4 (src/ConicIP.jl:684-692), device pointers.
- * r and dz are 4-block vectors (y[n], w[p], v[m], s[m]) stored contiguously. */
+ * r and dz are 4-block vectors (y[n], w[p], v[m], s[m]) stored contiguously.
+ * Aliasing: dz may be r itself (an in-place call), and dz may start inside or behind the s block of r (dz >= r + n + p + m):
+ * every block of dz is then written after the blocks of r it covers have been read.  Such a call gives the bits of a call with
+ * separate buffers; it always takes the element-wise path (with R cones only, separate buffers take two fused kernels that
+ * gather r across threads while dz is written -- the same bits, fewer launches).  This holds with R and Q cones and with S cones
+ * below order 133 (their kernels stage a cone before they write it), with and without regularisation; it is not promised for
+ * larger S cones.  Any other overlap of dz and r is not checked and is undefined: blocks of r would be overwritten before they
+ * are read.  lambda must not overlap dz. */
 int cip_solve4x4_dev(cip_handle *h, const double *lambda, const double *r, double *dz);
 
 /* ---- block operator / cone algebra on the device (device pointers, length m) */

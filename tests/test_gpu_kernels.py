@@ -635,6 +635,40 @@ def test_solve4x4_fused_r_path_bitwise(sparse, n, m, p):
     assert np.linalg.norm(outs[1] - ref) / np.linalg.norm(ref) < 1e-9
 
 
+@pytest.mark.parametrize("name", ["allR_330_dense", "allR_330_csr", "allR_150_dense", "allR_150_csr"])
+def test_solve4x4_fused_r_path_bitwise_on_hard_iterates(name):
+    """The same identity at the late-iteration all-R iterates of tests/_newton_ref.py (F over ten decades, mu down to 1e-10;
+    m above and below Npad, dense and CSR A, sections off the 64-lane boundaries), on a random and on a graded right-hand
+    side.  (What the step is worth there is judged stage by stage in tests/test_gpu_newton.py.)"""
+    import os
+    import cipkkt
+    import _newton_ref as NR
+    Pb = NR.make_problem(name)
+    rhs = [NR.rhs4(Pb, kind, np.random.default_rng(17)) for kind in ("normal", "graded")]
+    outs = []
+    for fused in ("0", "1"):
+        os.environ["CIP_S4_FUSED"] = fused
+        try:
+            ks = cipkkt.KKTSystem(Pb.Q, Pb.A, Pb.G, Pb.cone_dims)
+            lam = torch.zeros(Pb.m, dtype=torch.float64, device="cuda")
+            ks.set_scaling_from_iterate(dev(Pb.v), dev(Pb.s), lam)
+            ks.factor(check=True)
+            got = []
+            for r in rhs:
+                dz = torch.full((Pb.n + Pb.p + 2 * Pb.m,), float("nan"), dtype=torch.float64, device="cuda")
+                ks.solve4x4_dev(lam, dev(r), dz)
+                torch.cuda.synchronize()
+                got.append(dz.cpu().numpy())
+            assert ks.health()["n_regularized"] == 0
+            outs.append(got)
+            ks.close()
+        finally:
+            os.environ.pop("CIP_S4_FUSED")
+    for a, b in zip(*outs):
+        assert np.isfinite(a).all()
+        np.testing.assert_array_equal(a.view(np.int64), b.view(np.int64))
+
+
 @pytest.mark.parametrize("n", [1024, 2048, 4096])
 def test_lazy_copy_of_Q_gives_the_same_factor_and_step(n):
     """Box-QP family (A = I as CSR, R cones, p = 0, n a multiple of 128): cip_factor copies only the first outer block's columns
