@@ -104,6 +104,7 @@ SIGNATURES = {
     "cip_release_cached_memory": (C.c_int, []),
     "cip_lockstep_stats": (C.c_int, [c_int_p]),
     "cip_set_lockstep_regularize": (C.c_int, [C.c_int]),
+    "cip_set_lockstep_ragged": (C.c_int, [C.c_int]),
     "cip_lockstep_regularized": (C.c_int, [c_int_p]),
     "cip_conicip_many": (C.c_int, [C.POINTER(C.c_void_p), C.c_int] + [C.POINTER(C.c_void_p)] * 3 +
                          [C.POINTER(CipOptions)] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(CipResult), C.c_int]),

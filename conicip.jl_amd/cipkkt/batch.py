@@ -99,7 +99,15 @@ def lockstep_regularize(on=None):
     return int(L.load().cip_set_lockstep_regularize(-1 if on is None else int(bool(on))))
 
 
-def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, keep_regularized=False):
+def lockstep_ragged(on=None):
+    """The process-wide switch `cip_set_lockstep_ragged`: True / 1 -- problems of one shape whose CSR A or CSR Q differ in their
+    numbers of non-zeros (or whose CSR Q take different mat-vec forms) share a lock-step group; False / 0 (the default) -- the nnz
+    is part of the shape.  None only queries.  Returns the previous value (0 or 1)."""
+    from . import _lib as L
+    return int(L.load().cip_set_lockstep_ragged(-1 if on is None else int(bool(on))))
+
+
+def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, keep_regularized=False, ragged=False):
     """All problems of this rank through the library's batch entry points.
     mode "lockstep": `cip_conicip_lockstep` (csrc/lockstep.hip) -- problems of identical shape advance through the loop
     together, every step one launch with the problem index in the grid; "threads": `cip_conicip_problems`
@@ -107,7 +115,8 @@ def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, 
     with the next problem of the queue; "auto": `cip_conicip_mixed` -- every group of problems that share a shape (and
     hold no chip-wide S cone) in lock-step, the others through the threads.  CIP_BATCH=threads|lockstep overrides "auto".
     sparse_q (or a problem's own "sparse_q" key): Q goes over in CSR (cipkkt.kkt.make_problem); the form is part of the shape.
-    keep_regularized: `lockstep_regularize(True)` around the native call, the previous setting restored behind it."""
+    keep_regularized: `lockstep_regularize(True)` around the native call, the previous setting restored behind it.
+    ragged: `lockstep_ragged(True)` around the native call in the same way."""
     import ctypes as C
     from . import _lib as L
     from .driver import solution_from_result
@@ -149,6 +158,7 @@ def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, 
         if mode == "auto":
             mode = os.environ.get("CIP_BATCH", "auto")
         prev = lockstep_regularize(True) if keep_regularized else None
+        prev_ragged = lockstep_ragged(True) if ragged else None
         try:
             if mode == "lockstep":
                 L.check(lib.cip_conicip_lockstep(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs), res))
@@ -159,13 +169,15 @@ def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, 
                 L.check(lib.cip_conicip_mixed(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs),
                                               res, int(in_flight)))
         finally:
+            if prev_ragged is not None:
+                lockstep_ragged(prev_ragged)
             if prev is not None:
                 lockstep_regularize(prev)
     return [solution_from_result(res[i], ys[i][:dims[i][0]], ws[i][:dims[i][2]], vs[i][:dims[i][1]]) for i in range(k)]
 
 
 def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None, concurrency=1, native=False,
-                reduce_device=None, sparse_q=False, keep_regularized=False):
+                reduce_device=None, sparse_q=False, keep_regularized=False, ragged=False):
     """problems: list of dicts(Q, c, A, b, cone_dims, G, d, kwargs).  Each rank solves its
     shard with `solve_fn` (default: the HIP-backed cipkkt.conicIP) and the statistics are
     reduced over ranks:  SUM(iters, n_factor, n_solve, n_optimal, n_problems), MAX(wall).
@@ -177,7 +189,8 @@ def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None
     thread: what a C caller uses); `native="handles"` builds all handles first and calls `cip_conicip_many`
     (605-683 KKT solves/s on the same batch: the setup is not overlapped).  `sparse_q=True` (native paths; or a "sparse_q"
     key of a problem dict) hands Q over in CSR.  `keep_regularized=True` (native batch entry points): problems that need the
-    regularised factorisation stay in their lock-step group (`lockstep_regularize`).
+    regularised factorisation stay in their lock-step group (`lockstep_regularize`).  `ragged=True` (the same entry points): CSR
+    matrices of differing numbers of non-zeros share a lock-step group (`lockstep_ragged`).
     Returns (local_solutions, stats_dict)."""
     default_solver = solve_fn is None
     if solve_fn is None:
@@ -193,7 +206,7 @@ def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None
             out = _solve_many_native(shard, dev, max(1, concurrency), sparse_q=sparse_q)
         else:
             out = _solve_problems_native(shard, dev, max(1, concurrency), native if native in ("lockstep", "threads") else "auto",
-                                         sparse_q=sparse_q, keep_regularized=keep_regularized)
+                                         sparse_q=sparse_q, keep_regularized=keep_regularized, ragged=ragged)
         for i, sol in zip(mine, out):
             sols[i] = sol
     elif default_solver and concurrency > 1 and len(mine) > 1:

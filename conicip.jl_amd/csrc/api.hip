@@ -256,6 +256,13 @@ static int q_wave_form(int maxrow) {
 // may go through the symmetric mat-vec (the refinement's residual never did: it keeps its bits)
 int cip_mul_Q(cip_handle *h, double alpha, const double *x, double beta, double *y, bool symv) {
     hipStream_t s = h->stream;
+    if (h->Q_sparse && cip_in_batch()) {
+        // a lock-step group: h is problem 0's handle, the form is each live problem's own (a ragged group may hold both)
+        const unsigned long long live = cip_tl_bz.mask, wave = cip_tl_bz.q_wave & live;
+        if (wave == 0) return cip_spmv_csr(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y);
+        if (wave == live) return cip_spmv_csr_wave(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y);
+        return cip_spmv_csr_forms(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y, wave);
+    }
     if (h->Q_sparse)
         return h->Q_wave ? cip_spmv_csr_wave(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y)
                          : cip_spmv_csr(s, h->n, h->Q_rp, h->Q_ci, h->Q_v, alpha, x, beta, y);
@@ -491,9 +498,12 @@ static size_t sdp_flag_words(const ConeSet &cs) { return (size_t)rup(4 + (cs.nla
 // at problem 0's addresses + z * stride.  `extras`: what an ordinary handle allocates on first use and a lock-step handle must hold
 // at a fixed offset.  The workspace of chip-wide S cones is not part of it (cip_sdp_large_create: an allocation of its own).
 template <typename T> static void take(CipLayout &L, T *&ptr, size_t count) { ptr = L.take<T>(count ? count : 1); }
-size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras) {
+size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras, const CipCsrCap *cap) {
     ConeSet &cs = h->cs;
-    const size_t n = h->n, m = h->m, p = h->p, npad = h->npad, nnz = h->A_nnz;
+    const size_t n = h->n, m = h->m, p = h->p, npad = h->npad;
+    // (a capacity never below the handle's own count: the uploads fit whatever the caller passed)
+    const size_t nnz = cap && cap->A_nnz > (size_t)h->A_nnz ? cap->A_nnz : (size_t)h->A_nnz;
+    const size_t qnnz = cap && cap->Q_nnz > (size_t)h->Q_nnz ? cap->Q_nnz : (size_t)h->Q_nnz;
     if (cs.npackq > 0) take(L, cs.d_packq, cs.npackq);
     if (cs.nritems > 0) take(L, cs.d_ritems, cs.nritems);
     if (cs.nbigq > 0) take(L, cs.d_bigq, cs.nbigq);
@@ -507,7 +517,7 @@ size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras) {
     }
     // Q, G, A: contents by upload_problem (also used by cip_update_problem)
     if (h->Q_sparse) {                                    // O(nnz): neither the dense image nor the symv tables
-        take(L, h->Q_rp, n + 1); take(L, h->Q_ci, h->Q_nnz); take(L, h->Q_v, h->Q_nnz);
+        take(L, h->Q_rp, n + 1); take(L, h->Q_ci, qnnz); take(L, h->Q_v, qnnz);
     } else {
         take(L, h->Q, n * n);
         if (n >= 2048 && n % 128 == 0) take(L, h->symv_ws, 2 * (n / 128) * n);
@@ -621,11 +631,11 @@ int cip_plan(const cip_problem *pr, hipStream_t stream, cip_handle **out) {
 
 // The device half for a handle of a lock-step group: carved out of `slab` (cap bytes; it belongs to the caller and outlives the
 // handle) and filled without a host wait.
-int cip_create_in_slab(cip_handle *h, const cip_problem *pr, char *slab, size_t cap, unsigned extras) {
-    const size_t bytes = cip_handle_layout(nullptr, h, extras);
+int cip_create_in_slab(cip_handle *h, const cip_problem *pr, char *slab, size_t cap, unsigned extras, const CipCsrCap *csr_cap) {
+    const size_t bytes = cip_handle_layout(nullptr, h, extras, csr_cap);
     if (bytes > cap) { cip_set_error("lock-step batch: a handle of %zu bytes in a slab of %zu", bytes, cap); return CIP_E_UNSUPPORTED; }
     h->in_slab = true;
-    cip_handle_layout(slab, h, extras);
+    cip_handle_layout(slab, h, extras, csr_cap);
     const int rc = debug_poison(slab, bytes);
     return rc ? rc : handle_fill(pr, h, false);
 }

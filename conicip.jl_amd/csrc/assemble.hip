@@ -361,14 +361,14 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
         // (CSR Q: the Schur formation stores W W' alone -- h->Q is NULL -- and the stored entries of Q are added, each touched once)
         if ((rc = cip_syrk_schur(s, h->npad, h->mpad, n, 1.0, h->Wt, h->npad, h->Q, n, h->K, h->ldk, h->syrk_ws, h->syrk_n, h->syrk_len))) return rc;
         if ((rc = cip_prof_slot_end(CIP_PROF_SYRK, s))) return rc;
-        if (h->Q_sparse && h->Q_nnz > 0)
+        if (h->Q_sparse && cip_grp_Q_nonempty(h))
             cip_launch_b(k_qcsr_scatter<true>, dim3((n + 3) / 4), dim3(256), 0, s, h->K, h->ldk, 0, n, h->Q_rp, h->Q_ci, h->Q_v, 6);
     } else {
         const int lazy_now = g_lazy_copy.load(std::memory_order_relaxed);
         const int lazy_on = lazy_now < 0 ? cip_lazy_copy_set(-1) : lazy_now;
         bool all_r = h->m > 0 && h->nq == 0 && !h->cs.has_S;
         const int nb0 = cip_ldlt_outer_block_for(h->Npad);
-        if (!h->Q_sparse && lazy_on && lazy_ok && all_r && h->A_one_per_row && p == 0 && h->Npad == n && n > nb0 && h->reg_rel <= 0.0 && h->kdiag &&
+        if (!h->Q_sparse && lazy_on && lazy_ok && all_r && cip_grp_A_one_per_row(h) && p == 0 && h->Npad == n && n > nb0 && h->reg_rel <= 0.0 && h->kdiag &&
             copy_lower_vectorisable(h->K, h->ldk, 0, h->Q, (long)n, n)) {
             launch_copy_block_lower(s, h->K, h->ldk, 0, h->Q, (long)n, n, 1.0, nb0);
             cip_launch_b(k_schur_diag_lazy, dim3((n + 255) / 256), dim3(256), 0, s, n, nb0, h->T_rp, h->T_ci, h->T_v, h->A_rp, h->A_ci, h->A_v,
@@ -431,7 +431,7 @@ static int assemble_full(cip_handle *h) {
                                h->K, h->ldk, m);
     }
     if (h->Q_sparse) {
-        if (h->Q_nnz > 0)
+        if (cip_grp_Q_nonempty(h))
             cip_launch_b(k_qcsr_scatter<false>, dim3((n + 3) / 4), dim3(256), 0, s, h->K, h->ldk, m, n, h->Q_rp, h->Q_ci, h->Q_v, 7);
     } else if (n > 0)
         launch_copy_block_lower(s, h->K, h->ldk, m, h->Q, (long)n, n, 1.0);

@@ -130,8 +130,21 @@ int cip_handle_alloc(cip_handle *h, void **out, size_t bytes);      // api.hip: 
 #define CIP_EXTRA_DRIVER 1u         // h->drv: the vectors of the interior-point loop (cip_driver_bytes)
 #define CIP_EXTRA_REFINE 2u         // h->ref, h->c2x2: the refined solves of a regularised factor
 int cip_plan(const struct cip_problem *pr, hipStream_t stream, cip_handle **out);
-size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras);
-int cip_create_in_slab(cip_handle *h, const struct cip_problem *pr, char *slab, size_t cap, unsigned extras);
+// Entries the layout reserves for the index / value arrays of a CSR A (and of its transpose) and of a CSR Q.  NULL: the handle's own
+// numbers of non-zeros -- every ordinary handle, whose layout keeps its bytes.  A ragged lock-step group passes its largest ones, so that
+// every problem's arrays sit at problem 0's offsets; a handle uploads and checks (cip_update_problem) its own nnz, and the tail above
+// it is never read: every kernel walks the row pointers.
+struct CipCsrCap { size_t A_nnz, Q_nnz; };
+size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras, const CipCsrCap *cap = nullptr);
+int cip_create_in_slab(cip_handle *h, const struct cip_problem *pr, char *slab, size_t cap, unsigned extras, const CipCsrCap *csr_cap = nullptr);
+// What a branch of the host code asks about the CSR CONTENT of "the problem": inside a lock-step group, whose host code runs once on
+// problem 0's handle, a statement about every live problem of the group (the thread's mask); else about the handle.
+inline bool cip_grp_A_one_per_row(const cip_handle *h) {     // every one of them has at most one entry per row
+    return cip_in_batch() ? (cip_tl_bz.mask & ~cip_tl_bz.a_one_per_row) == 0 : h->A_one_per_row;
+}
+inline bool cip_grp_Q_nonempty(const cip_handle *h) {        // at least one of them stores an entry
+    return cip_in_batch() ? (cip_tl_bz.mask & cip_tl_bz.q_nonempty) != 0 : h->Q_nnz > 0;
+}
 size_t cip_driver_bytes(const cip_handle *h);                        // driver.hip: vectors of the interior-point loop
 // api.hip: resolve the pivot flag of the last factorisation (wait = 0: only if its read-back has already landed)
 int cip_factor_resolve(cip_handle *h, int wait);

@@ -84,6 +84,10 @@ struct CipBatchCtx {
     // bit z: problem z's factor is of the regularised matrix K + E -- its solves are refined against the true operator (api.hip:
     // cip_solve3x3_dev).  Kept current by the group (lockstep.hip: GroupLoop); 0 outside a batch, where h->reg_rel says the same
     unsigned long long reg_mask;
+    // What the group's host code -- run once, on problem 0's handle -- may not read from problem 0's CSR arrays alone (lockstep.hip:
+    // lockstep_group fills them from every handle; cip_handle.h: cip_grp_*).  Bit z: problem z's CSR A has at most one entry per row /
+    // its CSR Q has at least one entry / its CSR Q takes the wave-per-row mat-vec form
+    unsigned long long a_one_per_row = 0, q_nonempty = 0, q_wave = 0;
 };
 #define CIP_GATHER 64
 #define CIP_BATCH_MAX 64
@@ -337,6 +341,9 @@ int cip_spmv_csr(hipStream_t s, int rows, const int *rowptr, const int *colind, 
 #define CIP_SPMV_WAVE_MIN 8
 int cip_spmv_csr_wave(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val,
                       double alpha, const double *x, double beta, double *y);
+// per slice of a lock-step launch: bit z of wave_forms set -- slice z as cip_spmv_csr_wave, clear -- as cip_spmv_csr (their bits)
+int cip_spmv_csr_forms(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val,
+                       double alpha, const double *x, double beta, double *y, unsigned long long wave_forms);
 int cip_dots(hipStream_t s, int count, const double *const *x_host, const double *const *y_host,
              const int *len_host, double *scratch_dev, double *out_host);
 int cip_axpby(hipStream_t s, int len, double alpha, const double *x, double beta, double *y);

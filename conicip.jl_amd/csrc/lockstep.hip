@@ -1,5 +1,6 @@
 // Lock-step batches: B independent problems of IDENTICAL shape (n, m, p, cone list, route, dense / CSR A with the same
-// number of non-zeros, dense / CSR Q with the same number of non-zeros) advance through the interior-point loop of src/ConicIP.jl:468-939 together, every step of the
+// number of non-zeros, dense / CSR Q with the same number of non-zeros -- or, with cip_set_lockstep_ragged(1), any numbers: see
+// lockstep_group) advance through the interior-point loop of src/ConicIP.jl:468-939 together, every step of the
 // loop ONE launch whose grid carries the problem index in blockIdx.z (BASELINE config 5: 64 dense QPs of n = 2048;
 // SURVEY 7.4(5) "batch dimension").
 //
@@ -63,7 +64,10 @@ __global__ void k_gather_info(const int *info, double *gather, CipBatch cb) {
 }
 
 static thread_local bool g_stats_accumulate = false;     // cip_conicip_mixed: the groups' statistics add up
-bool same_shape(const cip_problem &a, const cip_problem &b) {
+// cip_set_lockstep_ragged: 1 = the nnz of a CSR A / Q and a CSR Q's mat-vec form are not part of the shape (process-wide; a call reads it once)
+std::atomic<int> g_ragged{0};
+// ragged: the numbers of non-zeros of CSR matrices do not count (dense beside CSR still does)
+bool same_shape(const cip_problem &a, const cip_problem &b, bool ragged) {
     if (a.n != b.n || a.m != b.m || a.p != b.p || a.ncones != b.ncones || a.route != b.route) return false;
     if ((a.A == nullptr) != (b.A == nullptr) || (a.flags & CIP_FLAG_DEVICE_PTRS) != (b.flags & CIP_FLAG_DEVICE_PTRS)) return false;
     for (int c = 0; c < a.ncones; ++c)
@@ -73,13 +77,13 @@ bool same_shape(const cip_problem &a, const cip_problem &b) {
     auto host_rowptr = [](const cip_problem &q) {
         return q.A == nullptr && q.m > 0 && q.A_rowptr && ((q.flags & CIP_FLAG_CSR_HOST) || !(q.flags & CIP_FLAG_DEVICE_PTRS));
     };
-    if (host_rowptr(a) && host_rowptr(b) && a.A_rowptr[a.m] != b.A_rowptr[b.m]) return false;
+    if (!ragged && host_rowptr(a) && host_rowptr(b) && a.A_rowptr[a.m] != b.A_rowptr[b.m]) return false;
     // Q: dense or CSR, and a CSR Q's number of non-zeros under the same rule
     if ((a.flags & CIP_FLAG_Q_CSR) != (b.flags & CIP_FLAG_Q_CSR)) return false;
     auto host_q_rowptr = [](const cip_problem &q) {
         return (q.flags & CIP_FLAG_Q_CSR) && q.Q_rowptr && ((q.flags & CIP_FLAG_CSR_HOST) || !(q.flags & CIP_FLAG_DEVICE_PTRS));
     };
-    if (host_q_rowptr(a) && host_q_rowptr(b) && a.Q_rowptr[a.n] != b.Q_rowptr[b.n]) return false;
+    if (!ragged && host_q_rowptr(a) && host_q_rowptr(b) && a.Q_rowptr[a.n] != b.Q_rowptr[b.n]) return false;
     return true;
 }
 
@@ -266,7 +270,13 @@ extern "C" int cip_lockstep_solve_block_for(int B) {
 }
 // One lock-step group (B <= CIP_BATCH_MAX problems of the same shape).  Returns 0 and fills res / y / w / v of every
 // problem, or an error code (nothing meaningful written).
-static int lockstep_group(int B, int call_count, const cip_problem *probs, const double *const *c, const double *const *b,
+// ragged (cip_set_lockstep_ragged(1), read by the call): the CSR matrices of the group's problems may differ in their numbers of
+// non-zeros.  Every problem is planned first (host work; CSR arrays in device memory cost the read-back of rowptr[m] they always did),
+// the slab is laid out for the group's largest A_nnz and Q_nnz, and every handle is carved with those capacities: problem z's arrays
+// sit at problem 0's offsets + z * stride, each handle uploads its own nnz, the tail above it is never read (every kernel walks the
+// row pointers).  What the host code, run once on problem 0's handle, would read from problem 0's CSR content becomes a statement
+// about the group (CipBatchCtx: a_one_per_row, q_nonempty, q_wave) -- also for groups of equal nnz, where the patterns still differ.
+static int lockstep_group(int B, int call_count, bool ragged, const cip_problem *probs, const double *const *c, const double *const *b,
                           const double *const *d, const cip_options *opt_in, double *const *y, double *const *w,
                           double *const *v, cip_result *res) {
     const auto t_start = std::chrono::steady_clock::now();
@@ -295,9 +305,15 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     // the loop's vectors, and what a regularised factor's refined solves would allocate on first use: part of every slab
     const unsigned extras = CIP_EXTRA_DRIVER | (keep_reg ? CIP_EXTRA_REFINE : 0u);
     G.h.assign(B, nullptr);
-    if ((rc = cip_plan(&probs[0], G.stream, &G.h[0]))) return rc;
-    if (G.h[0]->cs.nlarge > 0) { cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
-    const size_t slab = cip_handle_layout(nullptr, G.h[0], extras);
+    CipCsrCap cap = {0, 0};
+    for (int z = 0; z < B; ++z) {
+        if ((rc = cip_plan(&probs[z], G.stream, &G.h[z]))) return rc;
+        if (z == 0 && G.h[0]->cs.nlarge > 0) { cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
+        cap.A_nnz = std::max(cap.A_nnz, (size_t)G.h[z]->A_nnz);
+        cap.Q_nnz = std::max(cap.Q_nnz, (size_t)G.h[z]->Q_nnz);
+    }
+    const CipCsrCap *csr_cap = ragged ? &cap : nullptr;      // (not ragged: every handle's own nnz, which must then agree with problem 0's)
+    const size_t slab = cip_handle_layout(nullptr, G.h[0], extras, csr_cap);
     t_plan = since();
     // odd number of 256-byte granules: the same buffer of consecutive problems does not land on the same HBM channel
     size_t gran = (slab + 255) / 256;
@@ -309,24 +325,28 @@ static int lockstep_group(int B, int call_count, const cip_problem *probs, const
     G.gather_dev = (double *)(G.arena + G.stride * (size_t)B);
     CIP_HIP_CHECK(hipHostMalloc((void **)&G.gather_host, gather_bytes, hipHostMallocDefault));
     t_arena = since();
-    for (int z = 0; z < B; ++z) {
-        if (z > 0 && (rc = cip_plan(&probs[z], G.stream, &G.h[z]))) return rc;
-        cip_handle *hz = G.h[z];
-        // (device-resident CSR arrays with another number of non-zeros: same_shape could not look)
-        if (cip_handle_layout(nullptr, hz, extras) != slab) {
+    // (refused before anything is carved or uploaded.  Device-resident CSR arrays with another number of non-zeros: same_shape could not look)
+    for (int z = 1; z < B; ++z) {
+        if (cip_handle_layout(nullptr, G.h[z], extras, csr_cap) != slab) {
             cip_set_error("lock-step batch: problem %d does not fit problem 0's slab layout", z);
             return CIP_E_UNSUPPORTED;
         }
-        if ((rc = cip_create_in_slab(hz, &probs[z], G.arena + G.stride * (size_t)z, G.stride, extras))) return rc;
-        // the group's launches are problem 0's: a CSR Q whose longest row asks for the other mat-vec form (other bits) cannot follow
-        if (hz->Q_wave != G.h[0]->Q_wave) {
+        // not ragged: the group's Q mat-vec is one form for all, a CSR Q whose longest row asks for the other one (other bits) cannot follow
+        if (!ragged && G.h[z]->Q_wave != G.h[0]->Q_wave) {
             cip_set_error("lock-step batch: the CSR Q of problem %d takes another mat-vec form than problem 0's", z);
             return CIP_E_UNSUPPORTED;
         }
     }
+    CipBatchCtx ctx = {B, (long)G.stride, full_mask(B), G.gather_dev, G.gather_host, 0ull};
+    for (int z = 0; z < B; ++z) {
+        cip_handle *hz = G.h[z];
+        if ((rc = cip_create_in_slab(hz, &probs[z], G.arena + G.stride * (size_t)z, G.stride, extras, csr_cap))) return rc;
+        if (hz->A_one_per_row) ctx.a_one_per_row |= 1ull << z;
+        if (hz->Q_nnz > 0) ctx.q_nonempty |= 1ull << z;
+        if (hz->Q_wave) ctx.q_wave |= 1ull << z;
+    }
     t_create = since();
     hipStream_t s = G.stream;
-    CipBatchCtx ctx = {B, (long)G.stride, full_mask(B), G.gather_dev, G.gather_host, 0ull};
     BatchScope scope(ctx);
     GroupLoop L(G, keep_reg);
     if ((rc = L.run(c, b, d, o, res, nullptr, 0))) return rc;
@@ -391,8 +411,9 @@ extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const d
     if (count < 0 || (count > 0 && (!probs || !c || !y || !res))) { cip_set_error("cip_conicip_lockstep: null argument"); return CIP_E_INVALID; }
     if (count == 0) return 0;
     if ((probs[0].m > 0 && (!b || !v)) || (probs[0].p > 0 && (!d || !w))) { cip_set_error("cip_conicip_lockstep: null argument"); return CIP_E_INVALID; }
+    const bool ragged = g_ragged.load() != 0;                  // (read once: the shape check and every group's slab must agree)
     for (int i = 1; i < count; ++i)
-        if (!same_shape(probs[0], probs[i])) { cip_set_error("lock-step batch: problem %d differs in shape from problem 0", i); return CIP_E_UNSUPPORTED; }
+        if (!same_shape(probs[0], probs[i], ragged)) { cip_set_error("lock-step batch: problem %d differs in shape from problem 0", i); return CIP_E_UNSUPPORTED; }
     for (int c0 = 0; c0 < probs[0].ncones; ++c0)       // S cones of order >= 133 take chip-wide kernels with a single workspace (sdp_large.hip)
         if (probs[0].cone_type[c0] == CIP_CONE_S && probs[0].cone_dim[c0] >= CIP_LARGE_S_MIN * (CIP_LARGE_S_MIN + 1) / 2) {
             cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN);
@@ -403,7 +424,7 @@ extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const d
     auto range = [&](int i0, int i1) -> int {                // groups of up to 64 over [i0, i1), one after the other, on the calling thread
         for (int g0 = i0; g0 < i1; g0 += CIP_BATCH_MAX) {
             const int B = (i1 - g0 < CIP_BATCH_MAX) ? (i1 - g0) : CIP_BATCH_MAX;
-            const int rc = lockstep_group(B, count, probs + g0, c + g0, b ? b + g0 : nullptr, d ? d + g0 : nullptr, opt, y + g0,
+            const int rc = lockstep_group(B, count, ragged, probs + g0, c + g0, b ? b + g0 : nullptr, d ? d + g0 : nullptr, opt, y + g0,
                                           w ? w + g0 : nullptr, v ? v + g0 : nullptr, res + g0);
             if (rc) return rc;
         }
@@ -460,6 +481,7 @@ extern "C" int cip_conicip_mixed(int count, const cip_problem *probs, const doub
             if (q.cone_type[c0] == CIP_CONE_S && q.cone_dim[c0] >= CIP_LARGE_S_MIN * (CIP_LARGE_S_MIN + 1) / 2) return false;
         return true;
     };
+    const bool ragged = g_ragged.load() != 0;
     std::vector<std::vector<int>> bins;                         // bins[k][0] is the representative
     for (int i = 0; i < count; ++i) {
         if ((probs[i].m > 0 && (!b || !v || !b[i] || !v[i])) || (probs[i].p > 0 && (!d || !w || !d[i] || !w[i])) || !c[i] || !y[i]) {
@@ -468,7 +490,7 @@ extern "C" int cip_conicip_mixed(int count, const cip_problem *probs, const doub
         }
         size_t k = 0;
         for (; k < bins.size(); ++k)
-            if (same_shape(probs[bins[k][0]], probs[i])) break;
+            if (same_shape(probs[bins[k][0]], probs[i], ragged)) break;
         if (k == bins.size()) bins.emplace_back();
         bins[k].push_back(i);
     }
@@ -497,7 +519,7 @@ extern "C" int cip_conicip_mixed(int count, const cip_problem *probs, const doub
         if (bin.size() < 2 || !lockstep_ok(probs[bin[0]])) { rest.insert(rest.end(), bin.begin(), bin.end()); continue; }
         const int rc = run(bin, true);
         // a bin that turns out not to qualify (same shape, yet a different slab layout: CSR arrays in device memory with differing
-        // numbers of non-zeros) has written nothing: its problems join the thread pool's share instead of failing the batch
+        // numbers of non-zeros, or a CSR Q of another mat-vec form -- neither with cip_set_lockstep_ragged(1)) has written nothing: its problems join the thread pool's share instead of failing the batch
         if (rc == CIP_E_UNSUPPORTED) { rest.insert(rest.end(), bin.begin(), bin.end()); continue; }
         if (rc) return rc;
     }
@@ -528,6 +550,13 @@ extern "C" int cip_lockstep_stats(int *out3) {
 extern "C" int cip_set_lockstep_regularize(int on) {
     const int prev = g_keep_regularized.load();
     if (on == 0 || on == 1) g_keep_regularized.store(on);
+    return prev;
+}
+// 1: problems whose CSR matrices differ in their numbers of non-zeros (or whose CSR Q take different mat-vec forms) share a lock-step
+// group; 0 (default): the nnz is part of the shape.  Process-wide; any other argument only queries.  Returns the previous value
+extern "C" int cip_set_lockstep_ragged(int on) {
+    const int prev = g_ragged.load();
+    if (on == 0 || on == 1) g_ragged.store(on);
     return prev;
 }
 // the calling thread's last cip_conicip_lockstep / cip_conicip_mixed: problems switched to the regularised factorisation inside their group

@@ -168,15 +168,20 @@ int cip_symv_lower(hipStream_t s, int n, double alpha, const double *Q, long ldq
 
 // CSR spmv, one wave per row group: rows are short in the KKT use (identity-like A), so use
 // thread-per-row for simplicity (coalescing over rows of rowptr; gathers from x).
-__global__ __launch_bounds__(256) void k_spmv_csr(int rows, const int *rowptr, const int *colind, const double *val,
-                                                   double alpha, const double *x, double beta, double *y, CipBatch cb) {
-    CIP_BATCH_GUARD(cb);
-    CIP_BO5(cb, rowptr, colind, val, x, y);
+// (the two forms' bodies, shared with k_spmv_csr_forms below: one source, one accumulation order, one epilogue)
+__device__ __forceinline__ void spmv_thread_rows(int rows, const int *rowptr, const int *colind, const double *val,
+                                                 double alpha, const double *x, double beta, double *y) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
     double s = 0;
     for (int q = rowptr[r]; q < rowptr[r + 1]; ++q) s += val[q] * x[colind[q]];
     y[r] = alpha * s + (beta == 0.0 ? 0.0 : beta * y[r]);
+}
+__global__ __launch_bounds__(256) void k_spmv_csr(int rows, const int *rowptr, const int *colind, const double *val,
+                                                   double alpha, const double *x, double beta, double *y, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO5(cb, rowptr, colind, val, x, y);
+    spmv_thread_rows(rows, rowptr, colind, val, alpha, x, beta, y);
 }
 
 int cip_spmv_csr(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val, double alpha,
@@ -190,10 +195,8 @@ int cip_spmv_csr(hipStream_t s, int rows, const int *rowptr, const int *colind, 
 // One wave per row (four rows per workgroup): lane l takes the row's entries l, l + 64, .. in that order, the 64 partial sums
 // are added by cip_wave_sum's fixed tree -- the same bits on every run.  For long rows (a CSR Q that is nearly full: thread per
 // row reads each row serially from one lane); an empty row gives y = beta y, and y is not read when beta == 0.
-__global__ __launch_bounds__(256) void k_spmv_csr_wave(int rows, const int *rowptr, const int *colind, const double *val,
-                                                        double alpha, const double *x, double beta, double *y, CipBatch cb) {
-    CIP_BATCH_GUARD(cb);
-    CIP_BO5(cb, rowptr, colind, val, x, y);
+__device__ __forceinline__ void spmv_wave_rows(int rows, const int *rowptr, const int *colind, const double *val,
+                                               double alpha, const double *x, double beta, double *y) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;                                      // (wave-uniform: the wave sum below sees whole waves only)
@@ -203,10 +206,38 @@ __global__ __launch_bounds__(256) void k_spmv_csr_wave(int rows, const int *rowp
     s = wsum(s);
     if (lane == 0) y[r] = alpha * s + (beta == 0.0 ? 0.0 : beta * y[r]);
 }
+__global__ __launch_bounds__(256) void k_spmv_csr_wave(int rows, const int *rowptr, const int *colind, const double *val,
+                                                        double alpha, const double *x, double beta, double *y, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO5(cb, rowptr, colind, val, x, y);
+    spmv_wave_rows(rows, rowptr, colind, val, alpha, x, beta, y);
+}
 int cip_spmv_csr_wave(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val, double alpha,
                       const double *x, double beta, double *y) {
     if (rows <= 0) return 0;
     cip_launch_b(k_spmv_csr_wave, dim3((rows + 3) / 4), dim3(256), 0, s, rows, rowptr, colind, val, alpha, x, beta, y);
+    CIP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// A ragged lock-step group (lockstep.hip): the CSR matrices of its problems differ, and with them the form their longest row selects.
+// One launch: slice z (blockIdx.z, one problem) runs as k_spmv_csr_wave when bit z of `wave_forms` is set and as k_spmv_csr when it is
+// clear -- the body of that kernel, hence its bits.  The choice is uniform over a workgroup, so the wave sum still sees whole waves.
+// The grid is the wave form's (rows / 4 workgroups per slice); a thread-form slice needs rows / 256 of them, the surplus exits.
+__global__ __launch_bounds__(256) void k_spmv_csr_forms(int rows, const int *rowptr, const int *colind, const double *val, double alpha,
+                                                         const double *x, double beta, double *y, unsigned long long wave_forms, CipBatch cb) {
+    CIP_BATCH_GUARD(cb);
+    CIP_BO5(cb, rowptr, colind, val, x, y);
+    if ((wave_forms >> blockIdx.z) & 1ull) { spmv_wave_rows(rows, rowptr, colind, val, alpha, x, beta, y); return; }
+    if ((long)blockIdx.x * 256 >= rows) return;
+    spmv_thread_rows(rows, rowptr, colind, val, alpha, x, beta, y);
+}
+int cip_spmv_csr_forms(hipStream_t s, int rows, const int *rowptr, const int *colind, const double *val, double alpha,
+                       const double *x, double beta, double *y, unsigned long long wave_forms) {
+    if (rows <= 0) return 0;
+    const bool any_wave = (wave_forms & (cip_in_batch() ? cip_tl_bz.mask : 1ull)) != 0;
+    cip_launch_b(k_spmv_csr_forms, dim3(any_wave ? (rows + 3) / 4 : (rows + 255) / 256), dim3(256), 0, s, rows, rowptr, colind, val, alpha, x,
+                 beta, y, wave_forms);
     CIP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -255,13 +255,18 @@ int cip_conicip_problems(int count, const cip_problem *probs, const double *cons
  * the static order (every LP with a free variable, singular Q with free variables) needs the regularised factorisation.  With
  * cip_set_lockstep_regularize(0), the default, it leaves the group and is solved by the one-problem loop afterwards; with
  * cip_set_lockstep_regularize(1) it stays: the group regularises its matrix and refines its solves under a mask of its own, with
- * the launches and the bits of the one-problem loop.  Either way a problem whose panel chain gave up an in-launch wait leaves. */
+ * the launches and the bits of the one-problem loop.  Either way a problem whose panel chain gave up an in-launch wait leaves.
+ * The number of non-zeros of a CSR A or Q, and the mat-vec form a CSR Q's longest row selects, are part of the shape unless
+ * cip_set_lockstep_ragged(1) has been called: then problems that differ in them share a group (its slabs are laid out for the
+ * group's largest CSR arrays; every problem's Q mat-vec runs in its own form), with the same bits per problem. */
 int cip_conicip_lockstep(int count, const cip_problem *probs, const double *const *c, const double *const *bvec,
                          const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                          double *const *v, cip_result *res);
 /* ANY mix of problems: those that share a shape with at least one other problem of the batch (and qualify for lock-step)
  * advance together, shape group by shape group; the others go through cip_conicip_problems' thread pool (`in_flight`
  * threads).  Per problem the result is that of the entry point it went through; cip_lockstep_stats adds up over the groups.
+ * The bins follow cip_conicip_lockstep's notion of shape: with cip_set_lockstep_ragged(1) CSR matrices of differing numbers of
+ * non-zeros fall into one bin, with 0 (the default) each number is a bin of its own.
  * (The reference solves one problem per conicIP call, src/ConicIP.jl:472-480: a batch is N independent calls.) */
 int cip_conicip_mixed(int count, const cip_problem *probs, const double *const *c, const double *const *bvec,
                       const double *const *d, const cip_options *opt, double *const *y, double *const *w,
@@ -273,6 +278,11 @@ int cip_lockstep_stats(int *out3);
 /* 1: problems that need the regularised factorisation stay in their lock-step group (see cip_conicip_lockstep); 0 (default): they
  * leave it.  Process-wide; returns the previous value; any other argument only queries. */
 int cip_set_lockstep_regularize(int on);
+/* 1: problems of one shape (n, m, p, cone list, route, dense-or-CSR A, dense-or-CSR Q) whose CSR matrices differ in their
+ * numbers of non-zeros, or whose CSR Q take different mat-vec forms, share a lock-step group; 0 (default): they do not
+ * (cip_conicip_lockstep: CIP_E_UNSUPPORTED, nothing written; cip_conicip_mixed: thread pool).  Process-wide; returns the
+ * previous value; any other argument only queries. */
+int cip_set_lockstep_ragged(int on);
 /* the calling thread's last cip_conicip_lockstep / cip_conicip_mixed: how many problems were switched to the regularised factorisation
  * inside their group (summed over the groups, like cip_lockstep_stats; its third entry counts only the problems that still left) */
 int cip_lockstep_regularized(int *count);
@@ -280,7 +290,8 @@ int cip_lockstep_regularized(int *count);
  * groups fill each other's launch-latency gaps; per problem nothing changes: same kernels, same solve block, same bits).  k = 1: one
  * group after the other (the form up to round 5).  Also CIP_LOCKSTEP_SPLIT.  Process-wide; returns the previous value (k < 1: query).
  * With k > 1 a call that cip_conicip_lockstep refuses with CIP_E_UNSUPPORTED for a slab-layout reason found inside a group (CSR arrays
- * in device memory with differing numbers of non-zeros) may already have written other groups' results. */
+ * in device memory with differing numbers of non-zeros, with cip_set_lockstep_ragged(0) only: with 1 such arrays share a group) may
+ * already have written other groups' results. */
 int cip_set_lockstep_split(int k);
 int cip_conicip_many(cip_handle *const *handles, int count, const double *const *c, const double *const *bvec,
                      const double *const *d, const cip_options *opt, double *const *y, double *const *w,

@@ -352,14 +352,15 @@ the loop in lock-step (one launch per step for all of them), the others through 
 library (`sparse_q = true`: every Q as CSR; the form is part of the shape).  `keep_regularized = true`: a problem whose
 factorisation needs the regularised LDL' (an LP with a free variable, `Q = spzeros` with free variables) stays in its lock-step group
 instead of being solved alone afterwards (`cip_set_lockstep_regularize`, set around the call and restored; `regularized[]`, a
-`Ref{Cint}`, receives how many were).  `problems[i]` is a tuple `(Q, c, A, b, cone_dims)` or `(Q, c, A, b, cone_dims, G, d)`; the keywords are
+`Ref{Cint}`, receives how many were).  `ragged = true`: problems of one shape whose CSR matrices differ in their numbers of
+non-zeros share a lock-step group instead of going through the threads (`cip_set_lockstep_ragged`, set and restored the same way).  `problems[i]` is a tuple `(Q, c, A, b, cone_dims)` or `(Q, c, A, b, cone_dims, G, d)`; the keywords are
 `conicIP`'s and apply to every problem.  (The reference solves one problem per `conicIP` call, src/ConicIP.jl:472-480: this
 is N independent calls.  Sharding over several GPUs is one process per GPU, problem i on rank i mod N.)
 """
 function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, route = CIP_ROUTE_SCHUR,
                            optTol = 1e-6, DTB = 0.01, verbose = false, maxRefinementSteps = 3, maxIters = 100,
                            cache_nestodd = false, infeasTol = optTol, refinementThreshold = optTol / 1e7, stats = nothing,
-                           sparse_q = false, keep_regularized = false, regularized = nothing)
+                           sparse_q = false, keep_regularized = false, regularized = nothing, ragged = false)
     k = length(problems)
     k == 0 && return ConicIP.Solution[]
     staged = Vector{_Staged}(undef, k)
@@ -382,10 +383,12 @@ function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, rou
         # (a NULL entry is fine where the problem's m or p is 0: include/cipkkt.h, cip_conicip_mixed)
         # (the switch is process-wide: put back before the return code is looked at, so that an error leaves it as it was)
         prev = keep_regularized ? ccall(_sym(:cip_set_lockstep_regularize), Cint, (Cint,), 1) : Cint(-1)
+        prev_ragged = ragged ? ccall(_sym(:cip_set_lockstep_ragged), Cint, (Cint,), 1) : Cint(-1)
         rc = ccall(_sym(:cip_conicip_mixed), Cint,
             (Cint, Ptr{CipProblem}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ref{CipOptions},
              Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{CipResult}, Cint),
             k, probs, ptrs(cs), ptrs(bs), ptrs(ds), opt, ptrs(ys), ptrs(ws), ptrs(vs), res, in_flight)
+        prev_ragged >= 0 && ccall(_sym(:cip_set_lockstep_ragged), Cint, (Cint,), prev_ragged)
         prev >= 0 && ccall(_sym(:cip_set_lockstep_regularize), Cint, (Cint,), prev)
         _cipcheck(rc)
         regularized === nothing || _cipcheck(ccall(_sym(:cip_lockstep_regularized), Cint, (Ref{Cint},), regularized))
