@@ -50,7 +50,6 @@ void cip_range_push(const char *name) {
     if (g_roctx_push) (void)g_roctx_push(name);
 }
 void cip_range_pop(void) { if (g_roctx_pop) (void)g_roctx_pop(); }
-struct CipRange { explicit CipRange(const char *n) { cip_range_push(n); } ~CipRange() { cip_range_pop(); } };
 
 static int rup(int x, int q) { return ((x + q - 1) / q) * q; }
 
@@ -78,44 +77,6 @@ int cip_handle_alloc(cip_handle *h, void **out, size_t bytes) {
     CIP_HIP_CHECK(e);
     h->owned.push_back(*out);
     return debug_poison(*out, bytes);
-}
-#define DMALLOC(ptr, bytes)                                                        \
-    do {                                                                           \
-        int rc__ = cip_handle_alloc(h, (void **)&(ptr), (size_t)(bytes));          \
-        if (rc__) return rc__;                                                     \
-    } while (0)
-
-// ---- views of the handle's packed (8-byte granular) scratch buffers; each layout function sizes the allocation and carves for every user
-#define CIP_MANY_CHUNK 64
-struct Vec3 { double *x, *y, *z; };            // an (n, p, m) triple of k columns each
-static Vec3 take3(CipLayout &L, const cip_handle *h, size_t k = 1) { return Vec3{L.take<double>(h->n * k, 8), L.take<double>(h->p * k, 8), L.take<double>(h->m * k, 8)}; }
-// h->stage (k = cap = 1), h->many_stage (cap = CIP_MANY_CHUNK): input and output triple of k <= cap columns, each at the front of its half
-struct StageView { Vec3 in, out; };
-static size_t stage_layout(CipLayout L, const cip_handle *h, size_t k, size_t cap, StageView *v) {
-    const size_t slack = ((size_t)h->n + h->p + h->m) * (cap - k);
-    v->in = take3(L, h, k); L.take<double>(slack, 8);
-    v->out = take3(L, h, k); L.take<double>(slack, 8);
-    return L.bytes();
-}
-// h->ref: right-hand side, residual and correction of the refined solve, 8 spare doubles behind each
-struct RefView { Vec3 rhs, res, cor; };
-static size_t ref_layout(CipLayout L, const cip_handle *h, RefView *v) {
-    for (Vec3 *b : {&v->rhs, &v->res, &v->cor}) { *b = take3(L, h); L.take<double>(8, 8); }
-    return L.bytes();
-}
-// what the refined solves of a regularised factor allocate on first use; a lock-step group that may regularise has them in its
-// handles' slabs instead (handle_layout: CIP_EXTRA_REFINE)
-static int alloc_refine_buffers(cip_handle *h) {
-    if (!h->ref) { RefView v; DMALLOC(h->ref, ref_layout(nullptr, h, &v)); }
-    if (!h->c2x2 && h->m > 0 && h->route == CIP_ROUTE_SCHUR) DMALLOC(h->c2x2, sizeof(double) * h->m);
-    return 0;
-}
-// h->many, CIP_MANY_CHUNK columns each: the Npad-row right-hand sides R, the m-row blocks T and U of the Schur route, the sweeps' scratch S
-struct ManyView { double *R, *T, *U, *S; };
-static size_t many_layout(CipLayout L, const cip_handle *h, ManyView *v) {
-    const size_t c = CIP_MANY_CHUNK;
-    *v = ManyView{L.take<double>(c * h->Npad, 8), L.take<double>(c * h->m, 8), L.take<double>(c * h->m, 8), L.take<double>(c * h->ws.Bs, 8)};
-    return L.bytes();
 }
 
 static void free_all(cip_handle *h) {
@@ -276,7 +237,6 @@ static int upload_problem(cip_handle *h, const cip_problem *pr) {
     const int n = h->n, m = h->m, p = h->p;
     const bool dev = (pr->flags & CIP_FLAG_DEVICE_PTRS) != 0;
     hipStream_t s = h->stream;
-    int rc;
     const bool was_live = h->staging_live;                  // an earlier upload may still be reading A's staging vectors
     cip_sdp_large_invalidate(h->cs.lg);                     // (the mat(a_i) images of the large S cones follow A)
     if (h->Q_sparse) {
@@ -286,15 +246,15 @@ static int upload_problem(cip_handle *h, const cip_problem *pr) {
             CIP_HIP_CHECK(hipMemcpyAsync(h->Q_v, h->st_qv.data(), sizeof(double) * h->Q_nnz, hipMemcpyHostToDevice, s));
         }
         h->staging_live = true;
-    } else if ((rc = upload_matrix(h->Q, n, pr->Q, pr->ldq > 0 ? pr->ldq : n, n, n, dev, s))) return rc;
+    } else CIP_TRY(upload_matrix(h->Q, n, pr->Q, pr->ldq > 0 ? pr->ldq : n, n, n, dev, s));
     if (p > 0) {
-        if ((rc = upload_matrix(h->G, p, pr->G, pr->ldg > 0 ? pr->ldg : p, p, n, dev, s))) return rc;
-        if ((rc = transpose_dev(s, h->G, p, p, n, h->Gt, n))) return rc;
+        CIP_TRY(upload_matrix(h->G, p, pr->G, pr->ldg > 0 ? pr->ldg : p, p, n, dev, s));
+        CIP_TRY(transpose_dev(s, h->G, p, p, n, h->Gt, n));
     }
     if (!h->A_sparse) {
         if (m > 0) {
-            if ((rc = upload_matrix(h->A, m, pr->A, pr->lda > 0 ? pr->lda : m, m, n, dev, s))) return rc;
-            if ((rc = transpose_dev(s, h->A, m, m, n, h->At, h->npad))) return rc;
+            CIP_TRY(upload_matrix(h->A, m, pr->A, pr->lda > 0 ? pr->lda : m, m, n, dev, s));
+            CIP_TRY(transpose_dev(s, h->A, m, m, n, h->At, h->npad));
         }
         return 0;
     }
@@ -367,8 +327,7 @@ static int handle_plan(const cip_problem *pr, cip_handle *h) {
     if (pr->route != CIP_ROUTE_SCHUR && pr->route != CIP_ROUTE_FULL3X3) { cip_set_error("bad route"); return CIP_E_INVALID; }
     if (q_csr) {                                          // checked on the host before anything is allocated on the device
         int maxrow = 0;
-        const int rcq = stage_Q_csr(h, pr, -1, &maxrow);
-        if (rcq) return rcq;
+        CIP_TRY(stage_Q_csr(h, pr, -1, &maxrow));
         h->Q_sparse = true; h->Q_nnz = h->st_qrp[n]; h->Q_wave = q_wave_form(maxrow);
     }
     h->n = n; h->m = m; h->p = p; h->ncones = pr->ncones; h->route = pr->route;
@@ -543,7 +502,7 @@ size_t cip_handle_layout(CipLayout L, cip_handle *h, unsigned extras, const CipC
     take(L, h->rhs, h->Npad);
     take(L, h->mt1, m); take(L, h->mt2, m); take(L, h->mt3, m); take(L, h->nt1, n); take(L, h->pt1, p);
     take(L, h->dot_scratch, 32 * 32 + 32);
-    { StageView v; h->stage = (double *)L.take<char>(stage_layout(nullptr, h, 1, 1, &v)); }
+    { StageView v; h->stage = (double *)L.take<char>(stage_layout(nullptr, h, 1, &v)); }
     if (extras & CIP_EXTRA_DRIVER) h->drv = (double *)L.take<char>(cip_driver_bytes(h));
     if (extras & CIP_EXTRA_REFINE) {
         RefView v;
@@ -558,7 +517,6 @@ static int handle_fill(const cip_problem *pr, cip_handle *h, bool final_sync) {
     ConeSet &cs = h->cs;
     const int n = h->n, m = h->m, p = h->p;
     hipStream_t s = h->stream;   // default (null) stream until cip_set_stream
-    int rc;
     auto upload = [s](auto *dst, const auto &src, size_t count) {
         return count ? hipMemcpyAsync(dst, src.data(), sizeof(*dst) * count, hipMemcpyHostToDevice, s) : hipSuccess;
     };
@@ -570,7 +528,7 @@ static int handle_fill(const cip_problem *pr, cip_handle *h, bool final_sync) {
         if (cs.nlarge > 0) {
             int rmax_large = 0;
             for (int li = 0; li < cs.nlarge; ++li) if (h->h_cones[cs.large_cone[li]].r > rmax_large) rmax_large = h->h_cones[cs.large_cone[li]].r;
-            if ((rc = cip_sdp_large_create(rmax_large, cs.nlarge, n, &cs.lg))) return rc;
+            CIP_TRY(cip_sdp_large_create(rmax_large, cs.nlarge, n, &cs.lg));
         }
         CIP_HIP_CHECK(upload(cs.d_sidx, h->st_sidx, cs.ns));
         CIP_HIP_CHECK(hipMemsetAsync(cs.d_sdpflag, 0, sizeof(int) * sdp_flag_words(cs), s));
@@ -587,7 +545,7 @@ static int handle_fill(const cip_problem *pr, cip_handle *h, bool final_sync) {
             CIP_HIP_CHECK(hipMemsetAsync(h->WtS, 0, sizeof(double) * (size_t)h->npad * h->mSpad, s));
         }
     }
-    if ((rc = upload_problem(h, pr))) return rc;
+    CIP_TRY(upload_problem(h, pr));
     h->ws.x_zeroed = &h->x_zeroed;
     h->ws.side = h->in_slab ? nullptr : &h->ldlt_side;    // (handles of a lock-step arena factor inside batched launches)
     // pivot signs of the quasi-definite order: Schur route [S G'; G 0] = n positive, p negative; literal 3x3 in the
@@ -596,8 +554,8 @@ static int handle_fill(const cip_problem *pr, cip_handle *h, bool final_sync) {
     CIP_HIP_CHECK(hipEventCreate(&h->ev0)); CIP_HIP_CHECK(hipEventCreate(&h->ev1)); CIP_HIP_CHECK(hipEventCreate(&h->ev2));
     // (the pinned pivot-flag words are allocated by the first factorisation: pinned allocations cost ~0.1 ms each, and the
     //  64 handles of a lock-step group never use theirs)
-    if ((rc = cip_cones_identity_scaling(s, cs))) return rc;
-    if ((rc = cip_sdp_scaling_changed(s, cs))) return rc;
+    CIP_TRY(cip_cones_identity_scaling(s, cs));
+    CIP_TRY(cip_sdp_scaling_changed(s, cs));
     // the caller's Q / A / G may go away as soon as a public create returns: wait for the uploads.  A lock-step group
     // keeps its problems alive for the whole call and creates its 64 handles without a single host wait.
     if (final_sync) CIP_HIP_CHECK(hipStreamSynchronize(s));
@@ -636,8 +594,8 @@ int cip_create_in_slab(cip_handle *h, const cip_problem *pr, char *slab, size_t 
     if (bytes > cap) { cip_set_error("lock-step batch: a handle of %zu bytes in a slab of %zu", bytes, cap); return CIP_E_UNSUPPORTED; }
     h->in_slab = true;
     cip_handle_layout(slab, h, extras, csr_cap);
-    const int rc = debug_poison(slab, bytes);
-    return rc ? rc : handle_fill(pr, h, false);
+    CIP_TRY(debug_poison(slab, bytes));
+    return handle_fill(pr, h, false);
 }
 
 extern "C" int cip_create(int n, int m, int p, int ncones, const int *cone_type, const int *cone_dim, const double *Q,
@@ -664,19 +622,18 @@ extern "C" int cip_update_problem(cip_handle *h, const cip_problem *pr) {
         return CIP_E_INVALID;
     }
     if ((!h->Q_sparse && !pr->Q) || (h->p > 0 && !pr->G)) { cip_set_error("NULL matrix"); return CIP_E_INVALID; }
-    int rc;
     if (h->Q_sparse) {
         // refused (other nnz, or the level-1 check fails) before anything of the handle's device state is touched: it stays usable
         if (h->staging_live) { CIP_HIP_CHECK(hipStreamSynchronize(h->stream)); h->staging_live = false; }
         int maxrow = 0;
-        if ((rc = stage_Q_csr(h, pr, h->Q_nnz, &maxrow))) return rc;
+        CIP_TRY(stage_Q_csr(h, pr, h->Q_nnz, &maxrow));
         h->Q_wave = q_wave_form(maxrow);
     }
-    if ((rc = upload_problem(h, pr))) return rc;
+    CIP_TRY(upload_problem(h, pr));
     h->assembled = h->factored = false;
     h->info_pending = false;
     h->reg_rel = 0.0; h->n_regularized = 0;          // a fresh problem starts unregularised, as a fresh handle does
-    if ((rc = cip_cones_identity_scaling(h->stream, h->cs))) return rc;
+    CIP_TRY(cip_cones_identity_scaling(h->stream, h->cs));
     return cip_sdp_scaling_changed(h->stream, h->cs);
 }
 
@@ -715,8 +672,8 @@ extern "C" int cip_get_scaling_packed(cip_handle *h, double *packedF) {
 extern "C" int cip_set_scaling_identity(cip_handle *h) {
     if (!h) return CIP_E_INVALID;
     h->assembled = h->factored = false;
-    int rc = cip_cones_identity_scaling(h->stream, h->cs);
-    return rc ? rc : cip_sdp_scaling_changed(h->stream, h->cs);
+    CIP_TRY(cip_cones_identity_scaling(h->stream, h->cs));
+    return cip_sdp_scaling_changed(h->stream, h->cs);
 }
 extern "C" int cip_set_scaling_from_iterate_dev(cip_handle *h, const double *v, const double *s, double *lambda_out) {
     if (!h || (h->m > 0 && (!v || !s))) { cip_set_error("NULL argument"); return CIP_E_INVALID; }
@@ -738,8 +695,8 @@ extern "C" int cip_assemble_only(cip_handle *h) {
 // (profiles/r2/c5_*) shows 16.8 ms of serial kernel time per problem and an average of 3.4 kernels executing at once with
 // 8 problems in flight (more hardware queues make it worse): the ceiling is the number of concurrently progressing
 // launch-latency-bound streams, which only a lock-step batch (one launch for many problems) would lift.  Off by default
-// (rocprofv3 also crashed on the graph path with several host threads).
-static bool graph_wanted(cip_handle *h) {
+// (rocprofv3 also crashed on the graph path with several host threads).  graph_run (cip_handle.h) records and replays.
+bool cip_graph_wanted(cip_handle *h) {
     if (h->graph_state == 0) {
         const int npmax = cip_env_int("CIP_GRAPH_NMAX", 4096);
         h->graph_state = (h->Npad <= npmax && cip_env_int("CIP_GRAPH", 0) == 1 && !h->timing && !h->ws.prof) ? 1 : -1;
@@ -747,24 +704,6 @@ static bool graph_wanted(cip_handle *h) {
     return h->graph_state == 1;
 }
 thread_local CipGraphBuilder *cip_tl_builder = nullptr;
-template <class F>
-static int graph_run(cip_handle *h, hipGraphExec_t *exec, F &&enqueue, bool *replayed = nullptr) {
-    if (cip_in_batch() || !graph_wanted(h) || h->timing || h->ws.prof) return enqueue();
-    if (!*exec) {
-        CipGraphBuilder b = {nullptr, nullptr, false, true};
-        if (hipGraphCreate(&b.graph, 0) != hipSuccess) { (void)hipGetLastError(); h->graph_state = -1; return enqueue(); }
-        cip_tl_builder = &b;
-        const int rc = enqueue();                // records kernel nodes, launches nothing
-        cip_tl_builder = nullptr;
-        hipError_t ei = hipErrorUnknown;
-        if (rc == 0 && b.ok && b.have_last) ei = hipGraphInstantiate(exec, b.graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(b.graph);
-        if (ei != hipSuccess) { (void)hipGetLastError(); *exec = nullptr; h->graph_state = -1; return enqueue(); }
-    }
-    CIP_HIP_CHECK(hipGraphLaunch(*exec, h->stream));
-    if (replayed) *replayed = true;
-    return 0;
-}
 
 // the factorisation's four flag words -> host-mapped pinned memory, by a store from the device.  (Until round 5 a 16-byte
 // hipMemcpyAsync: a blit kernel between two barriers -- in the kernel trace the main queue stood idle for 24 us between the last
@@ -799,8 +738,7 @@ static int info_landed(cip_handle *h, bool wait, bool *landed) {
 }
 // assembly + LDL' + an asynchronous read-back of the pivot flag into pinned host memory; nothing here waits for the GPU
 static int factor_enqueue(cip_handle *h) {
-    int rc;
-    { CipRange rg("cip:assemble"); if ((rc = cip_assemble(h, true))) return rc; }
+    { CipRange rg("cip:assemble"); CIP_TRY(cip_assemble(h, true)); }
     if (h->timing) CIP_HIP_CHECK(hipEventRecord(h->ev1, h->stream));
     {
         CipRange rg("cip:ldlt");
@@ -811,15 +749,13 @@ static int factor_enqueue(cip_handle *h) {
         h->gx_factor_lazyC = h->ws.lazyC;
         h->gx_factor_unfused = h->ws.unfused;
         bool replayed = false;
-        if ((rc = graph_run(h, &h->gx_factor, [&]() {
-                 const int r = cip_ldlt_factor(h->stream, h->K, h->Npad, h->ldk, h->ws);
-                 if (cip_tl_builder) h->gx_factor_fused = cip_ldlt_last_factor_fused();
-                 return r;
-             }, &replayed)))
-            return rc;
+        CIP_TRY(graph_run(h, &h->gx_factor, [&]() {
+            const int r = cip_ldlt_factor(h->stream, h->K, h->Npad, h->ldk, h->ws);
+            if (cip_tl_builder) h->gx_factor_fused = cip_ldlt_last_factor_fused();
+            return r;
+        }, &replayed));
         // the give-up test hook of a replay decides from the chain the graph holds (a direct launch: cip_ldlt_factor has seen to it)
-        if (replayed && (rc = cip_ldlt_debug_giveup(h->stream, h->K, h->Npad, h->ldk, h->ws, h->gx_factor_fused)))
-            return rc;
+        if (replayed) CIP_TRY(cip_ldlt_debug_giveup(h->stream, h->K, h->Npad, h->ldk, h->ws, h->gx_factor_fused));
     }
     h->n_factor += 1;
     if (!h->info_host) {
@@ -839,34 +775,41 @@ static int factor_enqueue(cip_handle *h) {
     return 0;
 }
 
-// Resolve the pivot flag of the last factorisation.  wait = false: only if the read-back has already landed (no host
-// wait; the caller goes ahead speculatively otherwise).  A zero / non-finite / wrong-sign pivot means [S G'; G 0] is not
-// quasi-definite in the static order (typically an LP or a QP with singular Q and free variables: S is singular although
-// the KKT matrix is not).  The reference's pivoting LU / QR does not care; the static-order LDL' switches to a
-// regularised factorisation, once, for good -- and if that one fails too the error is reported (CIP_E_SINGULAR).
-static int factor_resolve(cip_handle *h, bool wait);
-int cip_factor_resolve(cip_handle *h, int wait) { return factor_resolve(h, wait != 0); }
 // enqueue the factorisation again and wait for its flags (after a give-up, or with the regularisation switched on).  A give-up of
 // the fused chain in THIS factorisation is answered at once: the handle switches to the three-launch chain and redoes it.
 static int refactor_and_wait(cip_handle *h) {
     for (;;) {
-        int rc;
-        if ((rc = factor_enqueue(h))) return rc;
-        { bool landed = false; if ((rc = info_landed(h, true, &landed))) return rc; }
+        CIP_TRY(factor_enqueue(h));
+        { bool landed = false; CIP_TRY(info_landed(h, true, &landed)); }
         h->info_pending = false;
         if (h->info_host[3] == 0 || h->info_host[1] != 0 || h->ws.unfused) return 0;
         h->ws.unfused = 1;
         h->n_chain_fallbacks += 1;
     }
 }
-static int factor_resolve(cip_handle *h, bool wait) {
+// the two verdicts on a factorisation that was (re)done.  The chain gave up for good (flag words [3] or [1], below): there is no factor
+static int chain_gave_up(cip_handle *h) {
+    if (h->info_host[3] == 0 && h->info_host[1] == 0) return 0;
+    cip_set_error("LDL': in-launch wait of the panel chain gave up (%d)", h->info_host[3]);
+    h->factored = false;
+    return CIP_E_HIP;
+}
+// ... and the redone factor is good, but `spec` solves were enqueued on the one it replaces (`why` it was replaced)
+static int solves_to_repeat(int spec, const char *why) {
+    if (spec <= 0) return 0;
+    cip_set_error("LDL': %d solve(s) were enqueued on a factorisation %s -- repeat them", spec, why);
+    return CIP_E_RETRY;
+}
+// Resolve the pivot flag of the last factorisation.  wait = false: only if the read-back has already landed (no host
+// wait; the caller goes ahead speculatively otherwise).  A zero / non-finite / wrong-sign pivot means [S G'; G 0] is not
+// quasi-definite in the static order (typically an LP or a QP with singular Q and free variables: S is singular although
+// the KKT matrix is not).  The reference's pivoting LU / QR does not care; the static-order LDL' switches to a
+// regularised factorisation, once, for good -- and if that one fails too the error is reported (CIP_E_SINGULAR).
+int cip_factor_resolve(cip_handle *h, bool wait) {
     if (!h->info_pending) return 0;
-    {
-        bool landed = false;
-        const int rc = info_landed(h, wait, &landed);
-        if (rc) return rc;
-        if (!landed) return 0;
-    }
+    bool landed = false;
+    CIP_TRY(info_landed(h, wait, &landed));
+    if (!landed) return 0;
     h->info_pending = false;
     // solves enqueued on the factorisation being resolved: if it is redone below, they ran on another factor -- repeat them
     const int spec = h->spec_solves;
@@ -882,47 +825,27 @@ static int factor_resolve(cip_handle *h, bool wait) {
         // checks below like any factorisation's.
         h->ws.unfused = 1;
         h->n_chain_fallbacks += 1;
-        int rc;
-        if ((rc = refactor_and_wait(h))) return rc;
+        CIP_TRY(refactor_and_wait(h));
         redone = true;
     }
-    if (h->info_host[3] != 0 || h->info_host[1] != 0) {
-        cip_set_error("LDL': in-launch wait of the panel chain gave up (%d)", h->info_host[3]);
-        h->factored = false;
-        return CIP_E_HIP;
-    }
+    CIP_TRY(chain_gave_up(h));
     int info = h->info_host[0];
     if (info == 0 || (h->reg_rel > 0.0 && h->info_host[2] == 0)) {
         // (regularised factor: a wrong-sign pivot -- |d| ~ delta, rounding decides its sign -- is harmless, the refinement in
         //  solve3x3 works against the true operator; a zero / non-finite one is not)
         h->pivots_verified = true;
-        if (redone && spec > 0) {
-            cip_set_error("LDL': %d solve(s) were enqueued on a factorisation whose panel chain gave up an in-launch wait; the handle has "
-                          "switched to the three-launch chain -- repeat them", spec);
-            return CIP_E_RETRY;
-        }
-        return 0;
+        return redone ? solves_to_repeat(spec, "whose panel chain gave up an in-launch wait; the handle has switched to the three-launch chain") : 0;
     }
     if (h->reg_rel > 0.0) {
         info = h->info_host[2];
     } else if (h->auto_reg) {
         h->reg_rel = cip_env_double("CIP_AUTO_REG", CIP_AUTO_REG);
         h->n_regularized += 1;
-        int rc;
-        if ((rc = refactor_and_wait(h))) return rc;
-        if (h->info_host[3] != 0 || h->info_host[1] != 0) {
-            cip_set_error("LDL': in-launch wait of the panel chain gave up (%d)", h->info_host[3]);
-            h->factored = false;
-            return CIP_E_HIP;
-        }
+        CIP_TRY(refactor_and_wait(h));
+        CIP_TRY(chain_gave_up(h));
         if (h->info_host[2] == 0) {
             h->pivots_verified = true;
-            if (spec > 0) {
-                cip_set_error("LDL': %d solve(s) were enqueued on a factorisation that met a bad pivot; the handle has switched "
-                              "to the regularised factorisation -- repeat them", spec);
-                return CIP_E_RETRY;
-            }
-            return 0;
+            return solves_to_repeat(spec, "that met a bad pivot; the handle has switched to the regularised factorisation");
         }
         info = h->info_host[2];
     }
@@ -935,21 +858,20 @@ static int factor_resolve(cip_handle *h, bool wait) {
 
 extern "C" int cip_factor(cip_handle *h) {
     if (!h) return CIP_E_INVALID;
-    int rc;
     if (h->timing) CIP_HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    if ((rc = factor_enqueue(h))) return rc;
+    CIP_TRY(factor_enqueue(h));
     h->flops_ldlt = (double)h->N * h->N * h->N / 3.0;
     h->factored = true;
     if (h->timing) {
         // (timed factorisations include the solve preparation that otherwise runs beside the first solve)
-        if ((rc = cip_ldlt_side_join(h->stream, h->ws, -1))) return rc;
+        CIP_TRY(cip_ldlt_side_join(h->stream, h->ws, -1));
         CIP_HIP_CHECK(hipEventRecord(h->ev2, h->stream));
         CIP_HIP_CHECK(hipEventSynchronize(h->ev2));
         float a = 0, b = 0;
         CIP_HIP_CHECK(hipEventElapsedTime(&a, h->ev0, h->ev1));
         CIP_HIP_CHECK(hipEventElapsedTime(&b, h->ev1, h->ev2));
         h->ms_assemble = a; h->ms_ldlt = b;
-        return factor_resolve(h, true);
+        return cip_factor_resolve(h, true);
     }
     return 0;
 }
@@ -970,437 +892,8 @@ extern "C" int cip_get_regularization(cip_handle *h, double *rel, int *times_swi
 extern "C" int cip_check_factor(cip_handle *h) {
     if (!h) return CIP_E_INVALID;
     if (!h->factored) { cip_set_error("no factorisation"); return CIP_E_NOTFACTORED; }
-    int rc;
-    if ((rc = factor_resolve(h, true))) return rc;
+    CIP_TRY(cip_factor_resolve(h, true));
     CIP_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// ------------------------------------------------------------------ products with A, A'
-static int mul_A(cip_handle *h, double alpha, const double *x, double beta, double *y) {      // y = alpha A x + beta y  (m)
-    if (h->m == 0) return 0;
-    if (h->A_sparse) return cip_spmv_csr(h->stream, h->m, h->A_rp, h->A_ci, h->A_v, alpha, x, beta, y);
-    return cip_gemv_t(h->stream, h->n, h->m, alpha, h->At, h->npad, x, beta, y);
-}
-static int mul_At(cip_handle *h, double alpha, const double *x, double beta, double *y) {     // y = alpha A' x + beta y (n)
-    if (h->m == 0) {                                                                          // y = beta y, as the G branch of cip_gemv_dev
-        if (beta == 0.0) return cip_zero(h->stream, h->n, y);
-        if (beta != 1.0) return cip_axpby(h->stream, h->n, 0.0, y, beta, y);
-        return 0;
-    }
-    if (h->A_sparse) return cip_spmv_csr(h->stream, h->n, h->T_rp, h->T_ci, h->T_v, alpha, x, beta, y);
-    return cip_gemv_t(h->stream, h->m, h->n, alpha, h->A, h->m, x, beta, y);
-}
-
-// (F'F)^-1 z = F^-1 F^-T z
-static int apply_FtF_inv(cip_handle *h, const double *z, double *tmp, double *out) {
-    int rc;
-    if ((rc = cip_cones_apply(h->stream, h->cs, CIP_OP_FINVT, z, tmp))) return rc;
-    return cip_cones_apply(h->stream, h->cs, CIP_OP_FINV, tmp, out);
-}
-
-// ------------------------------------------------------------------ level 3
-// z == NULL (Schur route only): the 2x2 form [S G'; G 0][a; b] = [x; y] (src/kktsolvers.jl:297-302), c is not written
-static int solve3x3_once(cip_handle *h, const double *x, const double *y, const double *z, double *a, double *b, double *c) {
-    hipStream_t s = h->stream;
-    const int n = h->n, p = h->p;
-    const int m = z ? h->m : 0;
-    int rc;
-    if (h->route == CIP_ROUTE_SCHUR) {
-        // algebra of pivotgen, src/kktsolvers.jl:324-330, with the exact (F'F)^-1 = F^-1 F^-T:
-        //   t = (F'F)^-1 z ; [S G'; G 0][a; b] = [x + A't; y] ; c = t - (F'F)^-1 A a
-        double *t = h->mt1, *tmp = h->mt2, *u = h->mt3;
-        if (m > 0 && (rc = apply_FtF_inv(h, z, tmp, t))) return rc;
-        { int rcc = cip_copy(s, n, x, h->rhs); if (rcc) return rcc; }
-        if (m > 0 && (rc = mul_At(h, 1.0, t, 1.0, h->rhs))) return rc;
-        if (p > 0) { int rcc = cip_copy(s, p, y, h->rhs + n); if (rcc) return rcc; }
-        if (h->Npad > h->N) { int rcc = cip_zero(s, (h->Npad - h->N), h->rhs + h->N); if (rcc) return rcc; }
-        if ((rc = graph_run(h, &h->gx_solve, [&]() { return cip_ldlt_solve(s, h->K, h->Npad, h->ldk, h->ws, h->rhs); }))) return rc;
-        { int rcc = cip_copy(s, n, h->rhs, a); if (rcc) return rcc; }
-        if (p > 0) { int rcc = cip_copy(s, p, h->rhs + n, b); if (rcc) return rcc; }
-        if (m > 0) {
-            if ((rc = mul_A(h, 1.0, h->rhs, 0.0, u))) return rc;
-            if ((rc = apply_FtF_inv(h, u, tmp, u))) return rc;
-            if ((rc = cip_axpby(s, m, 1.0, t, 0.0, c))) return rc;
-            if ((rc = cip_axpby(s, m, -1.0, u, 1.0, c))) return rc;
-        }
-    } else {
-        // [-F'F -A 0; -A' Q G'; 0 G 0] [c; a; b] = [-z; x; y]
-        if (m > 0 && (rc = cip_axpby(s, m, -1.0, z, 0.0, h->rhs))) return rc;
-        { int rcc = cip_copy(s, n, x, h->rhs + m); if (rcc) return rcc; }
-        if (p > 0) { int rcc = cip_copy(s, p, y, h->rhs + m + n); if (rcc) return rcc; }
-        if (h->Npad > h->N) { int rcc = cip_zero(s, (h->Npad - h->N), h->rhs + h->N); if (rcc) return rcc; }
-        if ((rc = graph_run(h, &h->gx_solve, [&]() { return cip_ldlt_solve(s, h->K, h->Npad, h->ldk, h->ws, h->rhs); }))) return rc;
-        if (m > 0) { int rcc = cip_copy(s, m, h->rhs, c); if (rcc) return rcc; }
-        { int rcc = cip_copy(s, n, h->rhs + m, a); if (rcc) return rcc; }
-        if (p > 0) { int rcc = cip_copy(s, p, h->rhs + m + n, b); if (rcc) return rcc; }
-    }
-    return 0;
-}
-
-// r = (x, y, z) - K3 (a, b, c) with the TRUE (unregularised) operator:
-//   rx = x - (Q a + G' b - A' c) ;  ry = y - G a ;  rz = z - (A a + F'F c)
-static int kkt3_residual(cip_handle *h, const double *x, const double *y, const double *z, const double *a, const double *b,
-                         const double *c, double *rx, double *ry, double *rz) {
-    hipStream_t s = h->stream;
-    const int n = h->n, m = h->m, p = h->p;
-    int rc;
-    if ((rc = cip_axpby(s, n, 1.0, x, 0.0, rx))) return rc;
-    if ((rc = cip_mul_Q(h, -1.0, a, 1.0, rx, false))) return rc;
-    if (p > 0) {
-        if ((rc = cip_gemv_t(s, p, n, -1.0, h->G, p, b, 1.0, rx))) return rc;
-        if ((rc = cip_axpby(s, p, 1.0, y, 0.0, ry))) return rc;
-        if ((rc = cip_gemv_t(s, n, p, -1.0, h->Gt, n, a, 1.0, ry))) return rc;
-    }
-    if (m > 0) {
-        if ((rc = mul_At(h, 1.0, c, 1.0, rx))) return rc;
-        if ((rc = cip_axpby(s, m, 1.0, z, 0.0, rz))) return rc;
-        if ((rc = mul_A(h, -1.0, a, 1.0, rz))) return rc;
-        if ((rc = cip_cones_apply(s, h->cs, CIP_OP_F, c, h->mt2))) return rc;
-        if ((rc = cip_cones_apply(s, h->cs, CIP_OP_FT, h->mt2, h->mt2))) return rc;
-        if ((rc = cip_axpby(s, m, -1.0, h->mt2, 1.0, rz))) return rc;
-    }
-    return 0;
-}
-
-extern "C" int cip_solve3x3_dev(cip_handle *h, const double *x, const double *y, const double *z, double *a, double *b,
-                                double *c) {
-    if (!h) return CIP_E_INVALID;
-    if (!h->factored) { cip_set_error("cip_solve3x3: no factorisation (call cip_factor first)"); return CIP_E_NOTFACTORED; }
-    const int n = h->n, m = h->m, p = h->p;
-    int rc;
-    CipRange rg("cip:solve3x3");
-    // speculative (no host wait, the flag is resolved only if its read-back has landed) once a factorisation of this handle
-    // has been verified; before that the solve waits for the flag
-    if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
-    if (h->info_pending) h->spec_solves += 1;
-    h->n_solve += 1;
-    // which problems of the call sit on a regularised factor: the handle's own state for one problem, the group's mask in a batch
-    const bool batch = cip_in_batch();
-    const unsigned long long mask0 = cip_tl_bz.mask;
-    unsigned long long live = batch ? (mask0 & cip_tl_bz.reg_mask) : (h->reg_rel > 0.0 ? 1ull : 0ull);
-    if (!live) return solve3x3_once(h, x, y, z, a, b, c);
-    // Regularised factor: iterative refinement against the true operator (the factor is of K + E, |E_ii| = reg_rel
-    // times the row's largest entry): a few steps bring the residual to rounding level while ||K^-1 E|| < 1.
-    // In a batch the first solve runs for every problem of the mask, from the private copy of the right-hand side (copies are
-    // exact: the others get the bits of solve3x3_once on the original); the refinement then runs under the mask of the regularised
-    // problems, each leaving it when ITS residual has converged, stagnates or is not finite -- every problem sees the launches it
-    // sees alone.
-    hipStream_t s = h->stream;
-    if (!h->ref) {
-        if (batch) { cip_set_error("cip_solve3x3: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
-        if ((rc = alloc_refine_buffers(h))) return rc;
-    }
-    RefView v;
-    ref_layout(h->ref, h, &v);
-    double *xs = v.rhs.x, *ys = v.rhs.y, *zs = v.rhs.z;           // private copy of the right-hand side (z may alias c)
-    double *rx = v.res.x, *ry = v.res.y, *rz = v.res.z, *da = v.cor.x, *db = v.cor.y, *dc = v.cor.z;
-    { int rcc = cip_copy(s, n, x, xs); if (rcc) return rcc; }
-    if (p > 0) { int rcc = cip_copy(s, p, y, ys); if (rcc) return rcc; }
-    if (m > 0) { int rcc = cip_copy(s, m, z, zs); if (rcc) return rcc; }
-    if ((rc = solve3x3_once(h, xs, ys, zs, a, b, c))) return rc;
-    struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
-    const int B = batch ? cip_tl_bz.B : 1;
-    double prev[CIP_BATCH_MAX], d6[6 * CIP_BATCH_MAX];
-    for (int q = 0; q < B; ++q) prev[q] = __builtin_inf();
-    for (int it = 0; it < 6 && live; ++it) {
-        if (batch) cip_tl_bz.mask = live;
-        if ((rc = kkt3_residual(h, xs, ys, zs, a, b, c, rx, ry, rz))) return rc;
-        const double *px[6] = {rx, ry, rz, xs, ys, zs};
-        const int ln[6] = {n, p, m, n, p, m};
-        if ((rc = cip_dots(s, 6, px, px, ln, h->dot_scratch, d6))) return rc;       // (a batch: B x 6, problem-major)
-        for (int q = 0; q < B; ++q) {
-            if (!((live >> q) & 1ull)) continue;
-            const double *dq = d6 + 6 * q;
-            const double rn = sqrt(dq[0] + dq[1] + dq[2]), bn = sqrt(dq[3] + dq[4] + dq[5]);
-            if (!(rn > 1e-14 * bn) || !(rn < prev[q])) live &= ~(1ull << q);         // converged, stagnating, or not finite
-            prev[q] = rn;
-        }
-        if (!live) break;
-        if (batch) cip_tl_bz.mask = live;
-        if ((rc = solve3x3_once(h, rx, ry, rz, da, db, dc))) return rc;
-        if ((rc = cip_axpby(s, n, 1.0, da, 1.0, a))) return rc;
-        if (p > 0 && (rc = cip_axpby(s, p, 1.0, db, 1.0, b))) return rc;
-        if (m > 0 && (rc = cip_axpby(s, m, 1.0, dc, 1.0, c))) return rc;
-    }
-    return 0;
-}
-extern "C" int cip_solve3x3(cip_handle *h, const double *x, const double *y, const double *z, double *a, double *b,
-                            double *c) {
-    if (!h) return CIP_E_INVALID;
-    hipStream_t s = h->stream;
-    const int n = h->n, m = h->m, p = h->p;
-    StageView v;
-    stage_layout(h->stage, h, 1, 1, &v);
-    CIP_HIP_CHECK(hipMemcpyAsync(v.in.x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(v.in.y, y, sizeof(double) * p, hipMemcpyHostToDevice, s));
-    if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(v.in.z, z, sizeof(double) * m, hipMemcpyHostToDevice, s));
-    int rc;
-    if (h->factored && (rc = factor_resolve(h, true))) return rc;      // this entry point is synchronous anyway
-    if ((rc = cip_solve3x3_dev(h, v.in.x, v.in.y, v.in.z, v.out.x, v.out.y, v.out.z))) return rc;
-    CIP_HIP_CHECK(hipMemcpyAsync(a, v.out.x, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(b, v.out.y, sizeof(double) * p, hipMemcpyDeviceToHost, s));
-    if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(c, v.out.z, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-// The 2x2 form of the plugin (src/ConicIP.jl:450-466; what `pivot` wraps, src/kktsolvers.jl:297-302, :316-349):
-//   [Q + A'(F'F)^-1 A   G'] [dy]   [y]
-//   [G                  0 ] [dw] = [w]      on the factor of the Schur route.
-extern "C" int cip_solve2x2_dev(cip_handle *h, const double *y, const double *w, double *dy, double *dw) {
-    if (!h) return CIP_E_INVALID;
-    if (h->route != CIP_ROUTE_SCHUR) { cip_set_error("cip_solve2x2: needs the Schur route"); return CIP_E_UNSUPPORTED; }
-    if (!h->factored) { cip_set_error("cip_solve2x2: no factorisation (call cip_factor first)"); return CIP_E_NOTFACTORED; }
-    int rc;
-    if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
-    const bool batch = cip_in_batch();
-    const unsigned long long mask0 = cip_tl_bz.mask;
-    const unsigned long long regd = batch ? (mask0 & cip_tl_bz.reg_mask) : (h->reg_rel > 0.0 ? 1ull : 0ull);
-    if (regd && h->m > 0) {
-        // regularised factor: go through the refined 3x3 solve with z = 0 (its first two components are the 2x2 solution); in a batch
-        // only the regularised problems of the mask do, the others take the 2x2 form below under theirs
-        struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
-        if (batch) cip_tl_bz.mask = regd;
-        { int rcc = cip_zero(h->stream, h->m, h->mt1); if (rcc) return rcc; }
-        if (!h->c2x2) {
-            if (batch) { cip_set_error("cip_solve2x2: regularised problems in a batch whose handles have no refinement buffers"); return CIP_E_INVALID; }
-            if ((rc = alloc_refine_buffers(h))) return rc;
-        }
-        if ((rc = cip_solve3x3_dev(h, y, w, h->mt1, dy, dw, h->c2x2))) return rc;
-        if (!batch || regd == mask0) return 0;
-        cip_tl_bz.mask = mask0 & ~regd;
-        return solve3x3_once(h, y, w, nullptr, dy, dw, nullptr);
-    }
-    if (h->info_pending) h->spec_solves += 1;
-    h->n_solve += 1;
-    return solve3x3_once(h, y, w, nullptr, dy, dw, nullptr);
-}
-extern "C" int cip_solve2x2(cip_handle *h, const double *y, const double *w, double *dy, double *dw) {
-    if (!h) return CIP_E_INVALID;
-    hipStream_t s = h->stream;
-    const int n = h->n, p = h->p;
-    StageView v;
-    stage_layout(h->stage, h, 1, 1, &v);
-    CIP_HIP_CHECK(hipMemcpyAsync(v.in.x, y, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(v.in.y, w, sizeof(double) * p, hipMemcpyHostToDevice, s));
-    int rc;
-    if (h->factored && (rc = factor_resolve(h, true))) return rc;
-    if ((rc = cip_solve2x2_dev(h, v.in.x, v.in.y, v.out.x, v.out.y))) return rc;
-    CIP_HIP_CHECK(hipMemcpyAsync(dy, v.out.x, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(dw, v.out.y, sizeof(double) * p, hipMemcpyDeviceToHost, s));
-    CIP_HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-// ------------------------------------------------------------------ many right-hand sides (level 3)
-// X n x nrhs, Y p x nrhs, Z m x nrhs (col-major, ld = rows); the same as nrhs calls of the single entry point, 64 columns at a time:
-// the cone operations and the CSR products per column, the dense A / A' products and the LDL' sweeps over all columns of a chunk
-// (solve_many.hip).  Regularised factor: nrhs refined single solves.
-// kc <= 64 columns of solve3x3_once (z == NULL: the 2x2 form of the Schur route); c may alias z
-static int solve3x3_chunk(cip_handle *h, int kc, const double *x, const double *y, const double *z, double *a, double *b, double *c) {
-    hipStream_t s = h->stream;
-    const int n = h->n, p = h->p, N = h->N, Npad = h->Npad;
-    const int m = z ? h->m : 0;
-    const long ldr = Npad;
-    ManyView v;
-    many_layout(h->many, h, &v);
-    double *R = v.R, *T = v.T, *U = v.U, *S = v.S;
-    int rc;
-    if (h->route == CIP_ROUTE_SCHUR) {
-        // t = (F'F)^-1 z ; [S G'; G 0][a; b] = [x + A't; y] ; c = t - (F'F)^-1 A a
-        for (int j = 0; j < kc && m > 0; ++j)
-            if ((rc = apply_FtF_inv(h, z + (long)j * m, h->mt2, T + (long)j * m))) return rc;
-        if ((rc = cip_block_copy(s, n, kc, 1.0, x, n, nullptr, R, ldr))) return rc;
-        if (m > 0) {
-            if (h->A_sparse) {
-                for (int j = 0; j < kc; ++j)
-                    if ((rc = cip_spmv_csr(s, n, h->T_rp, h->T_ci, h->T_v, 1.0, T + (long)j * m, 1.0, R + j * ldr))) return rc;
-            } else if ((rc = cip_gemm_tn(s, n, kc, m, 1.0, h->A, m, T, m, 1.0, R, ldr))) {
-                return rc;
-            }
-        }
-        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, y, p, nullptr, R + n, ldr))) return rc;
-        if (Npad > N && (rc = cip_block_copy(s, Npad - N, kc, 0.0, nullptr, 0, nullptr, R + N, ldr))) return rc;
-        if ((rc = cip_ldlt_solve_many(s, h->K, Npad, h->ldk, h->ws, S, R, ldr, kc, false))) return rc;
-        if ((rc = cip_block_copy(s, n, kc, 1.0, R, ldr, nullptr, a, n))) return rc;
-        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, R + n, ldr, nullptr, b, p))) return rc;
-        if (m > 0) {
-            if (h->A_sparse) {
-                for (int j = 0; j < kc; ++j)
-                    if ((rc = cip_spmv_csr(s, m, h->A_rp, h->A_ci, h->A_v, 1.0, R + j * ldr, 0.0, U + (long)j * m))) return rc;
-            } else if ((rc = cip_gemm_tn(s, m, kc, n, 1.0, h->At, h->npad, R, ldr, 0.0, U, m))) {
-                return rc;
-            }
-            for (int j = 0; j < kc; ++j)
-                if ((rc = apply_FtF_inv(h, U + (long)j * m, h->mt2, U + (long)j * m))) return rc;
-            if ((rc = cip_axpby(s, m * kc, 1.0, T, 0.0, c))) return rc;
-            if ((rc = cip_axpby(s, m * kc, -1.0, U, 1.0, c))) return rc;
-        }
-    } else {
-        // [-F'F -A 0; -A' Q G'; 0 G 0] [c; a; b] = [-z; x; y]
-        if (m > 0 && (rc = cip_block_copy(s, m, kc, -1.0, z, m, nullptr, R, ldr))) return rc;
-        if ((rc = cip_block_copy(s, n, kc, 1.0, x, n, nullptr, R + m, ldr))) return rc;
-        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, y, p, nullptr, R + m + n, ldr))) return rc;
-        if (Npad > N && (rc = cip_block_copy(s, Npad - N, kc, 0.0, nullptr, 0, nullptr, R + N, ldr))) return rc;
-        if ((rc = cip_ldlt_solve_many(s, h->K, Npad, h->ldk, h->ws, S, R, ldr, kc, false))) return rc;
-        if (m > 0 && (rc = cip_block_copy(s, m, kc, 1.0, R, ldr, nullptr, c, m))) return rc;
-        if ((rc = cip_block_copy(s, n, kc, 1.0, R + m, ldr, nullptr, a, n))) return rc;
-        if (p > 0 && (rc = cip_block_copy(s, p, kc, 1.0, R + m + n, ldr, nullptr, b, p))) return rc;
-    }
-    return 0;
-}
-// two2: the 2x2 form (y, w -> dy, dw; z, c unused).  one_is_single: nrhs == 1 is the single entry point (its bits)
-static int solve_many_impl(cip_handle *h, bool two2, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
-                           double *C, bool one_is_single) {
-    const int n = h->n, m = h->m, p = h->p;
-    if (nrhs == 1 && one_is_single) return two2 ? cip_solve2x2_dev(h, X, Y, A, Bo) : cip_solve3x3_dev(h, X, Y, Z, A, Bo, C);
-    const char *who = two2 ? "cip_solve2x2_many" : "cip_solve3x3_many";
-    if (!h->factored) { cip_set_error("%s: no factorisation (call cip_factor first)", who); return CIP_E_NOTFACTORED; }
-    int rc;
-    if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
-    if (h->reg_rel > 0.0 && (!two2 || m > 0)) {
-        // regularised factor: the refinement against the true operator runs per column, through the single path
-        for (int j = 0; j < nrhs; ++j) {
-            rc = two2 ? cip_solve2x2_dev(h, X + (long)j * n, Y + (long)j * p, A + (long)j * n, Bo + (long)j * p)
-                      : cip_solve3x3_dev(h, X + (long)j * n, Y + (long)j * p, Z + (long)j * m, A + (long)j * n, Bo + (long)j * p,
-                                         C + (long)j * m);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    if (h->info_pending) h->spec_solves += nrhs;
-    h->n_solve += nrhs;
-    if (!h->many) { ManyView v; DMALLOC(h->many, many_layout(nullptr, h, &v)); }
-    CipRange rg(two2 ? "cip:solve2x2_many" : "cip:solve3x3_many");
-    for (int c0 = 0; c0 < nrhs; c0 += CIP_MANY_CHUNK) {
-        const int kc = nrhs - c0 < CIP_MANY_CHUNK ? nrhs - c0 : CIP_MANY_CHUNK;
-        if ((rc = solve3x3_chunk(h, kc, X + (long)c0 * n, Y + (long)c0 * p, two2 ? nullptr : Z + (long)c0 * m, A + (long)c0 * n,
-                                 Bo + (long)c0 * p, two2 ? nullptr : C + (long)c0 * m)))
-            return rc;
-    }
-    return 0;
-}
-static bool many_args_ok(const cip_handle *h, bool two2, int nrhs, const void *X, const void *Y, const void *Z, const void *A,
-                         const void *Bo, const void *C) {
-    if (!h || nrhs < 0) return false;
-    if (nrhs == 0) return true;
-    return X && A && (h->p == 0 || (Y && Bo)) && (two2 || h->m == 0 || (Z && C));
-}
-// host staging of the host-pointer calls: chunk by chunk through h->many_stage (2 x (n + p + m) x 64 doubles)
-static int solve_many_host(cip_handle *h, bool two2, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
-                           double *C) {
-    hipStream_t s = h->stream;
-    const int n = h->n, p = h->p, m = two2 ? 0 : h->m;
-    StageView v;
-    if (!h->many_stage) DMALLOC(h->many_stage, stage_layout(nullptr, h, CIP_MANY_CHUNK, CIP_MANY_CHUNK, &v));
-    for (int c0 = 0; c0 < nrhs; c0 += CIP_MANY_CHUNK) {
-        const int kc = nrhs - c0 < CIP_MANY_CHUNK ? nrhs - c0 : CIP_MANY_CHUNK;
-        stage_layout(h->many_stage, h, kc, CIP_MANY_CHUNK, &v);
-        double *xi = v.in.x, *yi = v.in.y, *zi = v.in.z, *ao = v.out.x, *bo = v.out.y, *co = v.out.z;
-        CIP_HIP_CHECK(hipMemcpyAsync(xi, X + (size_t)c0 * n, sizeof(double) * n * kc, hipMemcpyHostToDevice, s));
-        if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(yi, Y + (size_t)c0 * p, sizeof(double) * p * kc, hipMemcpyHostToDevice, s));
-        if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(zi, Z + (size_t)c0 * m, sizeof(double) * m * kc, hipMemcpyHostToDevice, s));
-        int rc;
-        if (h->factored && (rc = factor_resolve(h, true))) return rc;      // this entry point is synchronous anyway
-        if ((rc = solve_many_impl(h, two2, kc, xi, yi, zi, ao, bo, co, nrhs == 1))) return rc;
-        CIP_HIP_CHECK(hipMemcpyAsync(A + (size_t)c0 * n, ao, sizeof(double) * n * kc, hipMemcpyDeviceToHost, s));
-        if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync(Bo + (size_t)c0 * p, bo, sizeof(double) * p * kc, hipMemcpyDeviceToHost, s));
-        if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync(C + (size_t)c0 * m, co, sizeof(double) * m * kc, hipMemcpyDeviceToHost, s));
-        CIP_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-extern "C" int cip_solve3x3_many_dev(cip_handle *h, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
-                                     double *C) {
-    if (!many_args_ok(h, false, nrhs, X, Y, Z, A, Bo, C)) { cip_set_error("cip_solve3x3_many_dev: bad argument"); return CIP_E_INVALID; }
-    if (nrhs == 0) return 0;
-    return solve_many_impl(h, false, nrhs, X, Y, Z, A, Bo, C, true);
-}
-extern "C" int cip_solve3x3_many(cip_handle *h, int nrhs, const double *X, const double *Y, const double *Z, double *A, double *Bo,
-                                 double *C) {
-    if (!many_args_ok(h, false, nrhs, X, Y, Z, A, Bo, C)) { cip_set_error("cip_solve3x3_many: bad argument"); return CIP_E_INVALID; }
-    if (nrhs == 0) return 0;
-    return solve_many_host(h, false, nrhs, X, Y, Z, A, Bo, C);
-}
-extern "C" int cip_solve2x2_many_dev(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW) {
-    if (!many_args_ok(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr)) { cip_set_error("cip_solve2x2_many_dev: bad argument"); return CIP_E_INVALID; }
-    if (nrhs == 0) return 0;
-    if (h->route != CIP_ROUTE_SCHUR) { cip_set_error("cip_solve2x2_many: needs the Schur route"); return CIP_E_UNSUPPORTED; }
-    return solve_many_impl(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr, true);
-}
-extern "C" int cip_solve2x2_many(cip_handle *h, int nrhs, const double *Y, const double *W, double *DY, double *DW) {
-    if (!many_args_ok(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr)) { cip_set_error("cip_solve2x2_many: bad argument"); return CIP_E_INVALID; }
-    if (nrhs == 0) return 0;
-    if (h->route != CIP_ROUTE_SCHUR) { cip_set_error("cip_solve2x2_many: needs the Schur route"); return CIP_E_UNSUPPORTED; }
-    return solve_many_host(h, true, nrhs, Y, W, nullptr, DY, DW, nullptr);
-}
-
-// diag F (the packed scaling) when the cone set is R cones only -- the native loops then fuse the cone operations of their
-// element-wise chains into the vector kernels (vecops.hip: k_loop_*); NULL otherwise
-const double *cip_loop_all_r(cip_handle *h) {
-    if (h->m <= 0) return nullptr;
-    for (int q = 0; q < h->cs.ncones; ++q) if (h->h_cones[q].type != CIP_CONE_R) return nullptr;
-    return h->cs.d_scal;
-}
-// solve4x4 (src/ConicIP.jl:684-692):  q = r.s (./) lambda ; t1 = F'q ; (dy,dw,dv) = solve3x3(r.y, r.w, r.v + t1) ;
-// ds = t1 - F'(F dv).   r, dz are contiguous (y[n], w[p], v[m], s[m]).
-extern "C" int cip_solve4x4_dev(cip_handle *h, const double *lambda, const double *r, double *dz) {
-    if (!h) return CIP_E_INVALID;
-    hipStream_t s = h->stream;
-    const int n = h->n, m = h->m, p = h->p;
-    const double *ry = r, *rw = r + n, *rv = r + n + p, *rs = r + n + p + m;
-    double *dy = dz, *dw = dz + n, *dv = dz + n + p, *ds = dz + n + p + m;
-    int rc;
-    if (h->all_r < 0) {
-        h->all_r = m > 0 ? 1 : 0;
-        for (int q = 0; q < h->cs.ncones; ++q) if (h->cs.h_cones[q].type != CIP_CONE_R) h->all_r = 0;
-        if (cip_env_int("CIP_S4_FUSED", 1) == 0) h->all_r = 0;
-    }
-    // the fused kernels read r across threads (CSR gathers) while writing dz: an in-place call (dz overlapping r) takes the
-    // element-wise generic path, which tolerates it
-    const size_t len4 = (size_t)n + p + 2 * (size_t)m;
-    const bool aliased = dz < r + len4 && r < dz + len4;
-    // a lock-step group with regularised problems (lockstep.hip): they take the generic path below with its refined solve, as they do
-    // alone; the others of the mask take the fused path first, under their own mask
-    const unsigned long long mask0 = cip_tl_bz.mask;
-    const unsigned long long regd = cip_in_batch() ? (mask0 & cip_tl_bz.reg_mask) : 0ull;
-    struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
-    if (h->all_r && !aliased && h->route == CIP_ROUTE_SCHUR && h->reg_rel <= 0.0 && regd != mask0) {
-        cip_tl_bz.mask = mask0 & ~regd;
-        // all cones R (F = diag(f), f = the packed scaling): the element-wise launches around the sweeps fused into one kernel
-        // in front and one behind them (vecops.hip: k_s4_pre_r / k_s4_post_r), the same operations on every element
-        if (!h->factored) { cip_set_error("cip_solve4x4: no factorisation (call cip_factor first)"); return CIP_E_NOTFACTORED; }
-        CipRange rg("cip:solve3x3");
-        if ((rc = factor_resolve(h, !h->pivots_verified))) return rc;
-        if (h->reg_rel <= 0.0) {                       // (the resolve may have switched the handle to the regularised factorisation)
-            if (h->info_pending) h->spec_solves += 1;
-            h->n_solve += 1;
-            const double *f = h->cs.d_scal;
-            double *t = h->mt1, *u = h->mt3;
-            if ((rc = cip_s4_pre_r(s, m, n, p, h->Npad, f, rs, lambda, rv, ry, rw, ds, t, h->rhs, h->A_sparse ? h->T_rp : nullptr, h->T_ci, h->T_v))) return rc;
-            if (!h->A_sparse && (rc = mul_At(h, 1.0, t, 1.0, h->rhs))) return rc;
-            if ((rc = graph_run(h, &h->gx_solve, [&]() { return cip_ldlt_solve(s, h->K, h->Npad, h->ldk, h->ws, h->rhs); }))) return rc;
-            if (!h->A_sparse && (rc = mul_A(h, 1.0, h->rhs, 0.0, u))) return rc;
-            if ((rc = cip_s4_post_r(s, m, n, p, f, t, h->rhs, h->A_sparse ? nullptr : u, h->A_sparse ? h->A_rp : nullptr, h->A_ci, h->A_v, dy, dw, dv, ds))) return rc;
-            if (!regd) return 0;
-            cip_tl_bz.mask = regd;
-        }
-    }
-    // ds is used as t1; dv temporarily holds r.v + t1 (input z of the 3x3 solve; solve3x3 copies it before writing c)
-    if (m > 0) {
-        if ((rc = cip_cones_div(s, h->cs, rs, lambda, ds))) return rc;          // q
-        if ((rc = cip_cones_apply(s, h->cs, CIP_OP_FT, ds, ds))) return rc;     // t1 = F'q (in place)
-        if ((rc = cip_axpby(s, m, 1.0, rv, 0.0, dv))) return rc;
-        if ((rc = cip_axpby(s, m, 1.0, ds, 1.0, dv))) return rc;                // dv <- r.v + t1
-    }
-    if ((rc = cip_solve3x3_dev(h, ry, rw, dv, dy, dw, dv))) return rc;
-    if (m > 0) {
-        double *u = h->mt3;
-        if ((rc = cip_cones_apply(s, h->cs, CIP_OP_F, dv, u))) return rc;
-        if ((rc = cip_cones_apply(s, h->cs, CIP_OP_FT, u, u))) return rc;
-        if ((rc = cip_axpby(s, m, -1.0, u, 1.0, ds))) return rc;                // ds = t1 - F'(F dv)
-    }
     return 0;
 }
 
@@ -1436,11 +929,11 @@ extern "C" int cip_gemv_dev(cip_handle *h, int which, int trans, double alpha, c
     hipStream_t s = h->stream;
     switch (which) {
         case CIP_MAT_Q: return cip_mul_Q(h, alpha, x, beta, y);                             // Q symmetric
-        case CIP_MAT_A: return trans ? mul_At(h, alpha, x, beta, y) : mul_A(h, alpha, x, beta, y);
+        case CIP_MAT_A: return trans ? cip_mul_At(h, alpha, x, beta, y) : cip_mul_A(h, alpha, x, beta, y);
         case CIP_MAT_G:
             if (h->p == 0) {
-                if (trans && beta == 0.0) { int rcc = cip_zero(s, h->n, y); if (rcc) return rcc; }
-                else if (trans && beta != 1.0) return cip_axpby(s, h->n, 0.0, y, beta, y);
+                if (trans && beta == 0.0) return cip_zero(s, h->n, y);
+                if (trans && beta != 1.0) return cip_axpby(s, h->n, 0.0, y, beta, y);
                 return 0;
             }
             return trans ? cip_gemv_t(s, h->p, h->n, alpha, h->G, h->p, x, beta, y)
@@ -1475,8 +968,7 @@ extern "C" int cip_ldlt_factor_dev(void *stream, double *K, int N, int ld, void 
     }
     LdltWorkspace ws{};
     cip_ldlt_ws_carve(workspace, N, &ws, cip_ldlt_fused_for(N));      // (the workspace has room for either mode: cip_ldlt_workspace_bytes)
-    int rc = cip_ldlt_factor((hipStream_t)stream, K, N, ld, ws);
-    if (rc) return rc;
+    CIP_TRY(cip_ldlt_factor((hipStream_t)stream, K, N, ld, ws));
     // all four flag words: [3] != 0 -- an in-launch wait of the fused chain gave up and K holds a partial factor
     int flags[4] = {0, 0, 0, 0};
     CIP_HIP_CHECK(hipMemcpyAsync(flags, ws.info, sizeof(flags), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -1538,7 +1030,7 @@ extern "C" int cip_kkt_order(const cip_handle *h, int *N, int *N_padded) {
 }
 extern "C" int cip_get_kkt_matrix(cip_handle *h, double *K_host) {
     if (!h || !K_host) return CIP_E_INVALID;
-    { const int rj = cip_ldlt_side_join(h->stream, h->ws, -1); if (rj) return rj; }
+    CIP_TRY(cip_ldlt_side_join(h->stream, h->ws, -1));
     CIP_HIP_CHECK(hipStreamSynchronize(h->stream));
     CIP_HIP_CHECK(hipMemcpy(K_host, h->K, sizeof(double) * (size_t)h->ldk * h->Npad, hipMemcpyDeviceToHost));
     return 0;

@@ -366,7 +366,7 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
     } else {
         const int lazy_now = g_lazy_copy.load(std::memory_order_relaxed);
         const int lazy_on = lazy_now < 0 ? cip_lazy_copy_set(-1) : lazy_now;
-        bool all_r = h->m > 0 && h->nq == 0 && !h->cs.has_S;
+        bool all_r = cip_all_r(h);
         const int nb0 = cip_ldlt_outer_block_for(h->Npad);
         if (!h->Q_sparse && lazy_on && lazy_ok && all_r && cip_grp_A_one_per_row(h) && p == 0 && h->Npad == n && n > nb0 && h->reg_rel <= 0.0 && h->kdiag &&
             copy_lower_vectorisable(h->K, h->ldk, 0, h->Q, (long)n, n)) {

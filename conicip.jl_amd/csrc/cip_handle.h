@@ -30,7 +30,7 @@ struct cip_handle {
     bool A_sparse = false;
     bool A_one_per_row = false;     // CSR A with at most one entry per row (A = I, bound constraints): A'(F'F)^-1 A is diagonal for R cones
     double *kdiag = nullptr;        // n doubles: the Schur route's diagonal of K beyond the first outer block when the copy of Q is lazy
-    int all_r = -1;                 // every cone is an R cone (F diagonal): solve4x4 takes the fused element-wise path; -1: not looked at yet
+    int s4_fused = -1;              // solve4x4 takes the fused element-wise path (cip_all_r and CIP_S4_FUSED); -1: not looked at yet
     double *A = nullptr;            // m x n, ld m            (dense A only)
     double *At = nullptr;           // npad x mpad, ld npad   (dense A only; zero padded)  At[i + r*npad] = A[r,i]
     int A_nnz = 0;
@@ -69,7 +69,7 @@ struct cip_handle {
     int n_chain_fallbacks = 0;     // factorisations redone with the three-launch chain after an in-launch wait of the fused one gave up
     int x_zeroed = 0;               // block-inverse storage zero-initialised
     // pivot flag of the last factorisation: read back asynchronously into pinned host memory, resolved lazily
-    // (api.hip: factor_resolve) so that cip_factor never waits for the GPU
+    // (api.hip: cip_factor_resolve) so that cip_factor never waits for the GPU
     int *info_host = nullptr;
     int info_seq = 0;                 // sequence number of the last factorisation's flag read-back (info_host[4] == info_seq: landed)
     bool info_pending = false;
@@ -86,7 +86,7 @@ struct cip_handle {
     double *nt1 = nullptr;          // n-vector
     double *pt1 = nullptr;          // p-vector
     double *dot_scratch = nullptr;
-    double *stage = nullptr;        // device staging for the host-pointer entry points: 2*(n+p+m) doubles
+    double *stage = nullptr;        // device staging for the host-pointer entry points (StageView, one column)
     double *ref = nullptr;          // right-hand side / residual / correction of the refinement inside solve3x3 (regularised factor only)
     double *c2x2 = nullptr;         // m-vector: discarded third component of a regularised 2x2 solve
     // many right-hand sides (cip_solve3x3_many*), allocated on first use, sized for chunks of 64 columns: the Npad x 64 right-hand
@@ -94,7 +94,7 @@ struct cip_handle {
     double *many = nullptr, *many_stage = nullptr;
     double *drv = nullptr;          // vectors of the native interior-point loop (cip_conicip), allocated on first use
 
-    // ---- hipGraphs of the two launch-bound inner loops of small systems (opt-in, CIP_GRAPH=1; api.hip: graph_run)
+    // ---- hipGraphs of the two launch-bound inner loops of small systems (opt-in, CIP_GRAPH=1; graph_run below)
     hipGraphExec_t gx_factor = nullptr, gx_solve = nullptr;
     // what the recorded factorisation baked in besides the handle's fixed pointers: where the first trailing update reads
     // its C operand (ws.lazyC: Q while the copy is lazy, else null).  A replay under another state would read stale data
@@ -116,13 +116,16 @@ int cip_assemble(cip_handle *h, bool lazy_ok = false);     // assemble.hip; lazy
 // Relative size of the automatic regularisation.  Miles problem 3 under the reference's 10 scalings (test/runtests.jl:
 // 618-637), iterations to :Optimal (oracle: 15 16 16 15 21 29 30 | 20 29 32): 1e-9 -> one false :Unbounded; 1e-11 -> 11 16 16
 // 15 21 26 24 | 20 28 27; 1e-13 -> 16 16 16 15 21 29 29 | 21 29 32.  The refinement inside solve3x3 is what makes the
-// small value work.  CIP_AUTO_REG overrides (api.hip: factor_resolve; lockstep.hip: GroupLoop).
+// small value work.  CIP_AUTO_REG overrides (api.hip: cip_factor_resolve; lockstep.hip: GroupLoop).
 #define CIP_AUTO_REG 1e-13
 
 // assemble.hip: the assembled K of every problem of the thread's mask becomes K + E, E_ii = +-rel * max_j |K_ij| (what cip_assemble does
 // behind the assembly while h->reg_rel > 0; a lock-step group calls it under the mask of its regularised problems)
 int cip_regularize(cip_handle *h, double rel);
 int cip_mul_Q(cip_handle *h, double alpha, const double *x, double beta, double *y, bool symv = true);   // api.hip: y = alpha Q x + beta y, dense or CSR Q
+int cip_mul_A(cip_handle *h, double alpha, const double *x, double beta, double *y);    // solve.hip: y = alpha A x + beta y (m), dense or CSR A
+int cip_mul_At(cip_handle *h, double alpha, const double *x, double beta, double *y);   // solve.hip: y = alpha A' x + beta y (n)
+inline bool cip_all_r(const cip_handle *h) { return h->m > 0 && h->nq == 0 && !h->cs.has_S; }   // every cone is an R cone: F = diag(packed scaling)
 int cip_handle_alloc(cip_handle *h, void **out, size_t bytes);      // api.hip: an allocation of the handle's own
 // api.hip, level 1 in parts (a lock-step group sizes its slabs from problem 0's plan before anything exists on the device):
 // the host half; the layout of the device block (null base: its size); the device half inside a slab.
@@ -146,9 +149,61 @@ inline bool cip_grp_Q_nonempty(const cip_handle *h) {        // at least one of 
     return cip_in_batch() ? (cip_tl_bz.mask & cip_tl_bz.q_nonempty) != 0 : h->Q_nnz > 0;
 }
 size_t cip_driver_bytes(const cip_handle *h);                        // driver.hip: vectors of the interior-point loop
-// api.hip: resolve the pivot flag of the last factorisation (wait = 0: only if its read-back has already landed)
-int cip_factor_resolve(cip_handle *h, int wait);
+// api.hip: resolve the pivot flag of the last factorisation (wait = false: only if its read-back has already landed)
+int cip_factor_resolve(cip_handle *h, bool wait);
 
 // api.hip: roctx ranges (no-ops when the marker library is not present)
 void cip_range_push(const char *name);
 void cip_range_pop(void);
+struct CipRange { explicit CipRange(const char *n) { cip_range_push(n); } ~CipRange() { cip_range_pop(); } };
+
+// ---- views of the handle's packed scratch buffers (8-byte granular, the staging view 16); each layout function sizes the allocation and
+// carves for every user
+#define CIP_MANY_CHUNK 64
+struct Vec3 { double *x, *y, *z; };            // an (n, p, m) triple of k columns each
+inline Vec3 cip_take3(CipLayout &L, const cip_handle *h, size_t k = 1, size_t g = 8) { return Vec3{L.take<double>(h->n * k, g), L.take<double>(h->p * k, g), L.take<double>(h->m * k, g)}; }
+// h->stage (cap = 1), h->many_stage (cap = CIP_MANY_CHUNK): an input and an output triple of `cap` columns each; a chunk of fewer
+// columns uses the front of every block, so the layout is one and the same for every chunk.  16-byte granular: the blocks stand in for a
+// device caller's vectors, and the mat-vecs sum in another order (vecops.hip: k_gemv_t) when theirs is not 16-byte aligned -- the
+// refined solve of a regularised factor multiplies by its own outputs
+struct StageView { Vec3 in, out; };
+inline size_t stage_layout(CipLayout L, const cip_handle *h, size_t cap, StageView *v) {
+    v->in = cip_take3(L, h, cap, 16);
+    v->out = cip_take3(L, h, cap, 16);
+    return L.bytes();
+}
+// h->ref: right-hand side, residual and correction of the refined solve, 8 spare doubles behind each
+struct RefView { Vec3 rhs, res, cor; };
+inline size_t ref_layout(CipLayout L, const cip_handle *h, RefView *v) {
+    for (Vec3 *b : {&v->rhs, &v->res, &v->cor}) { *b = cip_take3(L, h); L.take<double>(8, 8); }
+    return L.bytes();
+}
+// h->many, CIP_MANY_CHUNK columns each: the Npad-row right-hand sides R, the m-row blocks T and U of the Schur route, the sweeps' scratch S
+struct ManyView { double *R, *T, *U, *S; };
+inline size_t many_layout(CipLayout L, const cip_handle *h, ManyView *v) {
+    const size_t c = CIP_MANY_CHUNK;
+    *v = ManyView{L.take<double>(c * h->Npad, 8), L.take<double>(c * h->m, 8), L.take<double>(c * h->m, 8), L.take<double>(c * h->ws.Bs, 8)};
+    return L.bytes();
+}
+
+// ---- hipGraph replay of a handle's fixed launch sequences (api.hip: the factorisation; solve.hip: the triangular sweeps): `enqueue`
+// runs as it is, or -- where api.hip's cip_graph_wanted says so -- is recorded once into *exec (cip_launch) and replayed
+bool cip_graph_wanted(cip_handle *h);
+template <class F>
+static int graph_run(cip_handle *h, hipGraphExec_t *exec, F &&enqueue, bool *replayed = nullptr) {
+    if (cip_in_batch() || !cip_graph_wanted(h) || h->timing || h->ws.prof) return enqueue();
+    if (!*exec) {
+        CipGraphBuilder b = {nullptr, nullptr, false, true};
+        if (hipGraphCreate(&b.graph, 0) != hipSuccess) { (void)hipGetLastError(); h->graph_state = -1; return enqueue(); }
+        cip_tl_builder = &b;
+        const int rc = enqueue();                // records kernel nodes, launches nothing
+        cip_tl_builder = nullptr;
+        hipError_t ei = hipErrorUnknown;
+        if (rc == 0 && b.ok && b.have_last) ei = hipGraphInstantiate(exec, b.graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(b.graph);
+        if (ei != hipSuccess) { (void)hipGetLastError(); *exec = nullptr; h->graph_state = -1; return enqueue(); }
+    }
+    CIP_HIP_CHECK(hipGraphLaunch(*exec, h->stream));
+    if (replayed) *replayed = true;
+    return 0;
+}

@@ -21,11 +21,18 @@ void cip_set_error(const char *fmt, ...);
             return -3;                                                            \
         }                                                                         \
     } while (0)
+// a step of the library's own: its non-zero return code is the caller's
+#define CIP_TRY(expr)                                                             \
+    do {                                                                          \
+        const int rc__ = (expr);                                                  \
+        if (rc__) return rc__;                                                    \
+    } while (0)
 
 // ---------------------------------------------------------------- device workspaces: one walk sizes and carves
 // The layout of a workspace is ONE function that takes its members from a CipLayout, in order.  Over the allocation the walk carves;
 // over a null base take() returns null and only counts, and bytes() is what to allocate -- sizing and carve cannot disagree.  An offset
-// is tracked, not a moving pointer: no arithmetic on null.  A member's size is rounded up to `granule` bytes (api.hip: packed layouts, 8).
+// is tracked, not a moving pointer: no arithmetic on null.  A member's size is rounded up to `granule` bytes (cip_handle.h: packed
+// layouts, 8; the staging view, 16) -- the size, not the address: a layout's counts must not depend on who walks it.
 struct CipLayout {
     char *base; size_t off = 0;
     CipLayout(const void *b) : base((char *)b) {}          // (implicit: a layout function is called with the base pointer, or NULL)
@@ -81,7 +88,7 @@ struct CipBatch { long stride; unsigned long long mask; };            // stride 
 struct CipBatchCtx {
     int B; long stride; unsigned long long mask;
     double *gather_dev; double *gather_host;       // B x CIP_GATHER doubles (device / pinned host): per-problem scalar results
-    // bit z: problem z's factor is of the regularised matrix K + E -- its solves are refined against the true operator (api.hip:
+    // bit z: problem z's factor is of the regularised matrix K + E -- its solves are refined against the true operator (solve.hip:
     // cip_solve3x3_dev).  Kept current by the group (lockstep.hip: GroupLoop); 0 outside a batch, where h->reg_rel says the same
     unsigned long long reg_mask;
     // What the group's host code -- run once, on problem 0's handle -- may not read from problem 0's CSR arrays alone (lockstep.hip:
@@ -94,6 +101,12 @@ struct CipBatchCtx {
 struct CipScal64 { double v[CIP_BATCH_MAX]; };     // one scalar per problem, passed by value
 extern thread_local CipBatchCtx cip_tl_bz;
 inline bool cip_in_batch() { return cip_tl_bz.B > 1; }
+// host code that narrows the thread's mask (set) leaves it as it found it
+struct CipMaskScope {
+    const unsigned long long saved = cip_tl_bz.mask;
+    ~CipMaskScope() { cip_tl_bz.mask = saved; }
+    void set(unsigned long long mask) { cip_tl_bz.mask = mask; }
+};
 template <typename T>
 __device__ __forceinline__ T *cip_bo(T *p, const CipBatch &cb) { return p ? (T *)((char *)p + (long)blockIdx.z * cb.stride) : p; }
 #define CIP_BATCH_GUARD(cb) do { if (!(((cb).mask >> blockIdx.z) & 1ull)) return; } while (0)
@@ -357,7 +370,7 @@ int cip_axpby_ps(hipStream_t s, int len, const double *alpha_host, const double 
 int cip_zero(hipStream_t s, long len, double *y);                     // batch-aware memset(0) of doubles
 int cip_copy(hipStream_t s, long len, const double *x, double *y);    // batch-aware device-to-device copy
 struct cip_handle;
-const double *cip_loop_all_r(cip_handle *h);     // api.hip: the packed scaling = diag F when every cone is an R cone, else NULL
+const double *cip_loop_all_r(cip_handle *h);     // solve.hip: the packed scaling = diag F when every cone is an R cone, else NULL
 // the element-wise chains of the interior-point loop, one kernel each (vecops.hip; f != NULL: all cones R, cone operations fused in)
 int cip_loop_resid(hipStream_t s, int n, int m, int p, double *rl, const double *zs, const double *c, const double *d, const double *b,
                    const double *lam, const double *f, double *r0, double *Gy, double *Ays);

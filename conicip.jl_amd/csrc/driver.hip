@@ -51,8 +51,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
     std::vector<double> optBest(B, INFINITY), dt((size_t)B * 16), q4((size_t)B * 4), n2((size_t)B * 4), sigma(B), mu(B), mubar(B),
         alpha(B), av(B), as(B), tmp(B);
     // (the loop narrows the thread's batch mask as problems stop; it leaves the mask as it found it)
-    struct MaskScope { unsigned long long saved = cip_tl_bz.mask; ~MaskScope() { cip_tl_bz.mask = saved; } } mask_scope;
-    auto set_mask = [](unsigned long long mk) { cip_tl_bz.mask = mk; };
+    CipMaskScope mask;
     auto count = [&](std::vector<int> &cnt, unsigned long long mk) { for (int z = 0; z < B; ++z) cnt[z] += (int)((mk >> z) & 1ull); };
     // The max-step pair (x1, d1), (x2, d2) of every problem of the mask (:708-709, :881-882, :927-928).  The minima ride on the next
     // read-back (wait: read back now); pair(z) reads problem z's behind it.  One problem: slots MS_SLOT, MS_SLOT + 1 of the host-mapped
@@ -76,7 +75,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
     };
 
     // ---------------------------------------------------------------- initial point (:704-713)
-    set_mask(active);
+    mask.set(active);
     CK(cip_set_scaling_identity(h));
     CK(factor()); count(n_factor, active);
     CK(cip_axpby(s, n, 1.0, c_d, 0.0, r0.y)); CK(cip_axpby(s, p, 1.0, d_d, 0.0, r0.w)); CK(cip_axpby(s, m, 1.0, b_d, 0.0, r0.v));
@@ -84,7 +83,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
     // initial point: one wait (LPs meet their first bad pivot here)
     CK(ride_pivots());
     CK(take_pivots(false));
-    set_mask(active);
+    mask.set(active);
     if (active) {
         CK(cip_solve4x4_dev(h, e, r0.base, zv.base)); count(n_solve, active);
         if (m > 0) {
@@ -95,11 +94,10 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
         }
     }
 
-    struct IterRange { IterRange() { cip_range_push("cip:iteration"); } ~IterRange() { cip_range_pop(); } };
     for (iters = 1; iters <= o.maxIters && active; ++iters) {                          // :730
         const int Iter = iters;
-        IterRange iter_range;
-        set_mask(active);
+        CipRange iter_range("cip:iteration");
+        mask.set(active);
         if (m > 0) CK(cip_set_scaling_from_iterate_dev(h, zv.v, zv.s, lam));           // :732-735 (F, lambda = F v)
         CK(factor()); count(n_factor, active);                                        // :737 -> :682
         // (round 5) the element-wise part of :746-753 is one kernel (vecops.hip: k_loop_resid) behind the mat-vecs; with R cones
@@ -136,7 +134,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
             if (outcome[z].status != CIP_STATUS_NONE) active &= ~(1ull << z);
         }
         if (!active) break;
-        set_mask(active);
+        mask.set(active);
 
         // ------------------------------------------------------------ predictor (:879-887)
         CK(cip_solve4x4_dev(h, lam, r0.base, daff.base)); count(n_solve, active);
@@ -176,7 +174,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
         unsigned long long refine = active;
         bool step_known = false;
         for (int it = 0; it < o.maxRefinementSteps && refine; ++it) {
-            set_mask(refine);
+            mask.set(refine);
             // rkkt = K dz (mat-vecs), then rkkt.v -= dz.s, rkkt.s = lam o (F dz.v) + lam o (F^-T dz.s), rIr = r - rkkt: one kernel
             // (vecops.hip: k_loop_refine)
             CK(cip_gemv_dev(h, CIP_MAT_Q, 0, 1.0, dz.y, 0.0, rkkt.y));
@@ -209,11 +207,11 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
                 if (rnorm < o.refinementThreshold) refine &= ~(1ull << z);
             }
             if (!refine) { step_known = spec; break; }
-            set_mask(refine);
+            mask.set(refine);
             CK(cip_solve4x4_dev(h, lam, rIr.base, dzr.base)); count(n_solve, refine);
             CK(cip_axpby(s, NT, 1.0, dzr.base, 1.0, dz.base));                        // :920
         }
-        set_mask(active);
+        mask.set(active);
 
         // ------------------------------------------------------------ step (:927-932)
         for (int z = 0; z < B; ++z) alpha[z] = 1.0;
@@ -236,14 +234,14 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
 namespace {
 
 // One problem: the handle's own policy -- a bad pivot switches it to the regularised factorisation for good (api.hip:
-// factor_resolve); a dead (zero / non-finite) pivot even then is where the reference's LU hands back NaNs and the loop ends
+// cip_factor_resolve); a dead (zero / non-finite) pivot even then is where the reference's LU hands back NaNs and the loop ends
 // with :Error at its next residual check (src/ConicIP.jl:870-873)
 struct OneProblem final : Loop {
     explicit OneProblem(cip_handle *h_) : Loop(h_, 1) {}
     int factor() override { return cip_factor(h); }
     int ride_pivots() override { return 0; }           // (cip_factor has enqueued their read-back)
     int take_pivots(bool) override {
-        const int rc = cip_factor_resolve(h, 1);
+        const int rc = cip_factor_resolve(h, true);
         if (rc != CIP_E_SINGULAR) return rc;
         outcome[0].status = CIP_STATUS_ERROR;
         active = 0;

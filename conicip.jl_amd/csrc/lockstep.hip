@@ -21,7 +21,7 @@
 // factorisation meets a bad pivot (it would switch to the regularised factorisation: LPs, singular Q with free
 // variables) is taken out of the lock-step group and solved afterwards by cip_conicip on its own handle -- or, with
 // cip_set_lockstep_regularize(1), switched to the regularised factorisation INSIDE its group: the group keeps a mask of
-// its regularised problems, regularises their K behind the assembly and refines their solves (api.hip: cip_solve3x3_dev).
+// its regularised problems, regularises their K behind the assembly and refines their solves (solve.hip: cip_solve3x3_dev).
 //
 // Not supported in lock-step (the caller falls back to the thread pool of batch.hip): S cones of order >= 133 (their
 // chip-wide kernels own one workspace), problems of differing shape.
@@ -156,7 +156,7 @@ std::atomic<int> g_keep_regularized{0};
 // into its row of the gather buffer (they ride on the next read-back, normally the dots'), and the problems whose fused panel
 // chain gave up an in-launch wait taken out of the group (ejected: solved alone afterwards).  A problem that met a bad pivot is
 // ejected too (keep == false), or joins `reg` (keep): the group's problems on the regularised factorisation, for good -- what
-// factor_resolve (api.hip) does to one handle, per problem of the group.  `reg` lives with the group: the side-by-side groups of
+// cip_factor_resolve (api.hip) does to one handle, per problem of the group.  `reg` lives with the group: the side-by-side groups of
 // a split call have their own.  A group of ONE problem is no batch for the kernels (no mask): there bit 0 of `reg` is the
 // handle's own reg_rel, which cip_assemble and the solves read as they do for a stand-alone handle.
 struct GroupLoop final : Loop {
@@ -238,7 +238,7 @@ struct GroupLoop final : Loop {
         if (!joining) return 0;
         // the problems that have just met their first bad pivot: assembly, regularisation and LDL' again, for them alone, and their
         // flags back.  No solve has been enqueued on the factorisation being replaced (Loop::run takes the flags first), and the redo
-        // is not a factorisation of its own in n_factor -- as for one problem (api.hip: factor_resolve)
+        // is not a factorisation of its own in n_factor -- as for one problem (api.hip: cip_factor_resolve)
         reg |= joining; publish();
         const unsigned long long mk = cip_tl_bz.mask;
         cip_tl_bz.mask = joining;

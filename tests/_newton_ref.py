@@ -1,5 +1,5 @@
 """Stage-by-stage references for the layer that joins the primitives into a Newton step: solve3x3_once, solve3x3_chunk,
-cip_solve2x2_dev and cip_solve4x4_dev (conicip.jl_amd/csrc/api.hip) and the fused k_s4_pre_r / k_s4_post_r (csrc/vecops.hip there).  No GPU here;
+cip_solve2x2_dev and cip_solve4x4_dev (conicip.jl_amd/csrc/solve.hip) and the fused k_s4_pre_r / k_s4_post_r (csrc/vecops.hip there).  No GPU here;
 tests/test_newton_ref.py checks this module, tests/test_gpu_newton.py applies it to the device.
 
 Why stages.  At the last interior-point iterations F spans ten decades and the Schur route is not backward stable: one
@@ -310,7 +310,7 @@ MANY_CHUNK = 64
 
 
 def paths(name):
-    """the code paths a case reaches, restated from api.hip / vecops.hip"""
+    """the code paths a case reaches, restated from solve.hip / vecops.hip"""
     c = CASES[name]
     m = sum(k for _, k in c["cones"])
     N = c["n"] + c["p"] + (m if c["route"] == "full3x3" else 0)

@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE: drives the product's host control plane (libcipkkt built host-only under ASan + UBSan or TSan, linked against
 // tests/hostsan/fake_hip.cpp) through the C ABI of include/cipkkt.h:
-//   1. the plugin levels on one handle (create, identity scaling, factor, check, host-pointer solves, 65 right-hand sides at once, the
-//      refined solves of a regularised factor, packed scaling, destroy), dense and CSR A, p = 0 and p > 0, both routes;
+//   1. the plugin levels on one handle (create, identity scaling, factor, check, host-pointer solves, every many-column entry point at 1
+//      and 65 right-hand sides, solve4x4, the refined solves of a regularised factor -- with n_solve counted as include/cipkkt.h says --,
+//      packed scaling, destroy), dense and CSR A, p = 0 and p > 0, both routes;
 //   2. the native loop (cip_conicip) on a handle, with a trace buffer;
 //   3. cip_conicip_mixed on a batch built to hit every branch of the binning: 65 problems of one shape (a lock-step group of 64 and a
 //      group of ONE -- round 4's NULL write lived there), CSR problems of equal shape but different nnz, problems with p > 0, a
@@ -92,19 +93,42 @@ static void plugin_levels(const Prob &P) {
     REQUIRE(cip_factor(h) == CIP_OK);
     REQUIRE(cip_check_factor(h) == CIP_OK);
     std::vector<double> x(P.n, 1.0), y(P.p > 0 ? P.p : 1, 0.5), z(P.m, 0.25), dx(P.n), dy(P.p > 0 ? P.p : 1), dz(P.m);
+    const bool schur = P.route == CIP_ROUTE_SCHUR;
     REQUIRE(cip_solve3x3(h, x.data(), y.data(), z.data(), dx.data(), dy.data(), dz.data()) == CIP_OK);
-    if (P.route == CIP_ROUTE_SCHUR) REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_OK);
-    else REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_E_UNSUPPORTED);
+    REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == (schur ? CIP_OK : CIP_E_UNSUPPORTED));
     {   // 65 right-hand sides: a full chunk and a chunk of one through the handle's many-column buffers and their host staging
         const int k = 65;
         std::vector<double> X((size_t)P.n * k, 1.0), Y(y.size() * k, 0.5), Z((size_t)P.m * k, 0.25), DX(X.size()), DY(Y.size()), DZ(Z.size());
         REQUIRE(cip_solve3x3_many(h, k, X.data(), Y.data(), Z.data(), DX.data(), DY.data(), DZ.data()) == CIP_OK);
+        // 63: a chunk one column short of the staging buffer's 64 (on the tiny problem of main(): the blocks of the staging view must
+        // stay inside the allocation that was sized for 64 columns)
+        REQUIRE(cip_solve3x3_many(h, 63, X.data(), Y.data(), Z.data(), DX.data(), DY.data(), DZ.data()) == CIP_OK);
+        // the other many-column entry points, a single column (the single entry point) and 65 (the "device" pointers are host memory here)
+        for (int nr : {1, k}) {
+            REQUIRE(cip_solve2x2_many(h, nr, X.data(), Y.data(), DX.data(), DY.data()) == (schur ? CIP_OK : CIP_E_UNSUPPORTED));
+            REQUIRE(cip_solve3x3_many_dev(h, nr, X.data(), Y.data(), Z.data(), DX.data(), DY.data(), DZ.data()) == CIP_OK);
+            REQUIRE(cip_solve2x2_many_dev(h, nr, X.data(), Y.data(), DX.data(), DY.data()) == (schur ? CIP_OK : CIP_E_UNSUPPORTED));
+        }
     }
+    std::vector<double> lam(P.m, 1.0), r4((size_t)P.n + P.p + 2 * P.m, 1.0), dz4(r4.size());
+    REQUIRE(cip_solve4x4_dev(h, lam.data(), r4.data(), dz4.data()) == CIP_OK);
     // a regularised factor: the refined solves carve the handle's refinement buffers on first use
     REQUIRE(cip_set_regularization(h, 1e-13, 0) == CIP_OK);
     REQUIRE(cip_factor(h) == CIP_OK);
     REQUIRE(cip_solve3x3(h, x.data(), y.data(), z.data(), dx.data(), dy.data(), dz.data()) == CIP_OK);
-    if (P.route == CIP_ROUTE_SCHUR) REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_OK);
+    if (schur) REQUIRE(cip_solve2x2(h, x.data(), y.data(), dx.data(), dy.data()) == CIP_OK);
+    REQUIRE(cip_solve4x4_dev(h, lam.data(), r4.data(), dz4.data()) == CIP_OK);
+    {   // n_solve by the rule of include/cipkkt.h -- one per single solve, nrhs per many-column call, none for a refused call -- from
+        // the calls above: on the plain factor solve3x3, [solve2x2], solve3x3_many(65), solve3x3_many(63), then for nrhs = 1 and 65
+        // [solve2x2_many], solve3x3_many_dev, [solve2x2_many_dev], and solve4x4; on the regularised one solve3x3, [solve2x2], solve4x4.
+        // [Schur route only]
+        const int two2 = schur ? 1 : 0;
+        const int expect = (1 + two2 + 65 + 63 + (1 + 65) * (two2 + 1 + two2) + 1) + (1 + two2 + 1);
+        double st[8];
+        REQUIRE(cip_stats(h, st) == CIP_OK);
+        if ((int)st[1] != expect) fprintf(stderr, "drive: n_solve is %d, the call list gives %d\n", (int)st[1], expect);
+        REQUIRE((int)st[1] == expect);
+    }
     REQUIRE(cip_set_regularization(h, 0.0, 1) == CIP_OK);
     REQUIRE(cip_factor(h) == CIP_OK);
     const size_t len = cip_scaling_packed_len(h);
@@ -358,6 +382,8 @@ int main(int argc, char **argv) {
     plugin_levels(make(10, 2, {{CIP_CONE_R, 4}, {CIP_CONE_Q, 6}}, 0.4));
     plugin_levels(make(12, 3, {{CIP_CONE_R, 5}, {CIP_CONE_Q, 5}, {CIP_CONE_S, 6}}, 1.0, CIP_ROUTE_FULL3X3));
     plugin_levels(make(4, 0, {{CIP_CONE_S, 133 * 134 / 2}}, 1.0));
+    plugin_levels(make(1, 0, {{CIP_CONE_R, 1}}, 1.0));               // n + p + m = 2: every staged block is a few doubles
+    plugin_levels(make(3, 1, {{CIP_CONE_R, 1}}, 1.0));               // odd block lengths 3, 1, 1
     standalone_ldlt();
     run_mixed(65, true, 3);
     run_mixed(1, false, 1);

@@ -1,5 +1,5 @@
 """Problems that need the regularised LDL' inside their lock-step group (`cip_set_lockstep_regularize(1)`, csrc/lockstep.hip:
-GroupLoop; csrc/api.hip: the refined solves under a batch mask; csrc/assemble.hip: the regularisation's tile pass).
+GroupLoop; csrc/solve.hip: the refined solves under a batch mask; csrc/assemble.hip: the regularisation's tile pass).
 
 The bar is the one of tests/test_gpu_lockstep.py: bit-identity with `cip_conicip` on each problem -- status, Iter, n_factor,
 n_solve, (y, w, v), the six scalars -- with the one-problem reference run under the solve block the lock-step call uses.

@@ -1,5 +1,5 @@
 """The layer that joins the primitives into a Newton step -- solve3x3_once, solve3x3_chunk, cip_solve2x2_dev, cip_solve4x4_dev
-(conicip.jl_amd/csrc/api.hip) and the fused k_s4_pre_r / k_s4_post_r (csrc/vecops.hip there) -- at late-iteration scalings (F over ten decades, Q
+(conicip.jl_amd/csrc/solve.hip) and the fused k_s4_pre_r / k_s4_post_r (csrc/vecops.hip there) -- at late-iteration scalings (F over ten decades, Q
 iterates with gaps down to 1e-10, S iterates with spans up to 1e8), judged STAGE BY STAGE in extended precision at the device's
 own upstream outputs: the packed scaling read back with get_scaling_packed, the factor read back with kkt_matrix() after
 factor().  Stages, bounds, the case table and the end-to-end record are those of tests/_newton_ref.py (checked on the CPU by
@@ -166,7 +166,7 @@ def _bits(a, b):
 
 
 def _public_sequence(ks, P, lam, r):
-    """cip_solve4x4_dev's generic path as the public calls it is written as (api.hip): cone_div, F' in place, two axpby,
+    """cip_solve4x4_dev's generic path as the public calls it is written as (solve.hip): cone_div, F' in place, two axpby,
     solve3x3_dev with c aliasing z, F, F', axpby"""
     from cipkkt import OP_F, OP_FT
     n, p, m = P.n, P.p, P.m
@@ -220,6 +220,50 @@ def test_generic_solve4x4_is_its_sequence_of_public_calls(route, rel):
             ks.solve4x4_dev(lam, buf[:len4], buf[len4 - k:])
             torch.cuda.synchronize()
             assert _bits(rr.cpu().numpy(), got) and _bits(buf[len4 - k:].cpu().numpy(), got), (route, rel, kind)
+    finally:
+        ks.close()
+
+
+@pytest.mark.parametrize("rel", [0.0, 1e-10], ids=["plain", "regularised"])
+@pytest.mark.parametrize("route", ["schur", "full3x3"])
+def test_host_pointer_entry_points_return_their_device_twins_bits(route, rel):
+    """cip_solve3x3, cip_solve2x2 (Schur route) and the host cip_solve3x3_many / cip_solve2x2_many at 1 and 65 columns stage their
+    blocks through the handle and call the device entry point: exactly (torch.equal) what the _dev twin writes for the same inputs
+    on the same factor.  n = 96, p = 8, R(16) + Q(5) + S(3x3): every block of the right-hand side, Npad = 128 (Schur) or 256 (full
+    3x3), and a second 64-column chunk; on a plain factor and on a regularised one (the refined solves, column by column)."""
+    import cipkkt
+    P = NR.make_problem("hostdev", dict(n=96, p=8, cones=[("R", 16), ("Q", 5), ("S", 6)], route=route, csr=False, mu=1e-2))
+    n, p, m = P.n, P.p, P.m
+    ks = cipkkt.KKTSystem(P.Q, P.A, P.G, P.cone_dims, route=route)
+    try:
+        assert ks.Npad == (128 if route == "schur" else 256)
+        if rel:
+            assert ks.lib.cip_set_regularization(ks.h, C.c_double(rel), 0) == 0
+        ks.set_scaling_from_iterate(_dev(P.v), _dev(P.s), _dev(np.zeros(m)))
+        ks.factor()
+        assert ks.health() == dict(reg_rel=rel, n_regularized=0, n_chain_fallbacks=0)
+        rng = np.random.default_rng(17)
+        nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device="cuda")
+        same = lambda host, dev: torch.equal(torch.from_numpy(np.ascontiguousarray(host.T)), dev.cpu())    # (rows, k) against (k, rows)
+
+        x, y, z = rng.standard_normal(n), rng.standard_normal(p), rng.standard_normal(m)
+        a, b, c = nan(n), nan(p), nan(m)
+        ks.solve3x3_dev(_dev(x), _dev(y), _dev(z), a, b, c)
+        assert all(same(h_, d_) for h_, d_ in zip(ks.solve3x3(x, y, z), (a, b, c))), "solve3x3"
+        if route == "schur":
+            dy, dw = nan(n), nan(p)
+            ks.solve2x2_dev(_dev(x), _dev(y), dy, dw)
+            assert all(same(h_, d_) for h_, d_ in zip(ks.solve2x2(x, y), (dy, dw))), "solve2x2"
+        for k in (1, 65):
+            X, Y, Z = rng.standard_normal((k, n)), rng.standard_normal((k, p)), rng.standard_normal((k, m))
+            A, B, Cm = nan(k, n), nan(k, p), nan(k, m)
+            ks.solve3x3_many_dev(_dev(X), _dev(Y), _dev(Z), A, B, Cm)
+            assert all(same(h_, d_) for h_, d_ in zip(ks.solve3x3_many(X.T, Y.T, Z.T), (A, B, Cm))), ("solve3x3_many", k)
+            if route == "schur":
+                DY, DW = nan(k, n), nan(k, p)
+                ks.solve2x2_many_dev(_dev(X), _dev(Y), DY, DW)
+                assert all(same(h_, d_) for h_, d_ in zip(ks.solve2x2_many(X.T, Y.T), (DY, DW))), ("solve2x2_many", k)
+        assert ks.health()["reg_rel"] == rel
     finally:
         ks.close()
 
