@@ -66,6 +66,7 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
     const int wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int l15 = lane & 15, l4 = lane >> 4;
+    const int wu = __builtin_amdgcn_readfirstlane(wave);       // the wave index as a scalar: what is wave-uniform stays off the vector unit
 
     // staging: 64 rows x 16 k per operand = 512 double2 -> 2 per thread: e = q*256 + tid, k = e >> 5, rp = e & 31
     const int k_ld = tid >> 5, rp = tid & 31;
@@ -97,7 +98,7 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
     auto gdma = [&](int kt, int buf) {
         typedef __attribute__((address_space(1))) const void *gptr_t;
         typedef __attribute__((address_space(3))) void *lptr_t;
-        double *la = lds + buf * (2 * CIP_KT * SB) + 2 * wave * SB;      // wave-uniform; the hardware adds lane x 16 bytes
+        double *la = lds + buf * (2 * CIP_KT * SB) + 2 * wu * SB;        // wave-uniform; the hardware adds lane x 16 bytes
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const long k = (long)kt * CIP_KT + q * 8 + k_ld;
@@ -127,24 +128,51 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
         __syncthreads();
     }
     // lane holds, for tile (ti,tj), reg q: row = i0 + wm*32 + 2*l15 + ti, col = j0 + wn*32 + 2*(l4 + 4q) + tj
+    const long row = i0 + wm * 32 + 2 * l15;
+    const long col0 = j0 + wn * 32 + 2 * l4;             // col = col0 + 8 q + tj
+    // The epilogues that read memory fetch the lane's whole C operand in ONE batch, then update and store: a load placed behind a
+    // store to C cannot be hoisted over it (ldc is a run-time value: for all the compiler knows the two alias), and read, update
+    // and write tile by tile are eight dependent round trips to HBM per wave.
+    // EPI_ACCUM / EPI_LAZYC address their tile as (wave-uniform column base, a scalar) + (ONE 32-bit byte offset of the lane, below
+    // 48 ld + 256: the launchers refuse a pitch of 2^26 and more) -- no 64-bit vector address per column, on either side.
+    const long rowu = i0 + (wu & 1) * 32, colu = j0 + (wu >> 1) * 32;
+    const unsigned lofc = ((unsigned)(2 * l15) + (unsigned)(2 * l4) * (unsigned)g.ldc) * 8u;
+    const unsigned lofq = ((unsigned)(2 * l15) + (unsigned)(2 * l4) * (unsigned)g.ldq) * 8u;
+    auto cat = [&](int tj, int q) { return (v2d *)((char *)(g.C + rowu + (colu + 8 * q + tj) * g.ldc) + lofc); };
+    auto qat = [&](int tj, int q) { return (const v2d *)((const char *)(g.Qin + rowu + (colu + 8 * q + tj) * g.ldq) + lofq); };
+    v2d cin[2][4];
+    v2d cdg = (v2d){0.0, 0.0};     // EPI_LAZYC: Cdiag[row], Cdiag[row + 1] -- a lane meets the diagonal in one q (= l15 / 4) at the most
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const long col = j0 + wn * 32 + 2 * (l4 + 4 * q) + tj;
-            const long row = i0 + wm * 32 + 2 * l15;
+            const long col = col0 + 8 * q + tj;
+            if (EPI == EPI_ACCUM) cin[tj][q] = *cat(tj, q);
+            else if (EPI == EPI_LAZYC) cin[tj][q] = *qat(tj, q);
+            else if (EPI == EPI_SYRKQ && col < g.nvalid) {
+                const double *qp = g.Qin + row + col * g.ldq;       // Q keeps the caller's (possibly odd) pitch
+                if (row + 1 < g.nvalid) cin[tj][q] = (v2d){qp[0], qp[1]};
+                else if (row < g.nvalid) cin[tj][q].x = qp[0];
+            }
+        }
+    if (EPI == EPI_LAZYC && row >= col0 && row < col0 + 32 && ((row - col0) & 7) == 0) cdg = (v2d){g.Cdiag[row], g.Cdiag[row + 1]};
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const long col = col0 + 8 * q + tj;
             double *cp = g.C + row + col * g.ldc;
             const v2d val = (v2d){acc[0][tj][q], acc[1][tj][q]};
             if (EPI == EPI_ACCUM) {
-                v2d c = *(v2d *)cp;
+                v2d c = cin[tj][q];
                 c += g.alpha * val;
-                *(v2d *)cp = c;
+                *cat(tj, q) = c;
             } else if (EPI == EPI_LAZYC) {    // the C operand comes from Qin (+ Cdiag on the diagonal): what a copy into C would have put there
-                v2d c = *(const v2d *)(g.Qin + row + col * g.ldq);
-                if (row == col) c.x = g.Cdiag[row];
-                if (row + 1 == col) c.y = g.Cdiag[col];
+                v2d c = cin[tj][q];
+                if (row == col) c.x = cdg.x;
+                if (row + 1 == col) c.y = cdg.y;
                 c += g.alpha * val;
-                *(v2d *)cp = c;
+                *cat(tj, q) = c;
             } else if (EPI == EPI_STORE) {    // C = alpha acc, optionally also stored transposed
                 const v2d c = g.alpha * val;
                 *(v2d *)cp = c;
@@ -155,12 +183,8 @@ __device__ __forceinline__ void gemm_tile_64(const GemmArgs &g, double *lds, lon
                     else if (row < g.nvalid) *cp = g.alpha * val.x;
                 }
             } else if (col < g.nvalid) {      // EPI_SYRKQ: C = Qin + alpha acc inside the valid n x n corner
-                if (row + 1 < g.nvalid) {
-                    const double *qp = g.Qin + row + col * g.ldq;       // Q keeps the caller's (possibly odd) pitch
-                    *(v2d *)cp = (v2d){qp[0], qp[1]} + g.alpha * val;
-                } else if (row < g.nvalid) {
-                    *cp = g.Qin[row + col * g.ldq] + g.alpha * val.x;
-                }
+                if (row + 1 < g.nvalid) *(v2d *)cp = cin[tj][q] + g.alpha * val;
+                else if (row < g.nvalid) *cp = cin[tj][q].x + g.alpha * val.x;
             }
         }
 }

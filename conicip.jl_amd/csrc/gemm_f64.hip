@@ -117,8 +117,23 @@ __device__ __forceinline__ void gemm_tile_128(const GemmArgs &g, double *lds, in
     // ---- epilogue.  lane holds, for tile (ti,tj), reg q:  C[row, col] with
     //   row = i0 + wm*64 + (ti>>1)*32 + 2*l15 + (ti&1)
     //   col = j0 + wn*64 + (tj>>1)*32 + 2*(l4 + 4q) + (tj&1)
+    // The C operand is fetched one tj (eight loads) at a time, the batch of tj + 1 issued before the stores of tj: a load
+    // placed behind a store to C cannot be hoisted over it (gemm_tile_64: cfetch).
+    v2d cbuf[2][4][2];
+    auto cfetch = [&](int tj) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const long col = j0 + wn * 64 + (tj >> 1) * 32 + 2 * (l4 + 4 * q) + (tj & 1);
+#pragma unroll
+            for (int gi = 0; gi < 2; ++gi)
+                cbuf[tj & 1][q][gi] = STORE ? (v2d){0.0, 0.0} : *(const v2d *)(g.C + i0 + wm * 64 + gi * 32 + 2 * l15 + col * g.ldc);
+        }
+    };
+    cfetch(0);
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) {
+        if (tj + 1 < 4) cfetch(tj + 1);
+        const auto &cin = cbuf[tj & 1];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const long col = j0 + wn * 64 + (tj >> 1) * 32 + 2 * (l4 + 4 * q) + (tj & 1);
@@ -127,7 +142,7 @@ __device__ __forceinline__ void gemm_tile_128(const GemmArgs &g, double *lds, in
                 const long row = i0 + wm * 64 + gi * 32 + 2 * l15;
                 v2d val = (v2d){acc[2 * gi][tj][q], acc[2 * gi + 1][tj][q]};
                 double *cp = g.C + row + col * g.ldc;
-                v2d c = STORE ? (v2d){0.0, 0.0} : *(v2d *)cp;
+                v2d c = cin[q][gi];
                 c += g.alpha * val;
                 *(v2d *)cp = c;
             }
@@ -351,6 +366,12 @@ static bool gemm_dims_ok(int M, int N, int K, int *rc) {
     }
     return true;
 }
+// the accumulate epilogues of gemm_tile_64 address C (and Qin) with a 32-bit byte offset per lane, below 48 ld + 256
+static bool gemm_pitch_ok(long ld) {
+    if (ld < (1L << 26)) return true;
+    cip_set_error("gemm: leading dimension %ld too large", ld);
+    return false;
+}
 static long lower_tiles_128(int M) { const long tm = M / CIP_NB; return tm * (tm + 1) / 2; }
 static GemmArgs gemm_args(int M, int N, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc) {
     GemmArgs g = {};
@@ -361,6 +382,7 @@ static GemmArgs gemm_args(int M, int N, int K, double alpha, const double *A, lo
 
 int cip_gemm_lower(hipStream_t s, int M, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc) {
     int rc; if (!gemm_dims_ok(M, M, K, &rc)) return rc;
+    if (!gemm_pitch_ok(ldc)) return -1;
     GemmArgs g = gemm_args(M, M, K, alpha, A, lda, B, ldb, C, ldc);
     // every 128-tile of the lower triangle as four 64x64 quarter tiles (in plain tile order: an XCD-aware patch order fetched
     // less and ran slower, DESIGN_LOG.md "Experiments removed from the library")
@@ -373,6 +395,7 @@ int cip_gemm_lower_lazyc(hipStream_t s, int M, int K, double alpha, const double
                          const double *Qin, long ldq, const double *Cdiag) {
     int rc; if (!gemm_dims_ok(M, M, K, &rc)) return rc;
     if (!Qin || !Cdiag || (ldq & 1) || (((uintptr_t)Qin) & 15)) { cip_set_error("gemm: bad lazy-C arguments"); return -1; }
+    if (!gemm_pitch_ok(ldc) || !gemm_pitch_ok(ldq)) return -1;
     GemmArgs g = gemm_args(M, M, K, alpha, A, lda, B, ldb, C, ldc);
     g.Qin = Qin; g.ldq = ldq; g.Cdiag = Cdiag;
     cip_launch_b(k_ldlt_trailing_64<EPI_LAZYC>, dim3((unsigned)(4 * lower_tiles_128(M))), dim3(256), 0, s, g);
@@ -385,6 +408,7 @@ static bool rect_on_quarter_tiles(long tiles128) { return tiles128 < 256; }
 
 int cip_gemm_rect(hipStream_t s, int M, int N, int K, double alpha, const double *A, long lda, const double *B, long ldb, double *C, long ldc) {
     int rc; if (!gemm_dims_ok(M, N, K, &rc)) return rc;
+    if (!gemm_pitch_ok(ldc)) return -1;
     const GemmArgs g = gemm_args(M, N, K, alpha, A, lda, B, ldb, C, ldc);
     const long tiles = (long)(M / CIP_NB) * (N / CIP_NB);
     if (rect_on_quarter_tiles(tiles)) cip_launch_b(k_gemm_nt_64, dim3((unsigned)(4 * tiles)), dim3(256), 0, s, g);

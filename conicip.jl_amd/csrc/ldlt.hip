@@ -732,19 +732,21 @@ __global__ __launch_bounds__(256) void k_solve_step(SolveStepArgs a, CipBatch cb
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j < a.Bs) {
         const int r0 = a.tri == 1 ? 0 : (j & ~127), r1 = a.tri == 1 ? ((j + 128) & ~127) : a.Bs;
+        const double dj = a.out2 ? a.dsc[blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)] : 0.0;    // dsc[j], ahead of the dots as tgt[c] below
         double s = lane_dot(a.T + (long)j * a.Bs, a.v, r0, r1, lane);
         if (a.M) s -= lane_dot(a.M + (long)j * a.Bs, a.u, 0, a.Bs, lane);
         s = cip_wave_sum(s);
         if (lane == 0) {
             a.out[j] = s;
-            if (a.out2) a.out2[j] = s * a.dsc[j];
+            if (a.out2) a.out2[j] = s * dj;
         }
         return;
     }
     const int c = j - a.Bs;
     if (c >= a.ncols) return;
+    const double t0 = a.tgt[blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) - a.Bs];     // tgt[c], read ahead of the dot by a scalar load (vecops.hip: k_gemv_t)
     const double s = cip_wave_sum(lane_dot(a.Bm + (long)c * a.ldb, a.u, 0, a.Bs, lane));
-    if (lane == 0) a.tgt[c] -= s;
+    if (lane == 0) a.tgt[c] = t0 - s;
 }
 static int solve_fused(hipStream_t s, const double *K, int Npad, long ld, const LdltWorkspace &ws, double *rhs) {
     const int Bs = ws.Bs, nbk = Npad / Bs;

@@ -19,6 +19,10 @@ __global__ __launch_bounds__(256) void k_gemv_t(int rows, int cols, double alpha
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= cols) return;
     const double *a = A + (long)j * lda;
+    // y[j] is read ahead of the dot, not behind the wave reduction: one dependent round trip less at the tail of a launch, and
+    // the update launches of the triangular sweeps are latency-bound.  beta == 0: y may hold anything and is not read.
+    double y0 = 0.0;
+    if (beta != 0.0) y0 = y[blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];      // y[j], by a scalar load
     double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     int i = lane * 2;
     // rows even and 16-byte aligned columns are the common case (padded leading dimensions)
@@ -64,7 +68,7 @@ __global__ __launch_bounds__(256) void k_gemv_t(int rows, int cols, double alpha
         for (i = lane; i < rows; i += 64) s0 += a[i] * x[i];
     }
     const double s = wsum((s0 + s1) + (s2 + s3));
-    if (lane == 0) y[j] = alpha * s + (beta == 0.0 ? 0.0 : beta * y[j]);
+    if (lane == 0) y[j] = alpha * s + (beta == 0.0 ? 0.0 : beta * y0);
 }
 
 int cip_gemv_t(hipStream_t s, int rows, int cols, double alpha, const double *A, long lda, const double *x,
