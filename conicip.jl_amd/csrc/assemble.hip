@@ -9,7 +9,6 @@
 // Only the lower triangle is written / referenced; K is padded to a multiple of 128 with an
 // identity block.
 #include "cip_handle.h"
-#include <atomic>
 #include "../../include/cipkkt.h"
 
 // rows >= n of the Schur-route matrix: G block, zero block, identity padding (lower part)
@@ -336,19 +335,8 @@ __global__ __launch_bounds__(256) void k_pad_identity(double *K, long ldk, int N
 // columns are copied; the first trailing update takes its C operand from Q itself with the Schur diagonal from h->kdiag
 // (EPI_LAZYC) and writes K.  Every entry of K goes through the same operations as with the full copy (bit-identical
 // factor): 115 -> 25 us per factorisation at n = 8192, 7 of the 86 ms of a config-5 pass.
-int cip_ldlt_outer_block_for(int Npad);
-static std::atomic<int> g_lazy_copy{-1};  // CIP_LAZY_COPY / cip_set_lazy_copy: 1 (default) on, 0 off; read by worker threads
-int cip_lazy_copy_set(int on) {
-    int prev = g_lazy_copy.load(std::memory_order_relaxed);
-    if (prev < 0) {                                                  // first use: the environment decides (racing threads agree)
-        const int env = cip_env_int("CIP_LAZY_COPY", 1) != 0;
-        int expect = -1;
-        g_lazy_copy.compare_exchange_strong(expect, env);
-        prev = g_lazy_copy.load(std::memory_order_relaxed);
-    }
-    if (on == 0 || on == 1) g_lazy_copy.store(on);
-    return prev;
-}
+static CipKnob g_lazy_copy{[] { return (int)(cip_env_int("CIP_LAZY_COPY", 1) != 0); }};    // cip_set_lazy_copy: 1 (default) on, 0 off; read by worker threads
+int cip_lazy_copy_set(int on) { return g_lazy_copy.set(on, [](int v) { return v == 0 || v == 1; }); }
 static int assemble_schur(cip_handle *h, bool lazy_ok) {
     hipStream_t s = h->stream;
     int rc;
@@ -364,9 +352,12 @@ static int assemble_schur(cip_handle *h, bool lazy_ok) {
         if (h->Q_sparse && cip_grp_Q_nonempty(h))
             cip_launch_b(k_qcsr_scatter<true>, dim3((n + 3) / 4), dim3(256), 0, s, h->K, h->ldk, 0, n, h->Q_rp, h->Q_ci, h->Q_v, 6);
     } else {
-        const int lazy_now = g_lazy_copy.load(std::memory_order_relaxed);
-        const int lazy_on = lazy_now < 0 ? cip_lazy_copy_set(-1) : lazy_now;
+        const int lazy_on = g_lazy_copy.get();
         bool all_r = cip_all_r(h);
+        // nb0 must be the width of the FIRST outer block of the factorisation that follows: only its columns are copied, and that
+        // factorisation's first trailing update is what fills the rest of K.  The two agree because both ask the same rule
+        // (cip_ldlt_plan.h: ldlt_outer_block) with the settings as they stand -- the lazy form needs n > nb0, where the first block
+        // is the regular width whatever the tail rule -- and the caller factors right behind this assembly (lazy_ok)
         const int nb0 = cip_ldlt_outer_block_for(h->Npad);
         if (!h->Q_sparse && lazy_on && lazy_ok && all_r && cip_grp_A_one_per_row(h) && p == 0 && h->Npad == n && n > nb0 && h->reg_rel <= 0.0 && h->kdiag &&
             copy_lower_vectorisable(h->K, h->ldk, 0, h->Q, (long)n, n)) {

@@ -51,6 +51,21 @@ int cip_env_int(const char *name, int dflt);
 long cip_env_long(const char *name, long dflt);
 double cip_env_double(const char *name, double dflt);
 bool cip_env_set(const char *name);
+// A process-wide setting: the environment's default on first use (racing threads agree on it), a setter that returns the previous
+// value, and the library's worker threads may read while a caller sets.  Defined with its default as a captureless lambda that
+// calls cip_env_*, so that the variable's name stands at the knob's definition (ldlt.hip: g_solve_fused).
+#include <atomic>
+#include <limits.h>
+struct CipKnob {
+    int (*const dflt)(void);
+    std::atomic<int> v{INT_MIN};                                   // INT_MIN: not read yet
+    int get() {
+        int cur = v.load(std::memory_order_relaxed);
+        if (cur == INT_MIN && v.compare_exchange_strong(cur, dflt())) cur = v.load();      // (a lost race leaves the winner's value in cur)
+        return cur;
+    }
+    template <class Valid> int set(int nv, Valid valid) { const int prev = get(); if (valid(nv)) v.store(nv); return prev; }   // stores a valid nv, else only queries
+};
 
 // ---------------------------------------------------------------- launches that can be recorded into a hipGraph
 // The LDL' factorisation and the triangular solves of a handle are fixed launch sequences (same pointers, same sizes

@@ -7,7 +7,7 @@
 // whose LDL' exists for the static pivot order (S > 0, G full row rank).
 //
 // Blocked right-looking algorithm, two levels:
-//   outer block NBO (512, 768 from order 4096 on) = NBO/128 inner panels of 128 columns
+//   outer block NBO (512; from order 4096 on 896, and a last block of up to 2816 columns: cip_ldlt_plan.h) = NBO/128 inner panels of 128 columns
 //   per inner panel:  diag 128x128 LDL' (1 workgroup, LDS) -> substitution TRSM (W = A21 inv(L11)', L = W D^-1) -> update of
 //                     the block's remaining panel columns; on the serial schedule these are ONE launch per panel
 //                     (diag.hip: k_ldlt_panel), in lock-step batches three
@@ -25,51 +25,52 @@
 // that a wider block has more of, then run beside the diagonal kernels and a trailing update with K = 768 passes over C
 // less often: same-session A/B at n = 8192, 512 / 768 / 1024 -> 130.6-132.0 / 134.5 / 133.9 KKT solves/s), else 512 (unfused
 // chain, round 1: 256 / 384 / 512 -> 107.7 / 107.0 / 109.1; 1024 -> 125 against 128).
-#include <atomic>
-#include <mutex>
+// Round 4 re-tuned the automatic width on the current chain (same-session A/B, wide last block in force; CIP_LDLT_NBO_AUTO overrides):
+// 640 / 768 / 896 / 1024 -> 185.4 / 189.1 / 191.3 / 188.7 KKT solves/s at n = 8192 (6 x 896 + 2816: one trailing update
+// fewer, 60.1 TFLOP/s), config 3 (order 4608) 31.3 -> 30.0 ms, the literal 3x3 route at N = 16384 35.7 -> 35.8.
+#include "cip_ldlt_plan.h"
 #include <vector>
-static std::atomic<int> g_nbo{0};         // read by the library's worker threads (batch.hip) while a caller may set it
-static std::atomic<int> g_fuse_diag{-1};
-static std::once_flag g_fuse_once;
+static CipKnob g_nbo{[] { return 0; }};
 // 3 (default; CIP_FUSE_DIAG: any value but 0): one launch per panel, the previous panel's in-block update and this panel's
 // TRSM pipelined behind the diagonal kernel (k_ldlt_panel); 0: diag -> TRSM -> in-block update, three launches per panel
-static void fuse_env(void) {
-    std::call_once(g_fuse_once, [] {
-        g_fuse_diag = cip_env_int("CIP_FUSE_DIAG", 3) == 0 ? 0 : 3;
-    });
-}
-int cip_ldlt_outer_block_for(int Npad) {
-    { const int v = g_nbo.load(std::memory_order_relaxed); if (v > 0) return v; }
-    fuse_env();
-    // Round 4 re-tuned the width on the current chain (same-session A/B, wide last block in force; CIP_LDLT_NBO_AUTO overrides):
-    // 640 / 768 / 896 / 1024 -> 185.4 / 189.1 / 191.3 / 188.7 KKT solves/s at n = 8192 (6 x 896 + 2816: one trailing update
-    // fewer, 60.1 TFLOP/s), config 3 (order 4608) 31.3 -> 30.0 ms, the literal 3x3 route at N = 16384 35.7 -> 35.8.
-    static const int nbo_auto = [] { const int v = cip_env_int("CIP_LDLT_NBO_AUTO", 896); return (v >= 256 && v <= 1024 && v % CIP_NB == 0) ? v : 896; }();
-    return (Npad >= 4096 && g_fuse_diag) ? nbo_auto : 512;    // not a function of the batch: lock-step groups reproduce the one-problem loop bit for bit
-}
+static CipKnob g_fuse_diag{[] { return cip_env_int("CIP_FUSE_DIAG", 3) == 0 ? 0 : 3; }};
+static CipKnob g_side_prep{[] { return (int)(cip_env_int("CIP_SIDE_PREP", 1) != 0); }};
 #define CIP_NBO_MAX 1024
 #define CIP_TAIL_MAX 3072               // widest last block (CIP_LDLT_TAIL is clamped to it): Wbuf has room for it from order 4096 on
 static size_t wbuf_cols(int Npad) { return Npad >= 4096 ? (Npad < CIP_TAIL_MAX ? Npad : CIP_TAIL_MAX) : CIP_NBO_MAX; }
+// The settings of one factorisation (cip_ldlt_plan.h): the ONLY place where a factorisation loads them, once, before its first launch.
 // The LAST outer block takes everything that is left once that is no more than CIP_LDLT_TAIL columns (round 3; automatic
 // widths only, orders from 4096 on).  At the bottom of the matrix a trailing update is a handful of tiles per CU behind a
 // K = 768 loop (r = 1280 and r = 512 at n = 8192: 36 us each, 6 TFLOP/s) while the panel launches leave most of the chip idle:
 // in a wide last block the same flops are in-block update tiles (K = 128, lower triangle only) that run BESIDE the diagonal
 // kernels.  Same-session A/B at n = 8192, tail 0 / 1280 / 2048 / 2816 / 3584 / 4352: 180.5 / 181.8 / 183.1 / 185.4 / 184.7 /
 // 182.5 KKT solves/s (beyond 2816 the block's first panel launches are bound by their ~900 tiles: 57 / 52 / 51 us).
-// A function of the order and the column only, like the width itself.
-static int ldlt_tail_cols(void) {
-    static const int v = [] { const int t = cip_env_int("CIP_LDLT_TAIL", 2816); return t > CIP_TAIL_MAX ? CIP_TAIL_MAX : t; }();
-    return v;
+static LdltKnobs ldlt_knobs(void) {
+    static const LdltKnobs env = [] {
+        LdltKnobs k{};
+        k.nbo_auto = cip_env_int("CIP_LDLT_NBO_AUTO", 896);
+        if (k.nbo_auto < 256 || k.nbo_auto > 1024 || k.nbo_auto % CIP_NB) k.nbo_auto = 896;
+        k.tail = cip_env_int("CIP_LDLT_TAIL", 2816);
+        if (k.tail > CIP_TAIL_MAX) k.tail = CIP_TAIL_MAX;
+        k.side_from = cip_env_int("CIP_SIDE_PREP_FROM", 2048);
+        k.ls_panel_max = cip_env_int("CIP_LOCKSTEP_PANEL_MAX", 32);
+        if (cip_env_set("CIP_LOCKSTEP_PANEL_CUS")) k.ls_panel_cus = cip_env_int("CIP_LOCKSTEP_PANEL_CUS", 0);
+        else {
+            int dev = 0, cus = 256;
+            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+            k.ls_panel_cus = 4 * cus;
+        }
+        return k;
+    }();
+    return LdltKnobs{g_nbo.get(), env.nbo_auto, env.tail, g_fuse_diag.get(), g_side_prep.get(), env.side_from, env.ls_panel_max, env.ls_panel_cus};
 }
-static int outer_block_width(int Npad, int C0) {
-    const int NBO = cip_ldlt_outer_block_for(Npad), left = Npad - C0;
-    if (g_nbo == 0 && NBO >= 640 && left <= ldlt_tail_cols()) return left;
-    return left < NBO ? left : NBO;
-}
-int cip_ldlt_outer_block(void) { return g_nbo; }
-void cip_ldlt_set_outer_block(int nbo) {
-    if (nbo == 0 || (nbo >= CIP_NB && nbo % CIP_NB == 0 && nbo <= 1024)) g_nbo = nbo;
-}
+int cip_ldlt_outer_block_for(int Npad) { return ldlt_outer_block(ldlt_knobs(), Npad); }
+int cip_ldlt_outer_block(void) { return g_nbo.get(); }
+void cip_ldlt_set_outer_block(int nbo) { g_nbo.set(nbo, [](int v) { return v == 0 || (v >= CIP_NB && v % CIP_NB == 0 && v <= 1024); }); }
+// CIP_FUSE_DIAG=0 / cip_set_ldlt_fused_chain(0): the three-launch chain (diag -> TRSM -> update per panel), the give-up
+// fall-back and the bitwise reference of the fused one; 3 selects the fused chain, any other value only queries
+int cip_ldlt_set_fused_chain(int on) { return g_fuse_diag.set(on, [](int v) { return v == 0 || v == 3; }); }
+int cip_ldlt_set_side_prep(int on) { return g_side_prep.set(on, [](int v) { return v == 0 || v == 1; }); }
 
 // ---- optional instrumentation: HIP events around every trailing-update launch (bench.py roofline)
 struct LdltProfile {
@@ -162,16 +163,11 @@ int cip_prof_slot_end(int slot, hipStream_t s) {
 // thread's override (lock-step batches create their handles with 256: in a batch a block step is one launch for all
 // problems, so launches are cheap and the doubled inverses -- 1.5 GFLOP per n = 2048 factorisation on top of its 2.9 --
 // and the half-empty 1024-wide triangular blocks the solves stream are what cost).
-static std::atomic<int> g_solve_block_max{-1};
+static CipKnob g_solve_block_max{[] { return cip_env_int("CIP_SOLVE_BLOCK", 1024); }};
 thread_local int cip_tl_solve_block_max = 0;
-int cip_solve_block_max_set(int b) {
-    if (g_solve_block_max.load() < 0) { int v = -1; g_solve_block_max.compare_exchange_strong(v, cip_env_int("CIP_SOLVE_BLOCK", 1024)); }
-    const int prev = g_solve_block_max.load();
-    if (b == 128 || b == 256 || b == 512 || b == 1024) g_solve_block_max.store(b);
-    return prev;
-}
+int cip_solve_block_max_set(int b) { return g_solve_block_max.set(b, [](int v) { return v == 128 || v == 256 || v == 512 || v == 1024; }); }
 int cip_solve_block(int Npad) {
-    int mx = cip_tl_solve_block_max > 0 ? cip_tl_solve_block_max : cip_solve_block_max_set(0);
+    int mx = cip_tl_solve_block_max > 0 ? cip_tl_solve_block_max : g_solve_block_max.get();
     if (mx < CIP_NB) mx = CIP_NB;
     // (2048: only through the calling thread's override -- the order-2048 workspaces of large S cones want inv(L) of the WHOLE matrix,
     //  sdp_large.hip; the public knob stops at 1024)
@@ -189,15 +185,10 @@ int cip_solve_block(int Npad) {
 // +0.24 ms per step exposed (196.2 -> 190.3 KKT solves/s); lock-step shards of 8 / 64 problems of order 2048 15.2 -> 16.5 /
 // 78.0 -> 80.5 ms per pass (+28 % flops per factorisation); config 3 3.93 -> 4.0 ms per iteration.  It pays from about six
 // solves per factorisation on: off by default, kept for callers that solve many right-hand sides with one factor.
-static std::atomic<int> g_solve_fused{-1};
-int cip_solve_fused_set(int mode) {
-    if (g_solve_fused.load() < 0) { int v = -1; g_solve_fused.compare_exchange_strong(v, cip_env_int("CIP_SOLVE_FUSED", 0)); }
-    const int prev = g_solve_fused.load();
-    if (mode == 0 || mode == 1 || mode == 2) g_solve_fused.store(mode);
-    return prev;
-}
+static CipKnob g_solve_fused{[] { return cip_env_int("CIP_SOLVE_FUSED", 0); }};
+int cip_solve_fused_set(int mode) { return g_solve_fused.set(mode, [](int v) { return v == 0 || v == 1 || v == 2; }); }
 static int solve_fused_for(int Npad, int Bs) {
-    const int mode = cip_solve_fused_set(-1);
+    const int mode = g_solve_fused.get();
     if (Npad / Bs < 2) return 0;
     return mode == 2 || (mode == 1 && Bs <= 512);
 }
@@ -261,17 +252,19 @@ static int update_rest_of_block(hipStream_t s, double *K, int Npad, long ld, dou
     if (!rest_of_block(K, Npad, ld, Wb, C0, wblk, t, r)) return 0;
     return cip_gemm_rect(s, r.M, r.N, CIP_NB, -1.0, r.A, Npad, r.B, ld, r.C, ld);
 }
-// CIP_FUSE_DIAG=0 / cip_set_ldlt_fused_chain(0): the three-launch chain (diag -> TRSM -> update per panel), the give-up
-// fall-back and the bitwise reference of the fused one; 3 selects the fused chain, any other value only queries
-int cip_ldlt_set_fused_chain(int on) { fuse_env(); const int prev = g_fuse_diag; if (on == 0 || on == 3) g_fuse_diag = on; return prev; }
-
-// did the last factorisation this thread enqueued (or recorded) launch a panel with an in-launch wait? (the give-up hook, below)
-static thread_local bool tl_ran_fused = false;
-
-// one inner-panel sweep of an outer block: [strip update] -> diagonal kernel -> TRSM, for each 128 columns
-static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws, double *Wb, int C0,
+// One inner-panel sweep of an outer block: [strip update] -> diagonal kernel -> TRSM, for each 128 columns, on the chain the plan
+// chose.  The one-launch chain (plan.fused) runs when the chain has the chip to itself -- and in lock-step groups while the group's
+// long-lived workgroups (diagonal kernel, producers, strips: 10 + Npad / 64 per problem at the first panel) are no more
+// than about four rounds of the chip: order 2048, 8 / 16 / 24 problems 19.9 -> 17.8, 28.0 -> 26.5, 37.6 -> 37.1 ms per
+// pass against the three batched launches per panel, 32 problems equal, 64 problems 83 -> 86 (a big batch is
+// throughput-bound and wants the tiles' occupancy).  Residency is a matter of speed, not of progress: a strip waits
+// for its own problem's workgroup 0 only, which was dispatched before it; a workgroup 0 waits for its producers, which
+// follow it in dispatch order and find a CU as soon as any earlier problem's workgroups retire -- and the first
+// problem's always can.
+static int factor_outer_panels(hipStream_t s, double *K, const LdltPlan &plan, long ld, const LdltWorkspace &ws, double *Wb, int C0,
                                int wblk, int t0 = 0, int t1 = -1) {
     int rc;
+    const int Npad = plan.Npad;
     const int T = t1 < 0 ? wblk / CIP_NB : t1;               // panels [t0, T) of the block (all of them by default)
     for (int t = t0; t < T; ++t) {
         const int c0 = C0 + t * CIP_NB;
@@ -281,26 +274,7 @@ static int factor_outer_panels(hipStream_t s, double *K, int Npad, long ld, cons
         // need are produced by one batched launch after the factorisation).  Fused: one launch per panel, which from the second
         // panel of the block on also carries the previous panel's in-block update (diag.hip: k_ldlt_panel).
         GemmArgs gu;
-        fuse_env();
-        // fused when the chain has the chip to itself -- and in lock-step groups while the group's
-        // long-lived workgroups (diagonal kernel, producers, strips: 10 + Npad / 64 per problem at the first panel) are no more
-        // than about four rounds of the chip: order 2048, 8 / 16 / 24 problems 19.9 -> 17.8, 28.0 -> 26.5, 37.6 -> 37.1 ms per
-        // pass against the three batched launches per panel, 32 problems equal, 64 problems 83 -> 86 (a big batch is
-        // throughput-bound and wants the tiles' occupancy).  Residency is a matter of speed, not of progress: a strip waits
-        // for its own problem's workgroup 0 only, which was dispatched before it; a workgroup 0 waits for its producers, which
-        // follow it in dispatch order and find a CU as soon as any earlier problem's workgroups retire -- and the first
-        // problem's always can.
-        static const int lsmax = cip_env_int("CIP_LOCKSTEP_PANEL_MAX", 32);
-        static const int lscus = [] {
-            if (cip_env_set("CIP_LOCKSTEP_PANEL_CUS")) return cip_env_int("CIP_LOCKSTEP_PANEL_CUS", 0);
-            int dev = 0, cus = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            return 4 * cus;
-        }();
-        const bool small_group = cip_in_batch() && cip_tl_bz.B <= lsmax && (long)cip_tl_bz.B * (10 + Npad / 64) <= lscus;
-        const bool fuse = g_fuse_diag && !ws.unfused && (!cip_in_batch() || small_group);
-        if (fuse) {
-            tl_ran_fused = true;
+        if (plan.fused) {
             RestOfBlock rb;
             const bool upd = t > 0 && rest_of_block(K, Npad, ld, Wb, C0, wblk, t - 1, rb);
             // the panel kernel runs the update's tile bodies itself (diag.hip): their parameter block, A .. alpha
@@ -478,12 +452,6 @@ void cip_ldlt_side_destroy(LdltSide *sd) {
     if (sd->s2) (void)hipStreamDestroy(sd->s2);
     delete sd;
 }
-static std::atomic<int> g_side_prep{-1};
-static int side_prep_mode(void) {
-    if (g_side_prep.load() < 0) { int v = -1; g_side_prep.compare_exchange_strong(v, cip_env_int("CIP_SIDE_PREP", 1) != 0); }
-    return g_side_prep.load();
-}
-int cip_ldlt_set_side_prep(int on) { const int prev = side_prep_mode(); if (on == 0 || on == 1) g_side_prep.store(on); return prev; }
 static LdltSide *side_get(const LdltWorkspace &ws) {
     if (!ws.side) return nullptr;
     if (*ws.side) return *ws.side;
@@ -597,63 +565,49 @@ int cip_ldlt_debug_giveup(hipStream_t s, double *K, int Npad, long ld, const Ldl
     }
     return 0;
 }
-bool cip_ldlt_last_factor_fused(void) { return tl_ran_fused; }
-static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws);
-int cip_ldlt_factor(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws) {
-    tl_ran_fused = false;
-    const int rc = ldlt_factor_body(s, K, Npad, ld, ws);
-    if (rc == 0 && !cip_tl_builder) return cip_ldlt_debug_giveup(s, K, Npad, ld, ws, tl_ran_fused);     // (a recording: api.hip fires it on the replay)
-    return rc;
-}
-static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws) {
-    if (Npad % CIP_NB) { cip_set_error("ldlt: N must be a multiple of 128"); return -1; }
+// did the plan of the last factorisation this thread enqueued (or recorded) choose the one-launch chain, whose panels wait inside
+// the launch? (the give-up hook, above; api.hip keeps it with a recorded graph)
+static thread_local bool tl_last_fused = false;
+bool cip_ldlt_last_factor_fused(void) { return tl_last_fused; }
+static int ldlt_factor_body(hipStream_t s, double *K, const LdltPlan &plan, LdltProfile *prof, long ld, const LdltWorkspace &ws) {
+    const int Npad = plan.Npad, Bs = plan.Bs;
     int rc;
     // [0] bad pivot, [1] sweep bail-out, [2] dead pivot, [3] fused-launch wait timed out; from word 16: `ready` counters
     if ((rc = zero_fill(s, ws.info, 64 + 12 * (size_t)(Npad / CIP_NB)))) return rc;
     if ((rc = ensure_x_zeroed(s, Npad, ws))) return rc;
-    const int Bs = ws.Bs;
-    LdltProfile *prof_this = ws.prof ? ws.prof : (cip_tl_builder ? nullptr : g_tl_prof);
-    if (prof_this && (prof_this->nfact++ % prof_this->stride) != 0) prof_this = nullptr;      // a sampled profile skips this factorisation
     LdltSide *sd = nullptr;
     int Jdone = 0;                                           // solve blocks [0, Jdone) are prepared or being prepared on the side stream
     // serial right-looking schedule: panels of the outer block, then ONE trailing update
     for (int C0 = 0, wblk = 0; C0 < Npad; C0 += wblk) {
-        wblk = outer_block_width(Npad, C0);
-        const bool last = C0 + wblk >= Npad;
-        // side preparation only in a wide last block: at least one solve-block boundary strictly inside it or at its start,
-        // and more than one solve block in the matrix
-        if (last && side_prep_mode() && !cip_in_batch() && !cip_tl_builder && Bs > CIP_NB && Npad / Bs >= 2 &&
-            wblk >= 2 * cip_ldlt_outer_block_for(Npad) && wblk > Bs && (sd = side_get(ws))) {
+        wblk = plan.width_at(C0);
+        // the wide last block of a plan that forks solve preparation (no side stream to be had: as every other block)
+        if (C0 == plan.fork_C0 && (sd = side_get(ws))) {
             if ((rc = cip_ldlt_side_join(s, ws, -1))) return rc;      // (a factorisation nobody solved with)
             sd->nfork = 0; sd->waited = 0;
-            fuse_env();
             // panel by panel; from `side_from` columns before the end on, fork whenever the columns of another solve block
             // are final (the first fork takes everything to its left).  The wide block's FIRST panel launches carry ~900
             // update tiles each and fill the chip: side work beside them costs the chain what it saves (same-session A/B,
             // forking from the block's start: 187.5 against 188.7 KKT solves/s); the last ones are a chain on an idle chip.
-            static const int side_from = cip_env_int("CIP_SIDE_PREP_FROM", 2048);
+            // (forks no finer than 1024 columns: with a 512-wide solve block -- order 4608, config 3 -- a fork per block was five
+            //  groups of tiny launches per factorisation, 0.2 ms of side work more than the serial preparation)
             for (int c = C0; c < Npad; ) {
-                // (forks no finer than 1024 columns: with a 512-wide solve block -- order 4608, config 3 -- a fork per block was five
-                //  groups of tiny launches per factorisation, 0.2 ms of side work more than the serial preparation)
-                if (c % (Bs > 1024 ? Bs : 1024) == 0 && Npad - c <= side_from && c / Bs > Jdone) {
-                    if ((rc = side_fork(sd, s, K, Npad, ld, ws, Jdone, c / Bs))) return rc;
-                    Jdone = c / Bs;
+                if (const int J1 = plan.next_fork(c, Jdone)) {
+                    if ((rc = side_fork(sd, s, K, Npad, ld, ws, Jdone, J1))) return rc;
+                    Jdone = J1;
                 }
-                int cend = (c / Bs + 1) * Bs;               // next solve-block boundary
-                if (cend > Npad) cend = Npad;
+                const int cend = (c / Bs + 1) * Bs;         // next solve-block boundary (Bs divides Npad: cip_solve_block)
                 // the panels [c, cend) of the wide block: factor_outer_panels on a sub-range keeps the block's W buffer layout
-                if ((rc = factor_outer_panels(s, K, Npad, ld, ws, ws.Wbuf, C0, wblk, (c - C0) / CIP_NB, (cend - C0) / CIP_NB))) return rc;
+                if ((rc = factor_outer_panels(s, K, plan, ld, ws, ws.Wbuf, C0, wblk, (c - C0) / CIP_NB, (cend - C0) / CIP_NB))) return rc;
                 c = cend;
             }
             continue;                                        // (the last block has no trailing update)
         }
-        if ((rc = factor_outer_panels(s, K, Npad, ld, ws, ws.Wbuf, C0, wblk))) return rc;
+        if ((rc = factor_outer_panels(s, K, plan, ld, ws, ws.Wbuf, C0, wblk))) return rc;
         const int r0 = C0 + wblk;
         if (r0 < Npad) {
             const double *Wr = ws.Wbuf + r0, *Lr = K + r0 + (long)C0 * ld;
             double *Cr = K + r0 + (long)r0 * ld;
             const bool lazy = C0 == 0 && ws.lazyC;        // the trailing matrix is still in Q: read it from there, write K
-            LdltProfile *prof = prof_this;
             if (prof) {
                 if ((rc = prof_event(prof, s))) return rc;
                 const double r = (double)(Npad - r0);
@@ -666,14 +620,28 @@ static int ldlt_factor_body(hipStream_t s, double *K, int Npad, long ld, const L
             if (prof && (rc = prof_event(prof, s))) return rc;
         }
     }
-    if (sd && sd->nfork > 0) {
+    if (const int J1 = sd ? plan.next_fork(Npad, Jdone) : 0) {
         // The LAST group -- the solve blocks whose columns the last panels produced -- runs under the first solve's forward sweep,
         // which waits for it at the last block (cip_ldlt_side_join).  (On the factorisation's own stream it lost: DESIGN_LOG.md,
         // "Experiments removed from the library".)
-        return side_fork(sd, s, K, Npad, ld, ws, Jdone, Npad / Bs);      // joined by the solves (cip_ldlt_side_join)
+        return side_fork(sd, s, K, Npad, ld, ws, Jdone, J1);      // joined by the solves (cip_ldlt_side_join)
     }
     if (ws.no_prep) return 0;
     return build_solve_blocks(s, K, Npad, ld, ws, Jdone, Npad / Bs);
+}
+int cip_ldlt_factor(hipStream_t s, double *K, int Npad, long ld, const LdltWorkspace &ws) {
+    tl_last_fused = false;
+    if (Npad % CIP_NB) { cip_set_error("ldlt: N must be a multiple of 128"); return -1; }
+    // everything this factorisation decides, before its first launch: the schedule ...
+    const LdltPlan plan = ldlt_plan(ldlt_knobs(), LdltCtx{Npad, ws.Bs, cip_in_batch() ? cip_tl_bz.B : 1, cip_tl_builder != nullptr,
+                                                          ws.side != nullptr, ws.unfused != 0});
+    tl_last_fused = plan.fused;
+    // ... and whether its trailing updates are timed (a sampled profile skips factorisations)
+    LdltProfile *prof_this = ws.prof ? ws.prof : (cip_tl_builder ? nullptr : g_tl_prof);
+    if (prof_this && (prof_this->nfact++ % prof_this->stride) != 0) prof_this = nullptr;
+    const int rc = ldlt_factor_body(s, K, plan, prof_this, ld, ws);
+    if (rc == 0 && !cip_tl_builder) return cip_ldlt_debug_giveup(s, K, Npad, ld, ws, plan.fused);     // (a recording: api.hip fires it on the replay)
+    return rc;
 }
 
 // ---------------------------------------------------------------------------

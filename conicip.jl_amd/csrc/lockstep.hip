@@ -390,17 +390,8 @@ static int lockstep_group(int B, int call_count, bool ragged, const cip_problem 
 }
 
 // groups of a large lock-step call that run side by side (see cip_conicip_lockstep); k < 1 only reads; returns the previous value
-static std::atomic<int> g_lockstep_split{-1};
-int cip_lockstep_split_set(int k) {
-    if (g_lockstep_split.load() < 0) {
-        int v = -1, want = cip_env_int("CIP_LOCKSTEP_SPLIT", CIP_LOCKSTEP_SPLIT_DEFAULT);
-        want = want < 1 ? 1 : (want > 8 ? 8 : want);
-        g_lockstep_split.compare_exchange_strong(v, want);
-    }
-    const int prev = g_lockstep_split.load();
-    if (k >= 1 && k <= 8) g_lockstep_split.store(k);
-    return prev;
-}
+static CipKnob g_lockstep_split{[] { const int v = cip_env_int("CIP_LOCKSTEP_SPLIT", CIP_LOCKSTEP_SPLIT_DEFAULT); return v < 1 ? 1 : (v > 8 ? 8 : v); }};
+int cip_lockstep_split_set(int k) { return g_lockstep_split.set(k, [](int v) { return v >= 1 && v <= 8; }); }
 extern "C" int cip_set_lockstep_split(int k) { return cip_lockstep_split_set(k); }
 
 // Problems in, solutions out, in lock-step groups of up to 64.  CIP_E_UNSUPPORTED (nothing written): the problems differ

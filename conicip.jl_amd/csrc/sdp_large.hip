@@ -34,7 +34,6 @@
 #include "cip_gemm_tile.h"
 #include "cip_sdp_numerics.h"
 #include "../../include/cipkkt.h"
-#include <atomic>
 #include <stdio.h>
 #include <string.h>
 #include <thread>
@@ -1455,12 +1454,8 @@ static int lz_reorth(void) {
 // 2 (default; CIP_LG_LANCZOS changes it): the max-step's extreme eigenvalue by k_lg_lanczos1 at orders <= 256 + the inertia certificate
 // (lg_certify); 1: Lanczos alone; 3: certificate self-test; 0: full
 // tridiagonalisation + Sturm multisection at every order (A/B runs, tests).  on < 0 only reads; returns the previous setting
-int cip_sdp_large_lanczos(int on) {
-    static std::atomic<int> mode{[] { const int v = cip_env_int("CIP_LG_LANCZOS", 2); return (v >= 0 && v <= 3) ? v : 2; }()};
-    const int prev = mode.load();
-    if (on >= 0 && on <= 3) mode.store(on);
-    return prev;
-}
+static CipKnob g_lg_lanczos{[] { const int v = cip_env_int("CIP_LG_LANCZOS", 2); return (v >= 0 && v <= 3) ? v : 2; }};
+int cip_sdp_large_lanczos(int on) { return g_lg_lanczos.set(on, [](int v) { return v >= 0 && v <= 3; }); }
 // The two max-steps of a pair (v side, s side: src/ConicIP.jl:708-709, :881-882, :927-928) are independent: side 1 works in the
 // NT scaling's s-side buffers (Ks, its LDL' workspace, Tz / Ts / G as M1 / M2 / M3 -- all idle between scalings) on a second
 // stream.  Orders <= 256 with the Lanczos form only: there each side has its own stat / gate words, certificate pair and fallback dg / of.

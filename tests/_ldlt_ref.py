@@ -487,8 +487,9 @@ def build_case(name, mm=np.matmul):
 
 
 def dispatch(N, chain, nbo, bs_max, fused):
-    """(outer-block widths, solve block, one-launch block steps): the rules of ldlt.hip at their defaults --
-    cip_ldlt_outer_block_for / outer_block_width (automatic: 896 from order 4096 on with the fused chain, else 512; the
+    """(outer-block widths, solve block, one-launch block steps): the rules of ldlt.hip at their defaults, restated
+    independently (tests/test_ldlt_plan.py compares the widths with the library's own plan) --
+    cip_ldlt_plan.h: ldlt_outer_block / width_at (automatic: 896 from order 4096 on with the fused chain, else 512; the
     last block takes what is left once that is at most 2816 columns, automatic widths of 640 and more only),
     cip_solve_block (the largest of 1024 .. 128 within the limit that divides N) and solve_fused_for"""
     width = nbo if nbo else (896 if (N >= 4096 and chain) else 512)
@@ -522,7 +523,7 @@ def handle_order(name):
 
 
 def side_prep_forks(Npad):
-    """does a handle's factorisation of this order prepare solve blocks on the side stream (ldlt.hip: ldlt_factor_body, at the
+    """does a handle's factorisation of this order prepare solve blocks on the side stream (cip_ldlt_plan.h: ldlt_plan, at the
     defaults: fused chain, automatic outer block, solve-block limit 1024)?  The last outer block must be at least two automatic
     widths wide and wider than the solve block, the solve block wider than 128, and there must be two solve blocks."""
     widths, Bs, _ = dispatch(Npad, 3, 0, 1024, 0)

@@ -288,14 +288,15 @@ static Batch pair_of(const Prob &a, const Prob &b) { Batch B; B.P = {a, b}; B.fi
 // A cip_set_solve_fused between two lock-step calls of one shape changes what the handles' LDL' workspace holds (two solve blocks: the
 // pre-multiplied neighbour blocks), hence the slab: every call must size its slabs for the mode it runs under.
 static void knob_sequence(void) {
-    const int pb = cip_set_solve_block_max(128), ps = cip_set_lockstep_split(1), pf = cip_set_solve_fused(-1);
+    const int pb = cip_set_solve_block_max(128), ps = cip_set_lockstep_split(1), pf = cip_set_solve_fused(-1), pc = cip_set_ldlt_fused_chain(-1);
     for (int mode : {0, 2, 0}) {
         cip_set_solve_fused(mode);
+        cip_set_ldlt_outer_block(mode ? 128 : 0); cip_set_ldlt_fused_chain(mode ? 0 : 3);      // the factorisation's plan: a new one per call
         Batch B = pair_of(make(200, 0, {{CIP_CONE_R, 200}}, 1.0), make(200, 0, {{CIP_CONE_R, 200}}, 1.0));
         REQUIRE(lockstep(B, 1) == CIP_OK);
         for (auto &y : B.y) REQUIRE(y[0] != 777.0);
     }
-    cip_set_solve_fused(pf); cip_set_lockstep_split(ps); cip_set_solve_block_max(pb);
+    cip_set_solve_fused(pf); cip_set_lockstep_split(ps); cip_set_solve_block_max(pb); cip_set_ldlt_fused_chain(pc);
 }
 
 // One device allocation per handle (two with a chip-wide S cone, whose workspace keeps its own), none after destruction.

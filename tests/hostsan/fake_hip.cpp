@@ -32,8 +32,12 @@ std::atomic<long> g_launches{0}, g_emulated{0}, g_bytes_live{0};
 thread_local hipError_t tl_last = hipSuccess;
 struct CallCfg { dim3 grid, block; size_t shmem; hipStream_t stream; };
 thread_local std::vector<CallCfg> tl_cfg;
-struct FakeStream { int tag; };
-struct FakeEvent { int tag; };
+struct FakeStream { int tag; int ord; };       // ord: 1, 2, ... in creation order (the null stream is 0)
+struct FakeEvent { int tag; int ord; };
+std::atomic<int> g_streams{0}, g_events{0};
+// opt-in launch trace (fake_hip_trace): one line per launch, event record and stream wait -- names, sizes and ordinals, no pointers
+FILE *g_trace = nullptr;
+int ord(hipStream_t s) { return s ? ((FakeStream *)s)->ord : 0; }
 
 void *dev_alloc(size_t bytes, bool device) {
     void *p = calloc(bytes ? bytes : 1, 1);
@@ -89,7 +93,7 @@ hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *shmem, hip
 }
 
 // ---- launches: no-ops, but the configuration is checked the way the hardware would refuse it, and the two publishing kernels run
-hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t shmem, hipStream_t) {
+hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t shmem, hipStream_t stream) {
     g_launches += 1;
     if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024 ||
         shmem > 160 * 1024 || grid.y > 65535 || grid.z > 65535) {
@@ -102,6 +106,9 @@ hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, s
         auto it = kernels().find(fn);
         if (it == kernels().end()) { fprintf(stderr, "fake_hip: launch of an unregistered kernel\n"); abort(); }
         name = it->second;
+        if (g_trace)
+            fprintf(g_trace, "launch %s grid %u %u %u block %u %u %u lds %zu stream %d\n", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y,
+                    block.z, shmem, ord(stream));
     }
     if (name.find("k_publish_info") != std::string::npos) {              // (const int *info, int *host, int seq)
         const int *info = *(const int **)args[0]; int *host = *(int **)args[1]; const int seq = *(int *)args[2];
@@ -142,16 +149,24 @@ hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDev
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
 hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t a, int) { *v = (a == hipDeviceAttributeMultiprocessorCount) ? 256 : 0; return hipSuccess; }
 hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = -1; return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t) new FakeStream{1}; return hipSuccess; }
-hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = (hipStream_t) new FakeStream{2}; return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t) new FakeStream{1, ++g_streams}; return hipSuccess; }
+hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = (hipStream_t) new FakeStream{2, ++g_streams}; return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { delete (FakeStream *)s; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t) new FakeEvent{1}; return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = (hipEvent_t) new FakeEvent{2}; return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_trace) fprintf(g_trace, "wait stream %d event %d\n", ord(s), ((FakeEvent *)e)->ord);
+    return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t) new FakeEvent{1, ++g_events}; return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = (hipEvent_t) new FakeEvent{2, ++g_events}; return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { delete (FakeEvent *)e; return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_trace) fprintf(g_trace, "record event %d stream %d\n", ((FakeEvent *)e)->ord, ord(s));
+    return hipSuccess;
+}
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.001f; return hipSuccess; }
@@ -171,6 +186,17 @@ void fake_hip_stats(long *launches, long *emulated, long *live_bytes, long *live
     *launches = g_launches.load(); *emulated = g_emulated.load(); *live_bytes = g_bytes_live.load();
     std::lock_guard<std::mutex> lk(g_mu);
     *live_allocs = (long)allocs().size();
+}
+// path: start appending the launch trace to this file; NULL: stop.  `fake_hip_trace_note` puts a line of the driver's into it
+int fake_hip_trace(const char *path) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_trace) fclose(g_trace);
+    g_trace = path ? fopen(path, "a") : nullptr;
+    return path && !g_trace ? -1 : 0;
+}
+void fake_hip_trace_note(const char *text) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_trace) fprintf(g_trace, "# %s\n", text);
 }
 long fake_hip_device_allocs(void) {                 // live hipMalloc'ed blocks alone (pinned host memory not counted)
     std::lock_guard<std::mutex> lk(g_mu);
