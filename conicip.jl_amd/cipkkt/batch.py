@@ -41,6 +41,20 @@ def _solve_on_stream(pr, device):
     return sol
 
 
+def _native_options(kw):
+    """cip_options of a batch's keyword dict (both native batch paths).  `infeasTol` / `refinementThreshold`: absent or None
+    -> -1.0, which the library resolves to its defaults (optTol, optTol / 1e7); every number a caller gives goes through --
+    0.0 too ("never certify" / "always refine")."""
+    from . import _lib as L
+
+    def given(key):
+        x = kw.get(key)
+        return -1.0 if x is None else float(x)
+
+    return L.CipOptions(kw.get("optTol", 1e-6), kw.get("DTB", 0.01), given("infeasTol"), given("refinementThreshold"),
+                        kw.get("maxRefinementSteps", 3), kw.get("maxIters", 100), 0)
+
+
 def _solve_many_native(prs, device, in_flight, sparse_q=False):
     """All problems of this rank through `cip_conicip_many` (csrc/batch.hip): one handle + HIP stream per problem,
     `in_flight` native interior-point loops at once on the library's own host threads (no Python in the loop)."""
@@ -50,9 +64,7 @@ def _solve_many_native(prs, device, in_flight, sparse_q=False):
     from .kkt import KKTSystem
     lib = L.load()
     kw = prs[0].get("kwargs", {})
-    opt = L.CipOptions(kw.get("optTol", 1e-6), kw.get("DTB", 0.01), kw.get("infeasTol", -1.0) or -1.0,
-                       kw.get("refinementThreshold", -1.0) or -1.0, kw.get("maxRefinementSteps", 3),
-                       kw.get("maxIters", 100), 0)
+    opt = _native_options(kw)
     systems, streams, keep = [], [], []
     try:
         for pr in prs:
@@ -123,9 +135,7 @@ def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, 
     from .kkt import make_problem
     lib = L.load()
     kw = prs[0].get("kwargs", {})
-    opt = L.CipOptions(kw.get("optTol", 1e-6), kw.get("DTB", 0.01), kw.get("infeasTol", -1.0) or -1.0,
-                       kw.get("refinementThreshold", -1.0) or -1.0, kw.get("maxRefinementSteps", 3),
-                       kw.get("maxIters", 100), 0)
+    opt = _native_options(kw)
     k = len(prs)
     keep = []
     structs = (L.CipProblem * k)()

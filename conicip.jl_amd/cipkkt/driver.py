@@ -39,6 +39,7 @@ class Solution:
     n_solve: int = 0
     wall_s: float = 0.0
     trace: list = field(default_factory=list)
+    refine_rnorms: list = field(default_factory=list)      # driver="python" only: per iteration, every residual the refinement loop tested
 
 
 def _jlmax(*xs):
@@ -50,6 +51,15 @@ def _jlmax(*xs):
 
 def _nrm(x2):
     return math.sqrt(x2) if x2 >= 0 else math.nan
+
+
+def _norm_seq(x):
+    """2-norm as the native loop forms it on the host (csrc/cip_driver.h: host_norms): one running sum of squares in index order.
+    numpy's norm sums in another order and differs in the last bits, which showed in rDu / rPr / rCp once |c| >> 1."""
+    s = 0.0
+    for v in x.tolist():
+        s += v * v
+    return math.sqrt(s)
 
 
 def solution_from_result(res, y, w, v, trace=None):
@@ -163,9 +173,9 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
     c_d = torch.as_tensor(c_h, **f64)
     b_d = torch.as_tensor(b_h, **f64)
     d_d = torch.as_tensor(d_h, **f64)
-    normc = float(np.linalg.norm(c_h))
-    normd = -math.inf if p == 0 else float(np.linalg.norm(d_h))
-    normb = float(np.linalg.norm(b_h)) if m > 0 else 0.0
+    normc = _norm_seq(c_h)
+    normd = -math.inf if p == 0 else _norm_seq(d_h)
+    normb = _norm_seq(b_h) if m > 0 else 0.0
 
     # conedim (:547-552) and e (:559-565)
     conedim = 0
@@ -386,6 +396,7 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
         solve4x4(lam, r, dz)
         dzy, dzw, dzv, dzs = parts(dz)
         rky, rkw, rkv, rks = parts(rkkt)
+        sol.refine_rnorms.append([])
         for _ in range(maxRefinementSteps):
             kkt_apply(dz, rkkt)
             if m > 0:
@@ -402,6 +413,7 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
                          ([(iy, iy), (iv, iv), (is_, is_)] if m > 0 else
                           ([(iy, iy), (iw, iw)] if p > 0 else [(iy, iy)])))
             rnorm = sum(_nrm(x) for x in n2) / (n + 2 * m)                 # :917 (norm(v4x1) :61)
+            sol.refine_rnorms[-1].append(rnorm)
             if rnorm < refinementThreshold:
                 break
             solve4x4(lam, rIr, dzr)

@@ -323,12 +323,14 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
 
         # newton step + refinement :907-921
         dz = solve(r)
+        sol.trace[-1]["rnorm"] = []                           # oracle-only: every refinement residual this iteration tests
         for rStep in range(1, maxRefinementSteps + 1):
             pb1 = cone_prod(lam, F.mul(dz.v))
             pb2 = cone_prod(lam, FinvT.mul(dz.s))
             rkkt = V4(Q @ dz.y + GT @ dz.w - AT @ dz.v, G @ dz.y, A @ dz.y - dz.s, pb1 + pb2)
             rIr = r - rkkt
             rnorm = rIr.norm() / (n + 2 * m)
+            sol.trace[-1]["rnorm"].append(float(rnorm))
             if rnorm < refinementThreshold:
                 break
             dzr = solve(rIr)

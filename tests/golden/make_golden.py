@@ -113,7 +113,7 @@ def main():
         sol = conicIP(Q, c, A, b, K, G, d, optTol=1e-7, DTB=0.01, maxRefinementSteps=3)
         traj[name] = dict(status=sol.status, Iter=sol.Iter, n_factor=sol.n_factor, n_solve=sol.n_solve,
                           y=sol.y.tolist(), w=sol.w.tolist(), v=sol.v.tolist(),
-                          trace=[{k: float(v) for k, v in t.items()} for t in sol.trace])
+                          trace=[{k: float(v) for k, v in t.items() if k != "rnorm"} for t in sol.trace])
     json.dump(traj, open(os.path.join(HERE, "oracle_trajectories.json"), "w"), indent=1)
     print("wrote primitives.json, reference_pins.json, oracle_trajectories.json")
 
