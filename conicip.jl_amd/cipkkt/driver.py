@@ -54,7 +54,7 @@ def _nrm(x2):
 
 
 def _norm_seq(x):
-    """2-norm as the native loop forms it on the host (csrc/cip_driver.h: host_norms): one running sum of squares in index order.
+    """2-norm as the native loop forms it on the host (csrc/cip_driver_scalars.h: host_norms): one running sum of squares in index order.
     numpy's norm sums in another order and differs in the last bits, which showed in rDu / rPr / rCp once |c| >> 1."""
     s = 0.0
     for v in x.tolist():
@@ -339,7 +339,7 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
                 p_unscaled = _nrm(pinf2)                                   # :810
                 den = _nrm(yy) + (_nrm(vv) if m > 0 else 0.0)
                 p_cvx = p_unscaled / den if den != 0 else math.inf         # :811
-                p_ecos = p_unscaled / (max(1, normc) * abs(dTy_bTv))       # :812
+                p_ecos = p_unscaled / (_jlmax(1.0, normc) * abs(dTy_bTv))       # :812
                 p_infeas = _jlmax(p_cvx, p_ecos)
             else:
                 p_infeas = math.nan
@@ -353,7 +353,7 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
             d2 = -math.inf if p == 0 else _nrm(gy2)                        # :840
             d3 = _nrm(qy2)                                                 # :841
             if cTy > 0:
-                d_cvx = _jlmax(d1 / max(1, normb), d2 / max(1, normd), d3 / max(1, normc)) / abs(cTy)   # :843
+                d_cvx = _jlmax(d1 / _jlmax(1.0, normb), d2 / _jlmax(1.0, normd), d3 / _jlmax(1.0, normc)) / abs(cTy)   # :843
                 ny = _nrm(yy)
                 d_ecos = _jlmax(d1, d2, d3) / ny if ny != 0 else math.inf                             # :844
                 d_infeas = abs(_jlmax(d_cvx, d_ecos))

@@ -148,6 +148,94 @@ def make_cone_ops(cone_dims):
     return maxstep, nt_scaling, cone_div, cone_prod
 
 
+def _nrm(x2):
+    """the norm out of its square as the loop's scalar logic takes it: NaN for a negative (or NaN) square"""
+    return float(np.sqrt(x2)) if x2 >= 0 else np.nan
+
+
+def _jldiv(a, b):
+    """Julia's float division: x / 0 is +-Inf, 0 / 0 is NaN, no exception"""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+@dataclass
+class Verdict:
+    """what one pass through src/ConicIP.jl:756-873 decides"""
+    status: str                  # "None": keep iterating
+    scale: float                 # Infeasible: (w, v) / scale, y = NaN ; Unbounded: y / scale, (w, v) = NaN ; else NaN
+    mu: float
+    rDu: float
+    rPr: float
+    rCp: float
+    pobj: float
+    dobj: float
+    improved: bool               # this iterate is the best so far (:768): the caller records Iter, mu, rDu, rPr, rCp
+    optBest: float               # the running best after this iteration
+    p_infeas: float = np.nan
+    d_infeas: float = np.nan
+
+
+def evaluate_iteration(dots, normc, normb, normd, conedim, m, p, optTol, infeasTol, Iter, optBest):
+    """src/ConicIP.jl:756-873 on scalars alone: residuals, best-iterate test, objective values and the stopping verdicts in the
+    reference's order -- :Optimal is noted (:786), the primal certificate is tested (:815), then the dual one (:847), then a
+    noted :Optimal is acted upon (:867), then :Error (:870).  `dots`: the 16 dot products in the order of IterDots
+    (csrc/cip_driver_scalars.h); a norm is the square root of its square, NaN where the square is negative or NaN.
+    sol.y aliases the iterate (:726), so an :Infeasible verdict NaN-fills z.y and every quantity of the dual test after it is
+    NaN: the verdict stands, and the function returns there."""
+    (mubar, cTy, r0y2, r0v2, r0s2, yQy, wr0w, vr0v, dTw, bTv, pinf2, yy, vv, ays2, gy2, qy2) = (float(x) for x in dots)
+    with np.errstate(all="ignore"):
+        mu = _jldiv(mubar, conedim) if conedim > 0 else np.nan    # :756-757 (Julia: 0.0/0 = NaN, no exception)
+        rDu = _nrm(r0y2) / (1 + normc)                            # :764
+        rPr = (_nrm(r0v2) if m > 0 else 0.0) / (1 + normb)        # :765 (normsafe)
+        rCp = (_nrm(r0s2) if m > 0 else 0.0) / (1 + abs(cTy))     # :766
+        worst = _jlmax(_jlmax(rDu, rPr), rCp)
+        improved = bool(worst < optBest)                          # :768-773
+        if improved:
+            optBest = worst
+        pobj = 0.5 * yQy - cTy                                    # :775
+        dobj = pobj + wr0w + vr0v - mubar                         # :776
+        vd = Verdict("None", np.nan, mu, rDu, rPr, rCp, pobj, dobj, improved, optBest)
+
+        status = "Optimal" if worst < optTol else "None"          # :786
+        if not (p == 0 and m == 0):                               # :790
+            dTy_bTv = dTw - bTv                                   # :808
+            if dTy_bTv < 0:
+                p_unscaled = _nrm(pinf2)                          # :810
+                p_cvx = _jldiv(p_unscaled, _nrm(yy) + (_nrm(vv) if m > 0 else 0.0))      # :811
+                p_ecos = _jldiv(p_unscaled, _jlmax(1.0, normc) * abs(dTy_bTv))                # :812
+                vd.p_infeas = _jlmax(p_cvx, p_ecos)
+            if vd.p_infeas < infeasTol:                           # :815-818
+                vd.status, vd.scale = "Infeasible", -dTy_bTv
+                return vd
+            d1 = -np.inf if m == 0 else _nrm(ays2)                # :839
+            d2 = -np.inf if p == 0 else _nrm(gy2)                 # :840
+            d3 = _nrm(qy2)                                        # :841
+            if cTy > 0:
+                d_cvx = _jldiv(_jlmax(_jlmax(_jldiv(d1, _jlmax(1.0, normb)), _jldiv(d2, _jlmax(1.0, normd))),
+                                      _jldiv(d3, _jlmax(1.0, normc))), abs(cTy))              # :843
+                d_ecos = _jldiv(_jlmax(_jlmax(d1, d2), d3), _nrm(yy))                    # :844
+                vd.d_infeas = abs(_jlmax(d_cvx, d_ecos))
+            if vd.d_infeas < infeasTol:                           # :847-850
+                vd.status, vd.scale = "Unbounded", abs(cTy)
+                return vd
+        if status != "None":                                      # :867
+            vd.status = status
+        elif not np.all(np.isfinite([mu, rDu, rPr, rCp])):        # :870-873
+            vd.status = "Error"
+    return vd
+
+
+def apply_certificate(status, scale, y, w, v):
+    """what a verdict does to the returned iterate (:816, :848); every other status returns it as it is"""
+    with np.errstate(all="ignore"):
+        if status == "Infeasible":
+            return np.full(len(y), np.nan), w / scale, v / scale
+        if status == "Unbounded":
+            return y / scale, np.full(len(w), np.nan), np.full(len(v), np.nan)
+    return y, w, v
+
+
 def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
             kktsolver=kktsolver_qr,
             optTol=1e-6, DTB=0.01, verbose=False,
@@ -234,76 +322,27 @@ def conicIP(Q, c, A, b, cone_dims, G=None, d=None, *,
         rleft = V4(Qy + GT @ z.w - AT @ z.v, G @ z.y, A @ z.y - z.s, lamlam)   # :747-750
         r0 = V4(rleft.y - c, rleft.w - d, rleft.v - b, rleft.s)               # :753
 
-        mubar = float(np.dot(z.v, z.s))                       # :756
-        mu = mubar / conedim if conedim > 0 else np.nan      # :757 (Julia: 0.0/0 = NaN, no exception)
+        # the scalars of :756-873: 16 dot products (the order of csrc/cip_driver_scalars.h: IterDots); every norm the block
+        # takes is the square root of one of them (numpy's 2-norm of a vector is sqrt(dot(x, x)), bit for bit)
+        pinf = GT @ z.w - AT @ z.v                            # :810
+        sq = lambda x: float(np.dot(x, x))
+        dots = (float(np.dot(z.v, z.s)), float(np.dot(c, z.y)), sq(r0.y), sq(r0.v), sq(r0.s), float(np.dot(z.y, Qy)),
+                float(np.dot(z.w, r0.w)), float(np.dot(z.v, r0.v)), float(np.dot(d, z.w)), float(np.dot(b, z.v)), sq(pinf),
+                sq(z.y), sq(z.v), sq(rleft.v), sq(rleft.w),                 # A y - s (:839), G y (:840)
+                sq(Qy) if np.all(np.isfinite(z.y)) else np.nan)                  # :841
+        vd = evaluate_iteration(dots, normc, normb, normd, conedim, m, p, optTol, infeasTol, Iter, optBest)
+        optBest = vd.optBest
+        if vd.improved:                                       # :768-773
+            sol.Iter, sol.Mu = Iter, vd.mu
+            sol.duFeas, sol.prFeas, sol.muFeas = vd.rDu, vd.rPr, vd.rCp
+        sol.pobj, sol.dobj = vd.pobj, vd.dobj
+        sol.trace.append(dict(Iter=Iter, mu=vd.mu, rDu=vd.rDu, rPr=vd.rPr, rCp=vd.rCp, pobj=vd.pobj, dobj=vd.dobj))
+        mu, mubar = vd.mu, dots[0]
 
-        cTy = float(np.dot(c, z.y))                           # :763
-        rDu = float(np.linalg.norm(r0.y)) / (1 + normc)       # :764
-        rPr = _normsafe(r0.v) / (1 + normb)                   # :765
-        rCp = _normsafe(r0.s) / (1 + abs(cTy))                # :766
-
-        if max(rDu, rPr, rCp) < optBest:                      # :768-773
-            sol.Iter = Iter
-            sol.Mu = mu
-            sol.duFeas, sol.prFeas, sol.muFeas = rDu, rPr, rCp
-            optBest = max(rDu, rPr, rCp)
-
-        pobj = 0.5 * float(np.dot(z.y, Qy)) - cTy             # :775
-        dobj = pobj + float(np.dot(z.w, r0.w)) + float(np.dot(z.v, r0.v)) - mubar   # :776
-        sol.pobj, sol.dobj = pobj, dobj
-        sol.trace.append(dict(Iter=Iter, mu=mu, rDu=rDu, rPr=rPr, rCp=rCp,
-                              pobj=pobj, dobj=dobj))
-
-        if max(rDu, rPr, rCp) < optTol:                       # :786
-            sol.status = "Optimal"
-
-        if not (p == 0 and m == 0):                           # :790
-            dTy_bTv = float(np.dot(d, z.w)) - float(np.dot(b, z.v))           # :808
-            p_unscaled = float(np.linalg.norm(GT @ z.w - AT @ z.v))           # :810
-            if dTy_bTv < 0:
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    p_cvx = p_unscaled / (_normsafe(z.y) + _normsafe(z.v))    # :811
-                    p_ecos = p_unscaled / (max(1, normc) * abs(dTy_bTv))      # :812
-                p_infeas = _jlmax(p_cvx, p_ecos)
-            else:
-                p_infeas = np.nan
-            if p_infeas < infeasTol:                          # :815-818
-                sol.y = np.full(n, np.nan)
-                sol.w = z.w / -dTy_bTv
-                sol.v = z.v / -dTy_bTv
-                sol.status = "Infeasible"
-
-            if sol.status == "Infeasible":
-                # the reference NaN-fills sol.y, which aliases z.y (:726,:816): every
-                # quantity of the dual-infeasibility test below is then NaN -> skipped
-                sol.n_factor, sol.n_solve = counts["factor"], counts["solve"]
-                return sol
-            d1 = -np.inf if m == 0 or n == 0 else float(np.linalg.norm(A @ z.y - z.s))   # :839
-            d2 = -np.inf if p == 0 or n == 0 else float(np.linalg.norm(G @ z.y))         # :840
-            d3 = float(np.linalg.norm(Qy)) if np.all(np.isfinite(z.y)) else np.nan       # :841
-            if cTy > 0:
-                d_cvx = _jlmax(_jlmax(d1 / max(1, normb), d2 / max(1, normd)),
-                               d3 / max(1, normc)) / abs(cTy)                                 # :843
-                d_ecos = _jlmax(_jlmax(d1, d2), d3) / float(np.linalg.norm(z.y))              # :844
-                d_infeas = abs(_jlmax(d_cvx, d_ecos))
-            else:
-                d_infeas = np.nan
-            if d_infeas < infeasTol:                          # :847-850
-                sol.y = z.y / abs(cTy)
-                sol.v = np.full(m, np.nan)
-                sol.w = np.full(p, np.nan)
-                sol.status = "Unbounded"
-
-        if sol.status != "None":                              # :867
+        if vd.status != "None":                               # :815-818, :847-850, :867, :870-873
+            sol.status = vd.status
             sol.n_factor, sol.n_solve = counts["factor"], counts["solve"]
-            if sol.status == "Optimal":
-                sol.y, sol.w, sol.v = z.y, z.w, z.v
-            return sol
-
-        if not np.all(np.isfinite([mu, rDu, rPr, rCp])):      # :870-873
-            sol.status = "Error"
-            sol.n_factor, sol.n_solve = counts["factor"], counts["solve"]
-            sol.y, sol.w, sol.v = z.y, z.w, z.v
+            sol.y, sol.w, sol.v = apply_certificate(vd.status, vd.scale, z.y, z.w, z.v)
             return sol
 
         # predictor :879-887

@@ -77,21 +77,38 @@ def test_dense_qps_finishing_at_different_iterations():
 
 
 def test_statuses_differ_inside_one_group():
-    """feasible, infeasible and unbounded problems of one shape in one group"""
+    """feasible and infeasible problems of one shape in one group at the default options; then the same six with an unbounded
+    and an abandoned member behind them under the group options of tests/_stop_cases.py (every Newton step refined, maxIters = 9),
+    where one member of every end state is also compared with the oracle"""
+    import _stop_cases as SC
     n = 10
     prs = []
     for seed in range(3):
         prs.append(_as_problem(P.infeasible_box(n, seed)))                       # y >= 1 and y <= -1
-    rng = np.random.default_rng(3)
-    for _ in range(3):                                                           # same shape, feasible: -5 <= y <= 5
-        h = rng.standard_normal(n)
-        H = np.outer(h, h) + 0.1 * np.eye(n)
-        A = sp.vstack([sp.identity(n), -sp.identity(n)]).tocsr()
-        prs.append(dict(Q=H, c=rng.standard_normal(n), A=A, b=-5 * np.ones(2 * n), cone_dims=[("R", 2 * n)], G=None, d=None, kwargs={}))
+    for box in SC.lockstep_boxes(n):                                             # same shape, feasible: -5 <= y <= 5
+        prs.append(_as_problem(box))
     one = _solve(prs, "threads", in_flight=1)
     lock = _solve(prs, "lockstep")
     assert {s.status for s in one} == {"Infeasible", "Optimal"}
     _assert_identical(lock, one)
+
+    prs += SC.group_tail()
+    for pr in prs:
+        pr["kwargs"] = dict(SC.GROUP_OPTS)
+    one = _solve(prs, "threads", in_flight=1)
+    lock = _solve(prs, "lockstep")
+    assert {s.status for s in one[:6]} == {"Infeasible", "Optimal"}
+    assert [s.status for s in one[6:]] == ["Unbounded", "Abandoned"]
+    _assert_identical(lock, one)                                                 # certificates included: y, w, v bit for bit
+    # one member of every end state against the oracle, and its certificate against what a certificate must satisfy
+    for i, name in SC.GROUP_MEMBERS.items():
+        for got, how in ((lock[i], "lock-step"), (one[i], "alone")):
+            SC.assert_matches_oracle(got, name, how, trace=False)
+            if got.status in ("Infeasible", "Unbounded"):
+                SC.assert_certificate(got, name, how)
+    # the members do not stop together: the oracle's iteration counts (n_factor - 1) differ, and the device's are the oracle's
+    stops = [SC.oracle_run(name).n_factor - 1 for name in SC.GROUP_MEMBERS.values()]
+    assert len(set(stops)) == len(stops) and [lock[i].n_factor - 1 for i in SC.GROUP_MEMBERS] == stops
 
 
 def test_problems_that_need_the_regularised_factorisation_leave_the_group():
