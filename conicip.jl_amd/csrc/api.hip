@@ -716,25 +716,31 @@ __global__ void k_publish_info(const int *info, int *host, int seq) {
         __hip_atomic_store(host + 4, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-// has the flag read-back of factorisation `info_seq` landed?  wait: spin (the stream is polled too: a failed launch must not hang the host)
-static int info_landed(cip_handle *h, bool wait, bool *landed) {
-    volatile int *seqp = h->info_host + 4;
-    *landed = __atomic_load_n(seqp, __ATOMIC_ACQUIRE) == h->info_seq;
-    if (*landed || !wait) return 0;
-    for (long spin = 0;; ++spin) {
-        if (__atomic_load_n(seqp, __ATOMIC_ACQUIRE) == h->info_seq) { *landed = true; return 0; }
-        if ((spin & 0xfff) == 0xfff) {
-            std::this_thread::yield();
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipSuccess) {                                   // everything enqueued has run: the word must be there
-                *landed = __atomic_load_n(seqp, __ATOMIC_ACQUIRE) == h->info_seq;
-                if (*landed) return 0;
-                cip_set_error("LDL': the pivot flags of factorisation %d never arrived", h->info_seq);
-                return CIP_E_HIP;
-            }
-            if (q != hipErrorNotReady) { cip_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return CIP_E_HIP; }
+// The host's side of such a word (this kernel's, and k_lg_pubflag's of sdp_large_nt.hip): spin until it equals `seq`, yielding every
+// 4096 polls and looking at the stream once then -- a failed launch must not hang the host.
+int cip_await_seq(hipStream_t s, const volatile int *word, int seq, const char *what) {
+    for (long spin = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != seq; ++spin) {
+        if ((spin & 0xfff) != 0xfff) continue;
+        std::this_thread::yield();
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipSuccess) {                                       // everything enqueued has run: the word must be there
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return 0;
+            cip_set_error("%s never arrived", what);
+            return CIP_E_HIP;
         }
+        if (q != hipErrorNotReady) { cip_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return CIP_E_HIP; }
     }
+    return 0;
+}
+// has the flag read-back of factorisation `info_seq` landed?  wait: until it has
+static int info_landed(cip_handle *h, bool wait, bool *landed) {
+    *landed = __atomic_load_n((volatile int *)h->info_host + 4, __ATOMIC_ACQUIRE) == h->info_seq;
+    if (*landed || !wait) return 0;
+    char what[64];
+    snprintf(what, sizeof(what), "LDL': the pivot flags of factorisation %d", h->info_seq);
+    CIP_TRY(cip_await_seq(h->stream, h->info_host + 4, h->info_seq, what));
+    *landed = true;
+    return 0;
 }
 // assembly + LDL' + an asynchronous read-back of the pivot flag into pinned host memory; nothing here waits for the GPU
 static int factor_enqueue(cip_handle *h) {

@@ -28,6 +28,11 @@ void cip_set_error(const char *fmt, ...);
         if (rc__) return rc__;                                                    \
     } while (0)
 
+// Waits until the word that a publishing kernel stores last, with system-scope release, into host-mapped memory equals `seq`
+// (api.hip).  0: it does; CIP_E_HIP with the error set: hipStreamQuery failed, or the stream is idle and the word still old --
+// "<what> never arrived".
+int cip_await_seq(hipStream_t s, const volatile int *word, int seq, const char *what);
+
 // ---------------------------------------------------------------- device workspaces: one walk sizes and carves
 // The layout of a workspace is ONE function that takes its members from a CipLayout, in order.  Over the allocation the walk carves;
 // over a null base take() returns null and only counts, and bytes() is what to allocate -- sizing and carve cannot disagree.  An offset
@@ -230,7 +235,7 @@ struct LdltWorkspace {        // carved out of one device allocation
     // solve preparation beside the panel chain of the last (wide) outer block (ldlt.hip: cip_ldlt_factor): where the owner
     // keeps the side stream / events, created on first use (NULL: always behind the factorisation, on its own stream)
     struct LdltSide **side;
-    int no_prep;              // 1: the factor only (no block inverses for solves) -- inertia checks (sdp_large.hip)
+    int no_prep;              // 1: the factor only (no block inverses for solves) -- inertia checks (sdp_large_eig.hip)
     int unfused;              // 1: three launches per panel whatever the process-wide chain form (no in-launch wait: set after one gave up, api.hip)
 };
 struct LdltSide;
@@ -330,7 +335,7 @@ int cip_sdp_large_refresh(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li,
 int cip_sdp_large_apply(hipStream_t s, LargeWs *w, const ConeDesc &cd, int li, int mode, const double *x, double *out);
 int cip_sdp_large_prod(hipStream_t s, LargeWs *w, const ConeDesc &cd, const double *x, const double *y, double *out);
 int cip_sdp_large_div(hipStream_t s, LargeWs *w, const ConeDesc &cd, const double *x, const double *y, double *out, int *flag);
-int cip_sdp_large_lanczos(int on);                  // sdp_large.hip: max-step eigenvalue by Lanczos (1), Lanczos + inertia certificate (2), tridiagonalisation (0); < 0 reads; returns the previous setting
+int cip_sdp_large_lanczos(int on);                  // sdp_large_eig.hip: max-step eigenvalue by Lanczos (1), Lanczos + inertia certificate (2), tridiagonalisation (0); < 0 reads; returns the previous setting
 int cip_sdp_large_cert_stats(hipStream_t s, struct LargeWs *w, int *out2);     // {certificates failed -> fallbacks taken, 0}
 int cip_sdp_large_maxstep(hipStream_t s, LargeWs *w, const ConeDesc &cd, const double *x, const double *d, double scale,
                           double *partial, int side = 0);

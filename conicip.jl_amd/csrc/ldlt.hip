@@ -130,7 +130,7 @@ int cip_ldlt_profile_thread_collect(double *launches, double *ms, double *flops)
 
 // The same event-pair timing for other dominant kernels of the secondary configurations, per calling thread (bench.py's
 // `secondary` object: cip_conicip runs on the caller's thread): slot 1 = Schur formation (assemble.hip, dense A), slot 2 = the
-// one-sided Jacobi of a large S cone's NT scaling (sdp_large.hip).  Slot 0 is the trailing update's thread profile above.
+// one-sided Jacobi of a large S cone's NT scaling (sdp_large_nt.hip).  Slot 0 is the trailing update's thread profile above.
 static thread_local LdltProfile *g_tl_aux[CIP_PROF_SLOTS] = {nullptr, nullptr, nullptr};
 int cip_prof_slot_enable(int slot, int enabled) {
     if (slot == 0) return cip_ldlt_profile_thread(enabled);

@@ -413,7 +413,8 @@ int cip_set_ldlt_side_prep(int on);
  * itself (also CIP_LAZY_COPY=0).  Same factor bit for bit.  1 (default) on, 0 off; returns the previous setting. */
 int cip_set_lazy_copy(int on);
 /* S cones of order 133..256: the max-step's extreme eigenvalue (the reference's eigmin / eigmax, src/ConicIP.jl:272-303) by
-   Lanczos with full reorthogonalisation (1) or by a full tridiagonalisation + Sturm multisection (0); < 0 only
+   Lanczos (1: the plain three-term recurrence, stopped at the first convergence of the extreme Ritz value; CIP_LG_LANCZOS_REORTH=1
+   adds full reorthogonalisation, the form until round 6) or by a full tridiagonalisation + Sturm multisection (0); < 0 only
    reads.  Returns the previous setting.  Same eigenvalue to ~1e-11 relative either way; for A/B runs and tests.
    2 (DEFAULT): Lanczos + INERTIA CERTIFICATE -- a Krylov method started from a fixed vector can in principle settle on an interior
    eigenvalue (no component along the extreme eigenvector); mode 2 checks with an LDL' of theta' I - A (theta' = theta + 1e-9 |T|)

@@ -7,7 +7,7 @@
 // runs, so nothing a kernel would have overwritten may survive in a recycled arena), pinned host memory is ordinary memory, copies
 // are memmove, streams are in order and synchronous, events are always complete, and a kernel launch is a NO-OP --
 // except the two one-wave kernels whose only job is to hand a word to a polling host (k_publish_info of api.hip, k_lg_pubflag of
-// sdp_large.hip), which are emulated so that the host's polls end the way they do on the GPU.  With every "device" result zero the
+// sdp_large_nt.hip), which are emulated so that the host's polls end the way they do on the GPU.  With every "device" result zero the
 // interior-point loop sees zero residuals and stops at its first convergence test: what runs under the sanitizers is the control
 // plane, not the arithmetic (tests/hostsan/drive.cpp says what is driven through it).
 //

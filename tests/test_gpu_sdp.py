@@ -177,7 +177,7 @@ def test_mixed_rqs_problem():
 @pytest.mark.parametrize("r", [133, 200, 256])
 def test_lanczos_maxstep_against_lapack_on_hard_spectra(r):
     """Round 3: at orders 133..256 the max-step takes its ONE eigenvalue from Lanczos with full reorthogonalisation
-    (sdp_large.hip: k_lg_lanczos1) instead of a full tridiagonalisation.  Spectra chosen against it: a tight cluster at the
+    (sdp_large_eig.hip: k_lg_lanczos1) instead of a full tridiagonalisation.  Spectra chosen against it: a tight cluster at the
     wanted end, a dense edge (semicircle: the slowest case, close to a complete tridiagonalisation), an exactly repeated extreme
     eigenvalue, one isolated outlier, a multiple of the identity (breakdown at the first step), a rank-one perturbation of it;
     a negative definite and a zero direction (no bound: Inf);
@@ -241,7 +241,7 @@ def test_lanczos_maxstep_against_lapack_on_hard_spectra(r):
 def test_lanczos_inertia_certificate_catches_a_start_vector_without_the_extreme_direction(r):
     """the Lanczos max-step starts from a FIXED vector v1; a direction whose extreme eigenvector is orthogonal to v1 is
     invisible to the recurrence (until rounding brings it in), and the stop test -- a converged Ritz pair -- passes on the second
-    eigenvalue.  Such a direction is built here (v1 is cos(0.7 i + 0.3) + 1 / (1 + i), sdp_large.hip: k_lg_lanczos1): top eigenvalue
+    eigenvalue.  Such a direction is built here (v1 is cos(0.7 i + 0.3) + 1 / (1 + i), sdp_large_eig.hip: k_lg_lanczos1): top eigenvalue
     2.05 along u orthogonal to v1, 2.0 next, the rest in [0.2, 1].  Mode 2 (cip_set_sdp_lanczos(2)) must return LAPACK's answer,
     through the certificate's fallback when plain Lanczos is fooled; mode 1's answer is recorded, not asserted (rounding may or may
     not rescue it -- that is the point of the certificate)."""
@@ -355,7 +355,7 @@ def test_warm_start_of_the_jacobi_is_not_taken_from_a_scaling_that_left_the_cone
     """Round-5 advisor finding: cip_set_scaling_from_iterate on an iterate OUTSIDE the cone (a Cholesky pivot <= 0) left NaN in the
     stored right singular vectors, and the next scaling of a perfectly interior iterate on the same handle was warm-started from
     them: NaN out, clean flag.  Now the warm start is dropped on the host when the Cholesky flags are raised and gated on the device
-    (clean flags, finite positive singular values, |V'V - I| <= 1e-6: sdp_large.hip k_lg_warm_gate): the scaling behind a flagged one
+    (clean flags, finite positive singular values, |V'V - I| <= 1e-6: sdp_large_nt.hip k_lg_warm_gate): the scaling behind a flagged one
     has exactly the bits of a cold run on a fresh handle -- src/ConicIP.jl:196-210."""
     import cipkkt
     r = 150

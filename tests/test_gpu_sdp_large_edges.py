@@ -1,11 +1,13 @@
-"""The large S-cone kernels (csrc/sdp_large.hip) above padded order 256 at hard iterates, against the extended-precision
-references and error bounds of tests/_cone_ref.py.
+"""The large S-cone kernels (csrc/sdp_large.hip, sdp_large_nt.hip, sdp_large_eig.hip) above padded order 256 at hard iterates,
+against the extended-precision references and error bounds of tests/_cone_ref.py.
 
-tests/test_gpu_cone_edges.py stops at order 200, which is padded order rp = 256.  sdp_large.hip compiles one form of
+tests/test_gpu_cone_edges.py stops at order 200, which is padded order rp = 256.  The large path has one form of
 almost everything per rp in {256, 512, 1024, 2048}; the cases here reach the other three, the two tridiagonalisations
 behind the max step above order 256 with the slab sizes of the cooperative one, the batched-64 GEMM path that replaces
 k_gemm_nt_small above rp = 256, and a handle with two large cones of different order (the smaller one padded for its
-neighbour, per-cone slots of different order).  test_case_table_reaches_the_named_paths restates the dispatch rules.
+neighbour, per-cone slots of different order).  test_case_table_reaches_the_named_paths holds the table against the
+restatement of the dispatch rules in tests/_sdp_large_forms.py, which tests/test_sdp_large_forms.py holds against
+csrc/cip_sdp_large_forms.h.
 
 Iterates and device calls are those of test_s_cone_ops_at_the_edges: CR.s_point at spans 1e4 and 1e8 (1e8 only at
 orders 1024 and 1025), set_scaling_from_iterate, get_scaling_packed, apply_F (four modes, in place), cone_prod, cone_div
@@ -35,6 +37,7 @@ import numpy as np
 import pytest
 
 import _cone_ref as CR
+from _sdp_large_forms import PATHS, _reach
 from test_gpu_cone_edges import _bits_equal, _dev, _offsets, _sym_dir, _system
 
 gpu = pytest.mark.gpu
@@ -52,7 +55,7 @@ CASES = {
     "s512": [_s(512)],
     # smallest rp = 1024; k_lg_jacobi<512, 16>
     "s513": [_s(513)],
-    # the last order whose 32-column slab fits the LDS budget of lg_tridiag, and the first with 16 columns
+    # the last order whose 32-column slab fits the LDS budget of the cooperative form (lg_eig_form), and the first with 16 columns
     "s583": [_s(583)],
     "s584": [_s(584)],
     # the largest cooperative tridiagonalisation: 64 workgroups
@@ -65,42 +68,6 @@ CASES = {
 }
 SPANS = {name: [1e8] if name in ("s1024", "s1025") else [1e4, 1e8] for name in CASES}
 FULL_MAX = 257                      # full-matrix checks up to here, sampled rows and probes above
-
-LARGE_S_MIN = 133                   # sdp.hip below, sdp_large.hip from here
-PATHS = {
-    "s257": {"rp": 512, "jacobi": (1024, 8, 16), "gemm": "batched-64", "pairable": False, "maxstep": [("cooperative", 32, 9)]},
-    "s512": {"rp": 512, "jacobi": (1024, 8, 16), "gemm": "batched-64", "pairable": False, "maxstep": [("cooperative", 32, 16)]},
-    "s513": {"rp": 1024, "jacobi": (512, 16, 8), "gemm": "batched-64", "pairable": False, "maxstep": [("cooperative", 32, 17)]},
-    "s583": {"rp": 1024, "jacobi": (512, 16, 8), "gemm": "batched-64", "pairable": False, "maxstep": [("cooperative", 32, 19)]},
-    "s584": {"rp": 1024, "jacobi": (512, 16, 8), "gemm": "batched-64", "pairable": False, "maxstep": [("cooperative", 16, 37)]},
-    "s1024": {"rp": 1024, "jacobi": (512, 16, 8), "gemm": "batched-64", "pairable": False, "maxstep": [("cooperative", 16, 64)]},
-    "s1025": {"rp": 2048, "jacobi": (256, 32, 4), "gemm": "batched-64", "pairable": False, "maxstep": [("stepped", 0, 2 * 1024)]},
-    "mixed_140_300": {"rp": 512, "jacobi": (1024, 8, 16), "gemm": "batched-64", "pairable": False,
-                      "maxstep": [("lanczos", 0, 1), ("cooperative", 32, 10)], "padding": [372, 212]},
-}
-
-
-def _reach(cone_dims):
-    """the dispatch rules of sdp_large.hip: cip_sdp_large_padded on the largest large cone; per rp the Jacobi form (threads,
-    elements per lane, block width: cip_sdp_large_nt); k_gemm_nt_small and the paired max step at rp <= 256 only (lg_gemm,
-    cip_sdp_large_pairable); the max step's eigenvalue by Lanczos up to order 256, the cooperative tridiagonalisation up to
-    1024 (lg_tridiag: slabs of LG_SLAB = 32 columns while (slab (r | 1) + 3 r + 64) doubles fit 160 KiB, else 16; one
-    workgroup per slab), 2 (r - 1) stepped launches above"""
-    large = [CR.order(k) for t, k in cone_dims if t == "S" and CR.order(k) >= LARGE_S_MIN]
-    rmax = max(large)
-    rp = 256 if rmax <= 256 else 512 if rmax <= 512 else 1024 if rmax <= 1024 else 2048
-    out = {"rp": rp, "gemm": "small" if rp <= 256 else "batched-64", "pairable": rp <= 256,
-           "jacobi": {256: (256, 8, 8), 512: (1024, 8, 16), 1024: (512, 16, 8), 2048: (256, 32, 4)}[rp],
-           "padding": [rp - r for r in large], "maxstep": []}
-    for r in large:
-        if r > 1024:
-            out["maxstep"].append(("stepped", 0, 2 * (r - 1)))
-        elif r <= 256:
-            out["maxstep"].append(("lanczos", 0, 1))
-        else:
-            slab = 32 if (32 * (r | 1) + 3 * r + 64) * 8 <= 160 * 1024 else 16
-            out["maxstep"].append(("cooperative", slab, -(-r // slab)))
-    return out
 
 
 def test_case_table_reaches_the_named_paths():

@@ -1,6 +1,6 @@
 """The NT scaling of ONE large S cone (order r, padded to 1024 above 512) from ONE fixed interior pair (v, s), repeated: the packed
 scaling of every repetition must have the first one's bits.  Counts the repetitions that differ (a race in the cooperative kernels of
-sdp_large.hip: the one-sided Jacobi's block exchange).  usage: python tools/nt1024_repeat.py [r] [reps]"""
+sdp_large_nt.hip: the one-sided Jacobi's block exchange).  usage: python tools/nt1024_repeat.py [r] [reps]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p_ in (ROOT, ROOT + '/conicip.jl_amd'): sys.path.insert(0, p_)

@@ -1,4 +1,4 @@
-"""One SHA-256 per line over the raw fp64 bytes of what every form of the S-cone kernels (csrc/sdp.hip, csrc/sdp_large.hip)
+"""One SHA-256 per line over the raw fp64 bytes of what every form of the S-cone kernels (csrc/sdp.hip, csrc/sdp_large*.hip)
 produces, on the smallest orders that reach each form: compare two builds line by line,
 
     CIPKKT_LIB=/path/to/libcipkkt.so python tools/sdp_forms_digest.py
@@ -8,9 +8,10 @@ only (no host BLAS product), so the same machine gives the same inputs to both b
 lambda, the four apply_F modes, cone_prod, cone_div by lambda and both forms of maxstep.  The forms and what selects them:
   sdp.hip          256 threads up to order 48, 1024 above (sd_threads, by the handle's largest S cone); the one-sided
                    Jacobi keeps both columns in registers while r <= 8 lanes-per-pair
-  sdp_large.hip    order 133 (padded to 256): k_lg_lanczos1 with the certificate (mode 2), alone (1), k_lg_tridiag1 +
-                   k_lg_sturm (0), the certificate's fallback on every call (3); 257 and 584 (padded to 512 and 1024):
-                   k_lg_tridiag with slabs of 32 and of 16 columns; 1025 (padded to 2048): k_tg_symv / k_tg_rank2
+  sdp_large*.hip   (cip_sdp_large_forms.h selects; the max-step's kernels are in sdp_large_eig.hip, the Jacobi's in
+                   sdp_large_nt.hip)  order 133 (padded to 256): k_lg_lanczos1 with the certificate (mode 2), alone (1),
+                   k_lg_tridiag1 + k_lg_sturm (0), the certificate's fallback on every call (3); 257 and 584 (padded to 512
+                   and 1024): k_lg_tridiag with slabs of 32 and of 16 columns; 1025 (padded to 2048): k_tg_symv / k_tg_rank2
   corner handles   a cone of order 132 beside one of order 431 / 432: the small cone decides both max-steps (zero
                    direction, respectively the identity, on the large block)"""
 import hashlib
