@@ -35,6 +35,11 @@ class CipProblem(C.Structure):
                 ("Q_rowptr", C.c_void_p), ("Q_colind", C.c_void_p), ("Q_val", C.c_void_p)]
 
 
+class CipCertBlock(C.Structure):
+    _fields_ = [("cols", C.c_int), ("dense", C.c_void_p), ("ld", C.c_int),
+                ("rowptr", C.c_void_p), ("colind", C.c_void_p), ("val", C.c_void_p)]
+
+
 class CipOptions(C.Structure):
     _fields_ = [("optTol", C.c_double), ("DTB", C.c_double), ("infeasTol", C.c_double),
                 ("refinementThreshold", C.c_double), ("maxRefinementSteps", C.c_int), ("maxIters", C.c_int),
@@ -122,6 +127,7 @@ SIGNATURES = {
                                c_double_p, c_int_p]),
     "cip_imcols_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, c_int_p,
                                  c_int_p, c_int_p, c_double_p]),
+    "cip_rowrank_cert": (C.c_int, [C.c_int, C.c_int, C.POINTER(CipCertBlock), C.c_double, C.c_int, c_int_p, c_double_p, c_double_p]),
     "cip_kkt_order": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "cip_get_kkt_matrix": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cip_assemble_only": (C.c_int, [C.c_void_p]),

@@ -18,6 +18,11 @@ does the pivoted QR run, and above `DENSE_QR_LIMIT` entries it refuses with a me
 Device QR.  `preprocess_conicIP(..., rank_solver="device")` hands the uncertified cases to `qrcp.imcols_hip` instead: the same
 algorithm as a column-pivoted Householder QR in HIP (csrc/qrcp.hip), no size limit, the wide matrix concatenated on the device.
 The host path is the default and is unchanged.
+
+Device certificate.  `preprocess_conicIP(..., certificate="device")` runs the certificate itself on the GPU
+(`qrcp.full_row_rank_hip`, csrc/rowrank.hip): the Gram matrix through the fp64 MFMA GEMM (sparse blocks entry by entry), a shift by
+the threshold plus a rounding allowance, and the library's LDL' -- all pivots positive is the certificate, no eigenvalue solver.  It is
+one-sided like the host's: "not certified" only sends the case to the QR.  `_full_row_rank` stays the default.
 """
 import numpy as np
 import scipy.linalg as sla
@@ -90,22 +95,31 @@ def imcols(A, b, eps=1e-8):
     return [], False
 
 
-def preprocess_conicIP(Q, c, A, b, cone_dims, G=None, d=None, rank_solver="host", **options):
+def preprocess_conicIP(Q, c, A, b, cone_dims, G=None, d=None, rank_solver="host", certificate="host", **options):
     """`conicIP` behind the reference's rank pre-solve (src/preprocessor.jl:43-96); same keywords as `conicIP`.
     rank_solver: where the rank-revealing QR runs when the full-row-rank certificate does not hold -- "host" (LAPACK geqp3, refused
-    above `DENSE_QR_LIMIT` entries) or "device" (`imcols_hip`: no size limit, [Q A' G'] is put together on the device)."""
+    above `DENSE_QR_LIMIT` entries) or "device" (`imcols_hip`: no size limit, [Q A' G'] is put together on the device).
+    certificate: where the full-row-rank certificate itself runs -- "host" (`_full_row_rank`: numpy Gram matrix, LAPACK eigvalsh) or
+    "device" (`full_row_rank_hip`: Gram matrix, shift and LDL' in HIP; both certificates, G and then [Q A' G'])."""
     if rank_solver not in ("host", "device"):
         raise ValueError("preprocess_conicIP: rank_solver must be \"host\" or \"device\", not %r" % (rank_solver,))
+    if certificate not in ("host", "device"):
+        raise ValueError("preprocess_conicIP: certificate must be \"host\" or \"device\", not %r" % (certificate,))
     on_device = rank_solver == "device"
     if on_device:
         from .qrcp import imcols_hip
+    certify = _full_row_rank
+    if certificate == "device":
+        from .kkt import _require_gpu
+        from .qrcp import full_row_rank_hip as certify
+        _require_gpu()                                              # no fall-back to the host certificate
     c = np.asarray(c, dtype=np.float64).reshape(-1)
     n, m = c.size, A.shape[0]
     G = np.zeros((0, n)) if G is None else G
     d = np.zeros(0) if d is None else np.asarray(d, dtype=np.float64).reshape(-1)
     p = G.shape[0]
     Gd = _dense(G)
-    if p > 0 and _full_row_rank([G if sp.issparse(G) else Gd], 1e-8):
+    if p > 0 and certify([G if sp.issparse(G) else Gd], 1e-8):
         keep_p, primal_ok = list(range(p)), True                    # G has full row rank: G y = d is consistent, nothing to drop
     elif on_device:
         keep_p, primal_ok = imcols_hip(G if sp.issparse(G) else Gd, d)
@@ -113,7 +127,7 @@ def preprocess_conicIP(Q, c, A, b, cone_dims, G=None, d=None, rank_solver="host"
         keep_p, primal_ok = imcols(Gd, d)
     At = (A.T.tocsr() if sp.issparse(A) else np.asarray(A, dtype=np.float64).T) if m > 0 else np.zeros((n, 0))
     dual_blocks = [Q, At, Gd[keep_p, :].T]
-    if _full_row_rank(dual_blocks, 1e-8):
+    if certify(dual_blocks, 1e-8):
         keep_d, dual_ok = list(range(n)), True                      # [Q A' G'] has full row rank: every dual equation is determined
     elif on_device:
         keep_d, dual_ok = imcols_hip(dual_blocks, c)

@@ -352,6 +352,31 @@ int cip_qrcp_dev(void *hip_stream, double *M, int len, int cnt, int ld, double s
 int cip_imcols_dev(void *hip_stream, const double *M, int len, int cnt, int ld, const double *b, double eps,
                    void *workspace, int *rows_host, int *nrows_host, int *consistent_host, double *resid_host);
 
+/* ---- the pre-solve's full-row-rank certificate (cipkkt/preprocess.py: _full_row_rank) on the device, in one self-contained call.
+ * M = [B_1 B_2 ...] has n rows and is handed over as column blocks.  *certified = 1: M CERTAINLY has n independent rows by the
+ * reference's criterion (src/preprocessor.jl:19-23), sigma_min(M) / ||M||_F >= thr = max(100 eps, 1e-6); 0: not certified -- the
+ * caller runs the rank-revealing QR; it never means "rank deficient".  The n x n Gram matrix sum B_i B_i' is formed on the device
+ * (dense blocks through the fp64 MFMA GEMM, CSR blocks entry by entry: O(nnz), never densified), tau I is subtracted, tau =
+ * (thr^2 + 2 (L + n) 2^-53) ||M||_F^2 with L the number of columns of M, and the unpivoted LDL' must have only positive pivots
+ * (Sylvester).  Rounding can only cost a certificate, never grant one.  *fro2 = ||M||_F^2 (a fixed-order sum), *shift = tau; either
+ * may be NULL; the same input gives the same bits on every run.
+ * flags: CIP_FLAG_DEVICE_PTRS -- the dense blocks are device pointers; the CSR arrays are host pointers unless it is set without
+ * CIP_FLAG_CSR_HOST.  The call owns its device memory and its streams: it works on the null stream, waits for its result and frees
+ * everything on every path.
+ * Argument rules, each CIP_E_INVALID naming the block and the entry before any device allocation: n, nblocks, cols >= 0; eps finite
+ * and >= 0; certified non-NULL; a block with cols > 0 (and n > 0) has exactly one of the two forms, a dense one with ld >= n; CSR:
+ * rowptr[0] == 0, a monotone row pointer, indices in [0, cols), no entry stored twice (checked on the host in O(nnz); device-resident
+ * arrays are copied back first).  n == 0 or no column at all: not certified, fro2 = 0, CIP_OK.  A NaN or Inf entry (or a sum of
+ * squares that overflows): CIP_E_INVALID "non-finite entry".  An all-zero M: not certified. */
+/* one column block B of M = [B_1 B_2 ...]; every block has n rows */
+typedef struct cip_cert_block {
+    int cols;
+    const double *dense; int ld;      /* column-major n x cols, ld >= max(n,1); or NULL for a CSR block */
+    const int *rowptr; const int *colind; const double *val;   /* CSR of B: n+1 / nnz / nnz, 0-based */
+} cip_cert_block;
+int cip_rowrank_cert(int n, int nblocks, const cip_cert_block *blocks, double eps, int flags,
+                     int *certified, double *fro2, double *shift);
+
 /* ---- introspection (tests, bench) */
 int cip_kkt_order(const cip_handle *h, int *N, int *N_padded);
 int cip_get_kkt_matrix(cip_handle *h, double *K_host /* N_padded^2 */); /* assembled (before cip_factor) or factored */

@@ -14,6 +14,8 @@ triangular solves) runs in `libcipkkt.so` (hand-written HIP for gfx950, C ABI in
     # JuMP, with integration/moi_kktsolver.patch applied to ConicIP's src/MOI_wrapper.jl:
     model = Model(() -> ConicIP.Optimizer(kktsolver = kktsolver_hip))                 # plugin levels, ConicIP's loop
     model = Model(() -> ConicIP.Optimizer(solve = preprocess_conicIP_hip))           # pre-solve on the host, loop on the device
+    # ... with the full-row-rank certificate on the device in front of the host's rank-revealing QR
+    model = Model(() -> ConicIP.Optimizer(solve = (a...; k...) -> preprocess_conicIP_hip(a...; certificate = :device, k...)))
 
 The library is looked up once, at module initialisation: `ENV["CONICIP_LIBCIPKKT"]` (a full path) if set, else
 `Libdl.find_library` over `libcipkkt` in `LD_LIBRARY_PATH` and in `<this package>/../../conicip.jl_amd/cipkkt` (the in-tree
@@ -31,6 +33,7 @@ using SparseArrays
 
 export kktsolver_hip, kktsolver_hip_full3x3, kktsolver_2x2_hip, solve3x3_many, CIP_ROUTE_SCHUR, CIP_ROUTE_FULL3X3
 export conicIP_hip, conicIP_hip_batch, preprocess_conicIP_hip, CipOptions, CipResult
+export full_row_rank_hip, CipCertBlock
 
 const _libpath = Ref{String}("")
 const _lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -397,18 +400,71 @@ function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, rou
     [_solution(ys[i], ws[i], vs[i], res[i]) for i in 1:k]
 end
 
+# --- the pre-solve's full-row-rank certificate on the device (cip_rowrank_cert) --------------------------------------------
+struct CipCertBlock                    # mirrors `cip_cert_block` of include/cipkkt.h field by field
+    cols::Cint
+    dense::Ptr{Float64}; ld::Cint
+    rowptr::Ptr{Cint}; colind::Ptr{Cint}; val::Ptr{Float64}
+end
+# One block B (n x k) of M = [B_1 B_2 ...].  `keep` collects the arrays the struct points at.  Sparse blocks stay sparse: the library
+# wants the CSR of B, which is the CSC of B' -- so the adjoint of a SparseMatrixCSC (the A' and G' of the dual test) is handed over
+# with the arrays its parent already has.  Everything else goes over dense, column-major.
+function _cert_csr(P::SparseMatrixCSC, keep)                                   # P = B', k x n
+    rp, ci, v = Cint.(P.colptr .- 1), Cint.(P.rowval .- 1), Vector{Float64}(P.nzval)
+    push!(keep, rp, ci, v)
+    CipCertBlock(size(P, 1), Ptr{Float64}(C_NULL), Cint(0), pointer(rp), isempty(ci) ? Ptr{Cint}(C_NULL) : pointer(ci),
+                 isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v))
+end
+_cert_block(B::SparseMatrixCSC, keep) = _cert_csr(sparse(B'), keep)
+_cert_block(B::Union{Adjoint{<:Any, <:SparseMatrixCSC}, Transpose{<:Any, <:SparseMatrixCSC}}, keep) = _cert_csr(parent(B), keep)
+function _cert_block(B, keep)
+    D = Matrix{Float64}(B)
+    push!(keep, D)
+    CipCertBlock(size(D, 2), isempty(D) ? Ptr{Float64}(C_NULL) : pointer(D), max(size(D, 1), 1), Ptr{Cint}(C_NULL), Ptr{Cint}(C_NULL),
+                 Ptr{Float64}(C_NULL))
+end
+
 """
-    preprocess_conicIP_hip(Q, c, A, b, cone_dims, G, d; kwargs...)
+    full_row_rank_hip(blocks; eps = 1e-8) -> Bool
+
+`true` when `M = [blocks...]` (matrices with the same number of rows, dense or sparse) CERTAINLY has all its rows independent by
+the criterion of `ConicIP.imcols` (src/preprocessor.jl:19-23): `σ_min(M) / ‖M‖_F ≥ max(100 eps, 1e-6)`, decided on the device
+from the Gram matrix `Σ BᵢBᵢᵀ` (cip_rowrank_cert).  `false` means "not certified" -- run `ConicIP.imcols` -- never "rank deficient".
+"""
+function full_row_rank_hip(blocks; eps = 1e-8)
+    n = isempty(blocks) ? 0 : size(blocks[1], 1)
+    keep = Any[]
+    arr = CipCertBlock[]
+    for B in blocks
+        size(B, 1) == n || throw(DimensionMismatch("full_row_rank_hip: the column blocks must have the same number of rows"))
+        push!(arr, _cert_block(B, keep))
+    end
+    ok = Ref{Cint}(0)
+    GC.@preserve keep arr begin
+        _cipcheck(ccall(_sym(:cip_rowrank_cert), Cint,
+            (Cint, Cint, Ptr{CipCertBlock}, Cdouble, Cint, Ref{Cint}, Ptr{Float64}, Ptr{Float64}),
+            n, length(arr), arr, eps, 0, ok, C_NULL, C_NULL))
+    end
+    ok[] == 1
+end
+
+"""
+    preprocess_conicIP_hip(Q, c, A, b, cone_dims, G, d; certificate = :host, kwargs...)
 
 `ConicIP.preprocess_conicIP` (src/preprocessor.jl:29-96) with `conicIP_hip` in place of `conicIP`: the rank-revealing
 pre-solve stays on the host exactly as in the reference (`ConicIP.imcols`), the interior-point loop runs on the device.
+With `certificate = :device` the full-row-rank certificate (`full_row_rank_hip`) is asked first, for `G` and then for
+`[Q A' G']`: where it holds -- every well-posed program -- `ConicIP.imcols` and its sparse QR are skipped, because they would keep
+every row; where it does not, they run as before.
 This is what `ConicIP.Optimizer(solve = preprocess_conicIP_hip)` (integration/moi_kktsolver.patch) calls from JuMP.
 """
 function preprocess_conicIP_hip(Q, c::AbstractVector, A, b::AbstractVector, cone_dims,
-                                G = spzeros(0, length(c)), d = zeros(0); verbose = false, options...)
+                                G = spzeros(0, length(c)), d = zeros(0); verbose = false, certificate = :host, options...)
+    certificate in (:host, :device) || throw(ArgumentError("preprocess_conicIP_hip: certificate must be :host or :device"))
     n, m, p = length(c), size(A, 1), size(G, 1)
-    (IP, pconsistent) = ConicIP.imcols(G, d)                                   # src/preprocessor.jl:55
-    (ID, dconsistent) = ConicIP.imcols([Q A' G[IP, :]'], c)                    # :56
+    certified(blocks) = certificate == :device && full_row_rank_hip(blocks)
+    (IP, pconsistent) = (p > 0 && certified([G])) ? (collect(1:p), true) : ConicIP.imcols(G, d)        # src/preprocessor.jl:55
+    (ID, dconsistent) = certified([Q, A', G[IP, :]']) ? (collect(1:n), true) : ConicIP.imcols([Q A' G[IP, :]'], c)   # :56
     if !(pconsistent && dconsistent)                                           # :58-61
         return ConicIP.Solution(zeros(n) / 0, zeros(p) / 0, zeros(m) / 0, :Infeasible, 0, NaN, NaN, NaN, NaN, NaN, NaN)
     end

@@ -110,4 +110,9 @@ end
     @test sol.status == ref.status == :Optimal
     @test length(sol.w) == 2
     @test norm(sol.y - ref.y) <= 1e-6 * (1 + norm(ref.y))
+    # the device certificate in front of imcols: G = [g; 2g] is not certified (imcols runs), [Q A' g'] is (imcols is skipped)
+    @test !full_row_rank_hip([G])
+    @test full_row_rank_hip([Q, A', G[1:1, :]'])
+    dev = preprocess_conicIP_hip(Q, c, A, b, K, G, d; optTol = 1e-7, certificate = :device)
+    @test dev.status == :Optimal && dev.w == sol.w && dev.y == sol.y
 end
