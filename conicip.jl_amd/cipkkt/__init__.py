@@ -13,6 +13,7 @@ from . import blocks
 from .driver import Solution, conicIP
 from .preprocess import imcols, preprocess_conicIP
 from .qrcp import full_row_rank_hip, imcols_hip, qrcp_hip
+from .batch import small_fits
 
 __all__ = ["KKTSystem", "kktsolver_hip", "kktsolver_hip_full3x3", "kktsolver_2x2_hip", "pivot", "blocks", "conicIP", "Solution", "CipError", "imcols",
-           "preprocess_conicIP", "imcols_hip", "qrcp_hip", "full_row_rank_hip"]
+           "preprocess_conicIP", "imcols_hip", "qrcp_hip", "full_row_rank_hip", "small_fits"]

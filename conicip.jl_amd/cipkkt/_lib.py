@@ -106,6 +106,11 @@ SIGNATURES = {
                              [C.POINTER(CipOptions)] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(CipResult)]),
     "cip_conicip_mixed": (C.c_int, [C.c_int, C.POINTER(CipProblem)] + [C.POINTER(C.c_void_p)] * 3 +
                           [C.POINTER(CipOptions)] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(CipResult), C.c_int]),
+    "cip_conicip_small_fits": (C.c_int, [C.POINTER(CipProblem)]),
+    "cip_conicip_small": (C.c_int, [C.c_int, C.POINTER(CipProblem)] + [C.POINTER(C.c_void_p)] * 3 +
+                          [C.POINTER(CipOptions)] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(CipResult)]),
+    "cip_small_stats": (C.c_int, [c_int_p]),
+    "cip_small_step_time": (C.c_int, [C.c_int, c_double_p]),
     "cip_release_cached_memory": (C.c_int, []),
     "cip_lockstep_stats": (C.c_int, [c_int_p]),
     "cip_set_lockstep_regularize": (C.c_int, [C.c_int]),

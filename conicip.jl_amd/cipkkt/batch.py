@@ -186,8 +186,147 @@ def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, 
     return [solution_from_result(res[i], ys[i][:dims[i][0]], ws[i][:dims[i][2]], vs[i][:dims[i][1]]) for i in range(k)]
 
 
+def _host_problem(Q, A, G, cone_dims, route="schur"):
+    """(cip_problem, keep-alive list) with every matrix a HOST pointer (column-major copies; flags = 0): what the small-problem
+    path takes for thousands of instances without a device staging copy each.  A scipy-sparse A goes over as CSR, a
+    scipy-sparse Q is densified (as cipkkt.kkt.make_problem does without sparse_q).  Needs no GPU."""
+    import ctypes as C
+    from . import _lib as L
+    from .kkt import _CONE_CODE, _is_sparse
+    n = Q.shape[0]
+    m = A.shape[0] if A is not None else 0
+    p = G.shape[0] if G is not None else 0
+    keep = []
+    pr = L.CipProblem()
+    pr.n, pr.m, pr.p, pr.ncones = n, m, p, len(cone_dims)
+    ct = (C.c_int * max(1, len(cone_dims)))(*[_CONE_CODE[t] for t, _ in cone_dims])
+    cdm = (C.c_int * max(1, len(cone_dims)))(*[int(k) for _, k in cone_dims])
+    keep += [ct, cdm]
+    pr.cone_type, pr.cone_dim = ct, cdm
+
+    def dense(M, rows, cols):
+        if isinstance(M, torch.Tensor):
+            M = M.detach().cpu().numpy()
+        a = np.asfortranarray(np.asarray(M.toarray() if _is_sparse(M) else M, dtype=np.float64).reshape(rows, cols))
+        keep.append(a)
+        return C.c_void_p(a.ctypes.data)
+
+    pr.Q, pr.ldq = dense(Q, n, n), n
+    if m > 0 and _is_sparse(A):
+        csr = A.tocsr()
+        csr.sort_indices()
+        arrs = [np.ascontiguousarray(x, dtype=dt) for x, dt in ((csr.indptr, np.int32), (csr.indices, np.int32), (csr.data, np.float64))]
+        keep += arrs
+        pr.A_rowptr, pr.A_colind, pr.A_val = (C.c_void_p(x.ctypes.data) for x in arrs)
+        pr.A, pr.lda = None, max(m, 1)
+    else:
+        pr.A, pr.lda = (dense(A, m, n) if m > 0 else None), max(m, 1)
+    pr.G, pr.ldg = (dense(G, p, n) if p > 0 else None), max(p, 1)
+    pr.route = L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
+    pr.flags = 0
+    return pr, keep
+
+
+def small_fits(Q, A, G, cone_dims, route="schur"):
+    """Does `cip_conicip_small` -- one workgroup per problem (csrc/small.hip) -- take a problem of this description?  The Schur
+    route, dense A, R and Q cones, n + p <= 128, m <= 1024 (`cip_conicip_small_fits`; `small_fits.reason` holds the library's
+    message after a False).  Needs the built library, no GPU."""
+    import ctypes as C
+    from . import _lib as L
+    pr, keep = _host_problem(Q, A, G, [(str(t), int(k)) for t, k in cone_dims], route)
+    lib = L.load()
+    rc = lib.cip_conicip_small_fits(C.byref(pr))
+    small_fits.reason = "" if rc == 0 else (lib.cip_last_error() or b"").decode()
+    del keep
+    return rc == 0
+
+
+small_fits.reason = ""
+
+
+def small_stats():
+    """`cip_small_stats` of the calling thread's last small-problem call: dict(finished, handed_over, launches, readbacks)."""
+    import ctypes as C
+    from . import _lib as L
+    out = (C.c_int * 4)()
+    L.check(L.load().cip_small_stats(out))
+    return dict(finished=out[0], handed_over=out[1], launches=out[2], readbacks=out[3])
+
+
+def solve_small(problems, pointers="host", device=None, **options):
+    """Problems of ONE shape (n, m, p, cone list) through `cip_conicip_small`: one workgroup per problem, two launches and one
+    read-back per iteration whatever their number.  problems: dicts(Q, c, A, b, cone_dims, G, d) as for `solve_batch`; options: the
+    keyword arguments of conicIP (optTol, DTB, infeasTol, refinementThreshold, maxRefinementSteps, maxIters) -- when none is given,
+    the first problem's "kwargs".  pointers: "host" (default: the matrices stay numpy arrays, the library uploads them) or "device"
+    (staged through cipkkt.kkt.make_problem); the results are the same bits.  A description the path does not take raises CipError
+    (CIP_E_UNSUPPORTED, nothing computed); problems whose factorisation needs the regularised LDL' come back from
+    `cip_conicip_mixed` (see `small_stats`).  Returns the list of Solutions."""
+    import ctypes as C
+    from . import _lib as L
+    from .driver import solution_from_result
+    if not problems:
+        return []
+    lib = L.load()
+    kw = options if options else problems[0].get("kwargs", {})
+    opt = _native_options(kw)
+    k = len(problems)
+    keep = []
+    structs = (L.CipProblem * k)()
+    dims = []
+    for i, pr in enumerate(problems):
+        cd = [(str(t), int(kk)) for t, kk in pr["cone_dims"]]
+        if pointers == "device":
+            from .kkt import make_problem
+            dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+            st, kp, _ = make_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"), dev)
+        else:
+            st, kp = _host_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"))
+        structs[i] = st
+        keep.append(kp)
+        dims.append((st.n, st.m, st.p))
+    if pointers == "device":
+        torch.cuda.current_stream(dev).synchronize()        # the staging transposes ran on torch's stream
+    vp = C.c_void_p * k
+
+    def host(key, i, size):
+        x = problems[i].get(key)
+        a = np.zeros(max(size, 1)) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+        keep.append(a)
+        return a
+
+    cs = [host("c", i, dims[i][0]) for i in range(k)]
+    bs = [host("b", i, dims[i][1]) for i in range(k)]
+    ds = [host("d", i, dims[i][2]) for i in range(k)]
+    ys = [np.zeros(max(dims[i][0], 1)) for i in range(k)]
+    ws = [np.zeros(max(dims[i][2], 1)) for i in range(k)]
+    vs = [np.zeros(max(dims[i][1], 1)) for i in range(k)]
+    arr = lambda xs: vp(*[x.ctypes.data for x in xs])
+    res = (L.CipResult * k)()
+    L.check(lib.cip_conicip_small(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs), res))
+    return [solution_from_result(res[i], ys[i][:dims[i][0]], ws[i][:dims[i][2]], vs[i][:dims[i][1]]) for i in range(k)]
+
+
+def _small_bins(problems, indices):
+    """the problems of `indices` binned by shape (n, m, p, cone list); [(fits the small path, [indices])] in order of first appearance"""
+    from .kkt import _is_sparse
+    bins = {}
+    for i in indices:
+        pr = problems[i]
+        A, G = pr["A"], pr.get("G")
+        key = (pr["Q"].shape[0], 0 if A is None else A.shape[0], 0 if G is None else G.shape[0],
+               tuple((str(t), int(k)) for t, k in pr["cone_dims"]), bool(A is not None and _is_sparse(A)),
+               str(pr.get("kwargs", {}).get("kktsolver", "schur")), bool(pr.get("sparse_q", False)))
+        bins.setdefault(key, []).append(i)
+    out = []
+    for key, idx in bins.items():
+        pr = problems[idx[0]]
+        fits = not key[-1] and small_fits(pr["Q"], pr["A"], pr.get("G"), pr["cone_dims"], key[-2])
+        out.append((fits, idx))
+    return out
+
+
 def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None, concurrency=1, native=False,
-                reduce_device=None, sparse_q=False, keep_regularized=False, ragged=False):
+                reduce_device=None, sparse_q=False, keep_regularized=False, small=False, ragged=False):
     """problems: list of dicts(Q, c, A, b, cone_dims, G, d, kwargs).  Each rank solves its
     shard with `solve_fn` (default: the HIP-backed cipkkt.conicIP) and the statistics are
     reduced over ranks:  SUM(iters, n_factor, n_solve, n_optimal, n_problems), MAX(wall).
@@ -201,6 +340,9 @@ def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None
     key of a problem dict) hands Q over in CSR.  `keep_regularized=True` (native batch entry points): problems that need the
     regularised factorisation stay in their lock-step group (`lockstep_regularize`).  `ragged=True` (the same entry points): CSR
     matrices of differing numbers of non-zeros share a lock-step group (`lockstep_ragged`).
+    `small=True` (default solver only; off by default: today's callers keep today's bits; pass it by keyword): this rank's problems are binned by shape
+    (n, m, p, cone list) and every bin `small_fits` accepts goes through `solve_small` -- one workgroup per problem; the other
+    problems go where they go without the keyword.
     Returns (local_solutions, stats_dict)."""
     default_solver = solve_fn is None
     if solve_fn is None:
@@ -208,6 +350,16 @@ def solve_batch(problems, solve_fn=None, rank=0, world=1, dist=None, device=None
     mine = shard_indices(len(problems), rank, world)
     sols = {}
     t0 = time.perf_counter()
+    if small and default_solver and mine:
+        rest = []
+        for fits, idx in _small_bins(problems, mine):
+            same = all(problems[i].get("kwargs", {}) == problems[idx[0]].get("kwargs", {}) for i in idx)
+            if fits and same and not sparse_q:
+                for i, sol in zip(idx, solve_small([problems[i] for i in idx], device=device)):
+                    sols[i] = sol
+            else:
+                rest += idx
+        mine = sorted(rest)
     same_opts = all(problems[i].get("kwargs", {}) == problems[mine[0]].get("kwargs", {}) for i in mine) if mine else True
     if default_solver and native and len(mine) > 0 and same_opts:
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())

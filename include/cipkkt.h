@@ -27,6 +27,9 @@
  *   - `*_dev` entry points take DEVICE pointers and enqueue on the handle's
  *     stream without synchronising (except where a host scalar is returned);
  *     the un-suffixed ones take HOST pointers and are synchronous.
+ *   - whole problems in, solutions out: cip_conicip (one handle), cip_conicip_lockstep / cip_conicip_mixed (batches, a launch
+ *     chain per iteration for groups of up to 64) and cip_conicip_small (batches of problems with n + p <= 128: one workgroup per
+ *     problem, two launches per iteration whatever their number).
  */
 #ifndef CIPKKT_H
 #define CIPKKT_H
@@ -296,6 +299,47 @@ int cip_set_lockstep_split(int k);
 int cip_conicip_many(cip_handle *const *handles, int count, const double *const *c, const double *const *bvec,
                      const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                      double *const *v, cip_result *res, int in_flight);
+
+/* ---- batches of SMALL problems, one workgroup per problem (csrc/small.hip).  Every entry point above pays a launch chain per
+ * interior-point iteration whatever the problem size (cip_conicip_lockstep: 97 launches and 3 host read-backs per iteration of an
+ * 8-problem shard, groups of at most 64).  Here a problem whose KKT matrix of order n + p <= CIP_SMALL_MAX_N fits the LDS of one
+ * compute unit is one 256-thread workgroup: per iteration the call issues at most 2 launches and 1 host read-back WHATEVER count is,
+ * plus 2 launches (upload gather, initial point) and 1 read-back (the iterates) per call; cip_small_stats reports what ran.
+ * Taken: the Schur route; dense Q, A and G, as host or device pointers as `flags` says (the same for every problem of a call); R and Q
+ * cones of any dimension; n + p <= CIP_SMALL_MAX_N, m <= CIP_SMALL_MAX_M; m == 0 and p == 0; all problems of a call of one n, m, p and
+ * cone list; any count >= 0 (0: no-op).  Anything else (an S cone, a CSR A, CIP_FLAG_Q_CSR, the full 3x3 route, a larger problem,
+ * differing shapes): CIP_E_UNSUPPORTED with cip_last_error() naming the rule, nothing written and nothing allocated.  Argument errors
+ * (a NULL array or vector, bad dimensions, cones that do not cover m, a leading dimension below its row count): CIP_E_INVALID before
+ * any allocation.
+ * The algorithm, the options and every field of cip_result are cip_conicip's (same loop, same verdicts: the per-iteration verdict is
+ * the one host function every loop of the library calls; n_factor and n_solve as cip_conicip counts them; wall_s: the call's wall
+ * time; verbose prints nothing per problem); the iterates differ from the other paths' in rounding only.  A problem's bits do not
+ * depend on count, on its index in the batch or on the run.  The call owns its stream and its device memory, is synchronous and
+ * frees everything on every path.
+ * A problem whose factorisation meets a zero, non-finite or wrong-sign pivot (positive expected on the first n, negative on the last p:
+ * LPs, singular Q with free variables) cannot be finished by the kernels -- there is no regularised factor in them: after the loop
+ * all such problems are solved from the start by cip_conicip_mixed, and their results are that call's, bit for bit.
+ * When it pays, as measured on one MI355X against cip_conicip_mixed on the same problems (dense QPs, m = 2n, wall time with the
+ * upload; DESIGN_LOG.md, "Small problems, one workgroup each"): at n <= 64 from the smallest count measured on (64 problems: 2.3 to
+ * 4.1 times the problems per second; 8192 problems: 26 times at n = 16, 7 to 8 times at n = 64); at n = 120 from about a thousand
+ * problems on (1024: 1.5 to 1.9 times, 8192: 2.1 to 2.5 times) -- with 64 problems of n = 120 it is level or LOSES (0.8 to 1.1 times):
+ * 64 workgroups leave most of the chip idle. */
+#define CIP_SMALL_MAX_N 128    /* n + p */
+#define CIP_SMALL_MAX_M 1024
+/* CIP_OK when cip_conicip_small takes a problem of this description, else CIP_E_UNSUPPORTED (or CIP_E_INVALID) with cip_last_error()
+ * naming the rule; no device is touched */
+int cip_conicip_small_fits(const cip_problem *prob);
+/* arguments and results as cip_conicip_lockstep */
+int cip_conicip_small(int count, const cip_problem *probs, const double *const *c, const double *const *bvec,
+                      const double *const *d, const cip_options *opt, double *const *y, double *const *w,
+                      double *const *v, cip_result *res);
+/* of the calling thread's last cip_conicip_small: {problems finished by the kernels, problems handed to cip_conicip_mixed, kernel
+ * launches, host read-backs} */
+int cip_small_stats(int *out4);
+/* HIP-event timing of the step kernel (k_small_step) for the calling thread's cip_conicip_small calls: enable = 1 / 0 switches it on /
+ * off (any other value only queries); out2 (may be NULL) = {step launches timed, their total ms} of the last call.  Returns the
+ * previous setting. */
+int cip_small_step_time(int enable, double *out2);
 
 /* ---- dense symmetric LDL' building blocks (device pointers), usable on their own.
  * K is N x N column-major with leading dimension ld >= N; only the lower triangle is

@@ -32,7 +32,7 @@ using LinearAlgebra
 using SparseArrays
 
 export kktsolver_hip, kktsolver_hip_full3x3, kktsolver_2x2_hip, solve3x3_many, CIP_ROUTE_SCHUR, CIP_ROUTE_FULL3X3
-export conicIP_hip, conicIP_hip_batch, preprocess_conicIP_hip, CipOptions, CipResult
+export conicIP_hip, conicIP_hip_batch, conicIP_hip_small_batch, preprocess_conicIP_hip, CipOptions, CipResult
 export full_row_rank_hip, CipCertBlock
 
 const _libpath = Ref{String}("")
@@ -395,6 +395,54 @@ function conicIP_hip_batch(problems::AbstractVector; in_flight::Integer = 4, rou
         prev >= 0 && ccall(_sym(:cip_set_lockstep_regularize), Cint, (Cint,), prev)
         _cipcheck(rc)
         regularized === nothing || _cipcheck(ccall(_sym(:cip_lockstep_regularized), Cint, (Ref{Cint},), regularized))
+    end
+    stats === nothing || (stats[] = res)
+    [_solution(ys[i], ws[i], vs[i], res[i]) for i in 1:k]
+end
+
+"""
+    conicIP_hip_small_batch(problems; kwargs...) -> Vector{ConicIP.Solution}
+
+Problems of ONE shape (n, m, p, cone list) with n + p <= 128 and m <= 1024, R and Q cones, on one GPU through
+`cip_conicip_small`: one workgroup per problem, the KKT matrix in the compute unit's LDS, two launches and one read-back per
+iteration whatever `length(problems)` is.  Every A goes over dense (a sparse-structured A is densified: at these sizes that is the
+form the kernels want).  `problems[i]` and the keywords are `conicIP_hip_batch`'s; a batch the path does not take (an S cone, a
+larger problem, differing shapes) is an error naming the rule -- use `conicIP_hip_batch`.  Problems whose factorisation needs the
+regularised LDL' come back from `cip_conicip_mixed`; `small_stats[]`, an `NTuple{4, Cint}` Ref, receives (finished by the kernels,
+handed over, kernel launches, host read-backs).
+"""
+function conicIP_hip_small_batch(problems::AbstractVector;
+                                 optTol = 1e-6, DTB = 0.01, verbose = false, maxRefinementSteps = 3, maxIters = 100,
+                                 cache_nestodd = false, infeasTol = optTol, refinementThreshold = optTol / 1e7, stats = nothing,
+                                 small_stats = nothing)
+    k = length(problems)
+    k == 0 && return ConicIP.Solution[]
+    staged = Vector{_Staged}(undef, k)
+    cs = Vector{Vector{Float64}}(undef, k); bs = similar(cs); ds = similar(cs)
+    ys = similar(cs); ws = similar(cs); vs = similar(cs)
+    for (i, pr) in enumerate(problems)
+        Q, c, A, b, K = pr[1], pr[2], pr[3], pr[4], pr[5]
+        G = length(pr) >= 7 ? pr[6] : spzeros(0, length(c))
+        d = length(pr) >= 7 ? pr[7] : zeros(0)
+        n, m, p = _check_dims(Q, c, A, b, G, d)
+        staged[i] = _stage(Q, Matrix{Float64}(A), G, K, CIP_ROUTE_SCHUR)
+        cs[i], bs[i], ds[i] = Vector{Float64}(c), Vector{Float64}(b), Vector{Float64}(d)
+        ys[i], ws[i], vs[i] = zeros(n), zeros(p), zeros(m)
+    end
+    opt = Ref(CipOptions(optTol, DTB, infeasTol, refinementThreshold, maxRefinementSteps, maxIters, verbose ? 1 : 0))
+    res = fill(CipResult(), k)
+    GC.@preserve staged cs bs ds ys ws vs begin
+        probs = [_problem(st) for st in staged]
+        ptrs(xs) = Ptr{Float64}[isempty(x) ? Ptr{Float64}(C_NULL) : pointer(x) for x in xs]
+        _cipcheck(ccall(_sym(:cip_conicip_small), Cint,
+            (Cint, Ptr{CipProblem}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ref{CipOptions},
+             Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{CipResult}),
+            k, probs, ptrs(cs), ptrs(bs), ptrs(ds), opt, ptrs(ys), ptrs(ws), ptrs(vs), res))
+        if small_stats !== nothing
+            out = zeros(Cint, 4)
+            _cipcheck(ccall(_sym(:cip_small_stats), Cint, (Ptr{Cint},), out))
+            small_stats[] = (out[1], out[2], out[3], out[4])
+        end
     end
     stats === nothing || (stats[] = res)
     [_solution(ys[i], ws[i], vs[i], res[i]) for i in 1:k]

@@ -98,6 +98,24 @@ end
     end
 end
 
+@testset "conicIP_hip_small_batch: one workgroup per problem" begin
+    mk(n, s) = begin
+        M = [sin(0.37 * i * j + 0.11 * i + s) for i in 1:n, j in 1:n]
+        (M' * M / n + 0.1I, [cos(0.9 * i + s) for i in 1:n], sparse(1.0I, n, n), zeros(n), [("R", n)])
+    end
+    probs = Any[mk(32, 0.1 * i) for i in 1:40]
+    ss = Ref{NTuple{4, Cint}}()
+    sols = conicIP_hip_small_batch(probs; optTol = 1e-7, small_stats = ss)
+    @test length(sols) == 40 && ss[][1] == 40 && ss[][2] == 0
+    for (pr, sol) in zip(probs, sols)
+        ref = conicIP(pr...; optTol = 1e-7, verbose = false)
+        @test sol.status == ref.status == :Optimal
+        @test sol.Iter == ref.Iter
+        @test norm(sol.y - ref.y) <= 1e-6 * (1 + norm(ref.y))
+    end
+    @test_throws ErrorException conicIP_hip_small_batch(Any[mk(32, 0.1), mk(200, 0.2)])      # differing shapes, n > 128
+end
+
 @testset "preprocess_conicIP_hip" begin
     # a redundant equality row: the pre-solve drops it on the host, the loop runs on the device (src/preprocessor.jl:55-90)
     n = 20
