@@ -5,6 +5,7 @@ is data parallelism over independent problems: problem i -> rank (i mod world). 
 is no data-path collective; one tiny all-reduce (RCCL over xGMI on the GPU box, gloo in
 the CPU tests) combines convergence / timing statistics.
 """
+import ctypes as C
 import os
 import time
 
@@ -55,17 +56,49 @@ def _native_options(kw):
                         kw.get("maxRefinementSteps", 3), kw.get("maxIters", 100), 0)
 
 
+class _Vectors:
+    """What every native batch entry point takes behind the problems: the host vectors c, b, d of the problem dicts `prs` (a missing
+    one: zeros) and y, w, v to be filled -- each of max(size, 1) entries, problem i's sizes being dims[i] = (n, m, p) -- and the
+    result array.  `args(opt)`: the run of arguments from c to res; `solutions()`: the Solutions behind the call."""
+
+    def __init__(self, prs, dims):
+        from . import _lib as L
+
+        def host(key, i, size):
+            x = prs[i].get(key)
+            return np.zeros(max(size, 1)) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+
+        self.dims = dims
+        self.inputs = [[host(key, i, nmp[j]) for i, nmp in enumerate(dims)] for key, j in (("c", 0), ("b", 1), ("d", 2))]
+        self.y, self.v, self.w = ([np.zeros(max(nmp[j], 1)) for nmp in dims] for j in range(3))      # (j: n, m, p)
+        self.res = (L.CipResult * len(dims))()
+
+    def args(self, opt):
+        arr = lambda xs: (C.c_void_p * len(xs))(*[x.ctypes.data for x in xs])
+        return tuple(arr(xs) for xs in self.inputs) + (C.byref(opt), arr(self.y), arr(self.w), arr(self.v), self.res)
+
+    def solutions(self):
+        from .driver import solution_from_result
+        return [solution_from_result(self.res[i], self.y[i][:n], self.w[i][:p], self.v[i][:m]) for i, (n, m, p) in enumerate(self.dims)]
+
+
+def _problem_array(prs, build):
+    """(cip_problem array, keep-alive list, [(n, m, p)]) of the problem dicts `prs`; build(pr, its cone list as [(str, int)])
+    returns one problem's (cip_problem, keep-alive, ...)"""
+    from . import _lib as L
+    built = [build(pr, [(str(t), int(k)) for t, k in pr["cone_dims"]])[:2] for pr in prs]
+    return (L.CipProblem * len(prs))(*[st for st, _ in built]), [kp for _, kp in built], [(st.n, st.m, st.p) for st, _ in built]
+
+
 def _solve_many_native(prs, device, in_flight, sparse_q=False):
     """All problems of this rank through `cip_conicip_many` (csrc/batch.hip): one handle + HIP stream per problem,
     `in_flight` native interior-point loops at once on the library's own host threads (no Python in the loop)."""
-    import ctypes as C
     from . import _lib as L
-    from .driver import solution_from_result
     from .kkt import KKTSystem
     lib = L.load()
     kw = prs[0].get("kwargs", {})
     opt = _native_options(kw)
-    systems, streams, keep = [], [], []
+    systems, streams = [], []
     try:
         for pr in prs:
             st = torch.cuda.Stream(device=device)
@@ -74,28 +107,11 @@ def _solve_many_native(prs, device, in_flight, sparse_q=False):
             ks.set_stream(st.cuda_stream)
             systems.append(ks)
             streams.append(st)
-        k = len(prs)
-        vp = C.c_void_p * k
-
-        def host(key, i, size):
-            x = prs[i].get(key)
-            a = np.zeros(max(size, 1)) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
-            keep.append(a)
-            return a
-
-        cs = [host("c", i, ks.n) for i, ks in enumerate(systems)]
-        bs = [host("b", i, ks.m) for i, ks in enumerate(systems)]
-        ds = [host("d", i, ks.p) for i, ks in enumerate(systems)]
-        ys = [np.zeros(max(ks.n, 1)) for ks in systems]
-        ws = [np.zeros(max(ks.p, 1)) for ks in systems]
-        vs = [np.zeros(max(ks.m, 1)) for ks in systems]
-        arr = lambda xs: vp(*[x.ctypes.data for x in xs])
-        res = (L.CipResult * k)()
-        handles = vp(*[ks.h.value for ks in systems])
+        vec = _Vectors(prs, [(ks.n, ks.m, ks.p) for ks in systems])
+        handles = (C.c_void_p * len(prs))(*[ks.h.value for ks in systems])
         with torch.cuda.device(device):
-            L.check(lib.cip_conicip_many(handles, k, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs),
-                                         res, int(in_flight)))
-        return [solution_from_result(res[i], ys[i][:ks.n], ws[i][:ks.p], vs[i][:ks.m]) for i, ks in enumerate(systems)]
+            L.check(lib.cip_conicip_many(handles, len(prs), *vec.args(opt), int(in_flight)))
+        return vec.solutions()
     finally:
         for st in streams:
             st.synchronize()
@@ -129,80 +145,44 @@ def _solve_problems_native(prs, device, in_flight, mode="auto", sparse_q=False, 
     sparse_q (or a problem's own "sparse_q" key): Q goes over in CSR (cipkkt.kkt.make_problem); the form is part of the shape.
     keep_regularized: `lockstep_regularize(True)` around the native call, the previous setting restored behind it.
     ragged: `lockstep_ragged(True)` around the native call in the same way."""
-    import ctypes as C
     from . import _lib as L
-    from .driver import solution_from_result
     from .kkt import make_problem
     lib = L.load()
     kw = prs[0].get("kwargs", {})
     opt = _native_options(kw)
     k = len(prs)
-    keep = []
-    structs = (L.CipProblem * k)()
-    dims = []
     with torch.cuda.device(device):
-        for i, pr in enumerate(prs):
-            cd = [(str(t), int(kk)) for t, kk in pr["cone_dims"]]
-            st, kp, _ = make_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"), device,
-                                      sparse_q=pr.get("sparse_q", sparse_q))
-            structs[i] = st
-            keep.append(kp)
-            dims.append((st.n, st.m, st.p))
+        structs, keep, dims = _problem_array(prs, lambda pr, cd: make_problem(
+            pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"), device, sparse_q=pr.get("sparse_q", sparse_q)))
         torch.cuda.current_stream(device).synchronize()     # the staging transposes ran on torch's stream
-        vp = C.c_void_p * k
-
-        def host(key, i, size):
-            x = prs[i].get(key)
-            a = np.zeros(max(size, 1)) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
-            keep.append(a)
-            return a
-
-        cs = [host("c", i, dims[i][0]) for i in range(k)]
-        bs = [host("b", i, dims[i][1]) for i in range(k)]
-        ds = [host("d", i, dims[i][2]) for i in range(k)]
-        ys = [np.zeros(max(dims[i][0], 1)) for i in range(k)]
-        ws = [np.zeros(max(dims[i][2], 1)) for i in range(k)]
-        vs = [np.zeros(max(dims[i][1], 1)) for i in range(k)]
-        arr = lambda xs: vp(*[x.ctypes.data for x in xs])
-        res = (L.CipResult * k)()
+        vec = _Vectors(prs, dims)
         if mode == "auto":
             mode = os.environ.get("CIP_BATCH", "auto")
         prev = lockstep_regularize(True) if keep_regularized else None
         prev_ragged = lockstep_ragged(True) if ragged else None
         try:
             if mode == "lockstep":
-                L.check(lib.cip_conicip_lockstep(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs), res))
+                L.check(lib.cip_conicip_lockstep(k, structs, *vec.args(opt)))
             elif mode == "threads":
-                L.check(lib.cip_conicip_problems(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs),
-                                                 res, int(in_flight)))
+                L.check(lib.cip_conicip_problems(k, structs, *vec.args(opt), int(in_flight)))
             else:
-                L.check(lib.cip_conicip_mixed(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs),
-                                              res, int(in_flight)))
+                L.check(lib.cip_conicip_mixed(k, structs, *vec.args(opt), int(in_flight)))
         finally:
             if prev_ragged is not None:
                 lockstep_ragged(prev_ragged)
             if prev is not None:
                 lockstep_regularize(prev)
-    return [solution_from_result(res[i], ys[i][:dims[i][0]], ws[i][:dims[i][2]], vs[i][:dims[i][1]]) for i in range(k)]
+    return vec.solutions()
 
 
 def _host_problem(Q, A, G, cone_dims, route="schur"):
     """(cip_problem, keep-alive list) with every matrix a HOST pointer (column-major copies; flags = 0): what the small-problem
     path takes for thousands of instances without a device staging copy each.  A scipy-sparse A goes over as CSR, a
     scipy-sparse Q is densified (as cipkkt.kkt.make_problem does without sparse_q).  Needs no GPU."""
-    import ctypes as C
     from . import _lib as L
-    from .kkt import _CONE_CODE, _is_sparse
-    n = Q.shape[0]
-    m = A.shape[0] if A is not None else 0
-    p = G.shape[0] if G is not None else 0
-    keep = []
-    pr = L.CipProblem()
-    pr.n, pr.m, pr.p, pr.ncones = n, m, p, len(cone_dims)
-    ct = (C.c_int * max(1, len(cone_dims)))(*[_CONE_CODE[t] for t, _ in cone_dims])
-    cdm = (C.c_int * max(1, len(cone_dims)))(*[int(k) for _, k in cone_dims])
-    keep += [ct, cdm]
-    pr.cone_type, pr.cone_dim = ct, cdm
+    from .kkt import _host_csr, _is_sparse, _new_problem
+    pr, keep = _new_problem(Q, A, G, cone_dims, route)
+    n, m, p = pr.n, pr.m, pr.p
 
     def dense(M, rows, cols):
         if isinstance(M, torch.Tensor):
@@ -213,16 +193,11 @@ def _host_problem(Q, A, G, cone_dims, route="schur"):
 
     pr.Q, pr.ldq = dense(Q, n, n), n
     if m > 0 and _is_sparse(A):
-        csr = A.tocsr()
-        csr.sort_indices()
-        arrs = [np.ascontiguousarray(x, dtype=dt) for x, dt in ((csr.indptr, np.int32), (csr.indices, np.int32), (csr.data, np.float64))]
-        keep += arrs
-        pr.A_rowptr, pr.A_colind, pr.A_val = (C.c_void_p(x.ctypes.data) for x in arrs)
+        pr.A_rowptr, pr.A_colind, pr.A_val = _host_csr(A, keep)
         pr.A, pr.lda = None, max(m, 1)
     else:
         pr.A, pr.lda = (dense(A, m, n) if m > 0 else None), max(m, 1)
     pr.G, pr.ldg = (dense(G, p, n) if p > 0 else None), max(p, 1)
-    pr.route = L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
     pr.flags = 0
     return pr, keep
 
@@ -231,7 +206,6 @@ def small_fits(Q, A, G, cone_dims, route="schur"):
     """Does `cip_conicip_small` -- one workgroup per problem (csrc/small.hip) -- take a problem of this description?  The Schur
     route, dense A, R and Q cones, n + p <= 128, m <= 1024 (`cip_conicip_small_fits`; `small_fits.reason` holds the library's
     message after a False).  Needs the built library, no GPU."""
-    import ctypes as C
     from . import _lib as L
     pr, keep = _host_problem(Q, A, G, [(str(t), int(k)) for t, k in cone_dims], route)
     lib = L.load()
@@ -246,7 +220,6 @@ small_fits.reason = ""
 
 def small_stats():
     """`cip_small_stats` of the calling thread's last small-problem call: dict(finished, handed_over, launches, readbacks)."""
-    import ctypes as C
     from . import _lib as L
     out = (C.c_int * 4)()
     L.check(L.load().cip_small_stats(out))
@@ -261,49 +234,23 @@ def solve_small(problems, pointers="host", device=None, **options):
     (staged through cipkkt.kkt.make_problem); the results are the same bits.  A description the path does not take raises CipError
     (CIP_E_UNSUPPORTED, nothing computed); problems whose factorisation needs the regularised LDL' come back from
     `cip_conicip_mixed` (see `small_stats`).  Returns the list of Solutions."""
-    import ctypes as C
     from . import _lib as L
-    from .driver import solution_from_result
     if not problems:
         return []
     lib = L.load()
     kw = options if options else problems[0].get("kwargs", {})
     opt = _native_options(kw)
-    k = len(problems)
-    keep = []
-    structs = (L.CipProblem * k)()
-    dims = []
-    for i, pr in enumerate(problems):
-        cd = [(str(t), int(kk)) for t, kk in pr["cone_dims"]]
-        if pointers == "device":
-            from .kkt import make_problem
-            dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-            st, kp, _ = make_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"), dev)
-        else:
-            st, kp = _host_problem(pr["Q"], pr["A"], pr.get("G"), cd, kw.get("kktsolver", "schur"))
-        structs[i] = st
-        keep.append(kp)
-        dims.append((st.n, st.m, st.p))
+    route = kw.get("kktsolver", "schur")
     if pointers == "device":
+        from .kkt import make_problem
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        structs, keep, dims = _problem_array(problems, lambda pr, cd: make_problem(pr["Q"], pr["A"], pr.get("G"), cd, route, dev))
         torch.cuda.current_stream(dev).synchronize()        # the staging transposes ran on torch's stream
-    vp = C.c_void_p * k
-
-    def host(key, i, size):
-        x = problems[i].get(key)
-        a = np.zeros(max(size, 1)) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
-        keep.append(a)
-        return a
-
-    cs = [host("c", i, dims[i][0]) for i in range(k)]
-    bs = [host("b", i, dims[i][1]) for i in range(k)]
-    ds = [host("d", i, dims[i][2]) for i in range(k)]
-    ys = [np.zeros(max(dims[i][0], 1)) for i in range(k)]
-    ws = [np.zeros(max(dims[i][2], 1)) for i in range(k)]
-    vs = [np.zeros(max(dims[i][1], 1)) for i in range(k)]
-    arr = lambda xs: vp(*[x.ctypes.data for x in xs])
-    res = (L.CipResult * k)()
-    L.check(lib.cip_conicip_small(k, structs, arr(cs), arr(bs), arr(ds), C.byref(opt), arr(ys), arr(ws), arr(vs), res))
-    return [solution_from_result(res[i], ys[i][:dims[i][0]], ws[i][:dims[i][2]], vs[i][:dims[i][1]]) for i in range(k)]
+    else:
+        structs, keep, dims = _problem_array(problems, lambda pr, cd: _host_problem(pr["Q"], pr["A"], pr.get("G"), cd, route))
+    vec = _Vectors(problems, dims)
+    L.check(lib.cip_conicip_small(len(problems), structs, *vec.args(opt)))
+    return vec.solutions()
 
 
 def _small_bins(problems, indices):

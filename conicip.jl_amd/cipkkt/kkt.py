@@ -84,6 +84,30 @@ def pack_scaling(cone_dims, F, FinvT=None):
     return np.ascontiguousarray(np.concatenate(out)) if out else np.zeros(0)
 
 
+def _route_code(route):
+    return L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
+
+
+def _new_problem(Q, A, G, cone_dims, route):
+    """(cip_problem, keep-alive list) with what does not depend on where the matrices live: the dimensions, the cone table (C int
+    arrays, never of length 0) and the route code"""
+    pr = L.CipProblem()
+    pr.n, pr.m, pr.p = Q.shape[0], (A.shape[0] if A is not None else 0), (G.shape[0] if G is not None else 0)
+    arr = C.c_int * max(1, len(cone_dims))
+    keep = [arr(*[_CONE_CODE[t] for t, _ in cone_dims]), arr(*[int(k) for _, k in cone_dims])]
+    pr.ncones, pr.cone_type, pr.cone_dim, pr.route = len(cone_dims), keep[0], keep[1], _route_code(route)
+    return pr, keep
+
+
+def _host_csr(M, keep):
+    """(rowptr, colind, values) pointers of a scipy-sparse matrix for a cip_problem: host arrays (int32, int32, float64; the column
+    indices of a row sorted), appended to `keep`"""
+    csr = M.tocsr()
+    csr.sort_indices()
+    arrs = [np.ascontiguousarray(x, dtype=dt) for x, dt in ((csr.indptr, np.int32), (csr.indices, np.int32), (csr.data, np.float64))]
+    keep += arrs
+    return [C.c_void_p(x.ctypes.data) for x in arrs]
+
 
 def make_problem(Q, A, G, cone_dims, route, device, sparse_q=False):
     """(cip_problem, keep-alive list, A_is_sparse): every matrix handed over as a DEVICE pointer.  Host arrays are
@@ -94,16 +118,8 @@ def make_problem(Q, A, G, cone_dims, route, device, sparse_q=False):
     sparse_q=True hands Q over as host CSR arrays (CIP_FLAG_Q_CSR: the whole symmetric matrix, O(nnz) on the device, no
     dense image).  The default stays False -- even a scipy-sparse Q is densified unless the caller asks: the two forms
     add Q's entries in different orders, and today's callers keep today's bits."""
-    n = Q.shape[0]
-    m = A.shape[0] if A is not None else 0
-    p = G.shape[0] if G is not None else 0
-    keep = []
-    pr = L.CipProblem()
-    pr.n, pr.m, pr.p, pr.ncones = n, m, p, len(cone_dims)
-    ct = (C.c_int * max(1, len(cone_dims)))(*[_CONE_CODE[t] for t, _ in cone_dims])
-    cdm = (C.c_int * max(1, len(cone_dims)))(*[k for _, k in cone_dims])
-    keep += [ct, cdm]
-    pr.cone_type, pr.cone_dim = ct, cdm
+    pr, keep = _new_problem(Q, A, G, cone_dims, route)
+    n, m, p = pr.n, pr.m, pr.p
 
     def dense(M, rows, cols):
         """column-major fp64 device buffer"""
@@ -113,35 +129,21 @@ def make_problem(Q, A, G, cone_dims, route, device, sparse_q=False):
         keep.append(Mt)            # row-major of M' == column-major of M
         return C.c_void_p(Mt.data_ptr())
 
-    csr_host = False
     if sparse_q:
         import scipy.sparse as sp
-        qc = sp.csr_matrix(Q.detach().cpu().numpy() if isinstance(Q, torch.Tensor) else Q)
-        qc.sort_indices()
-        q_h = [np.ascontiguousarray(x, dtype=dt) for x, dt in ((qc.indptr, np.int32), (qc.indices, np.int32), (qc.data, np.float64))]
-        keep += q_h
-        pr.Q_rowptr, pr.Q_colind, pr.Q_val = (C.c_void_p(x.ctypes.data) for x in q_h)
+        pr.Q_rowptr, pr.Q_colind, pr.Q_val = _host_csr(sp.csr_matrix(Q.detach().cpu().numpy() if isinstance(Q, torch.Tensor) else Q), keep)
         pr.Q, pr.ldq = None, n
-        csr_host = True
     else:
         pr.Q, pr.ldq = dense(Q, n, n), n
-    a_sparse = False
-    if m > 0 and _is_sparse(A):          # (S cones too, round 4: the library expands their rows on the device)
-        csr = A.tocsr()
-        csr.sort_indices()
+    a_sparse = m > 0 and _is_sparse(A)   # (S cones too, round 4: the library expands their rows on the device)
+    if a_sparse:
         # the CSR arrays stay on the host (CIP_FLAG_CSR_HOST): the library builds the CSR of A' there and uploads both
-        rp_h, ci_h, av_h = (np.ascontiguousarray(x, dtype=dt)
-                            for x, dt in ((csr.indptr, np.int32), (csr.indices, np.int32), (csr.data, np.float64)))
-        keep += [rp_h, ci_h, av_h]
-        pr.A_rowptr, pr.A_colind, pr.A_val = (C.c_void_p(x.ctypes.data) for x in (rp_h, ci_h, av_h))
+        pr.A_rowptr, pr.A_colind, pr.A_val = _host_csr(A, keep)
         pr.A = None
-        a_sparse = True
-        csr_host = True
     else:
         pr.A, pr.lda = (dense(A, m, n) if m > 0 else None), max(m, 1)
     pr.G, pr.ldg = (dense(G, p, n) if p > 0 else None), max(p, 1)
-    pr.route = L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
-    pr.flags = L.FLAG_DEVICE_PTRS | (L.FLAG_CSR_HOST if csr_host else 0) | (L.FLAG_Q_CSR if sparse_q else 0)
+    pr.flags = L.FLAG_DEVICE_PTRS | (L.FLAG_CSR_HOST if sparse_q or a_sparse else 0) | (L.FLAG_Q_CSR if sparse_q else 0)
     return pr, keep, a_sparse
 
 
@@ -168,7 +170,7 @@ class KKTSystem:
         if sum(k for _, k in self.cone_dims) != m:
             raise ValueError("cone_dims do not cover the rows of A")
         self.n, self.m, self.p = n, m, p
-        self.route = L.ROUTE_SCHUR if route in ("schur", L.ROUTE_SCHUR) else L.ROUTE_FULL3X3
+        self.route = _route_code(route)
 
         self.Q_sparse = bool(sparse_q)
         pr, keep, self.A_sparse = make_problem(Q, A, G, self.cone_dims, self.route, self.device, sparse_q=self.Q_sparse)

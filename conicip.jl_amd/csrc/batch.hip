@@ -5,46 +5,30 @@
 // chip idle, several of them on different streams fill it (measured from Python threads: 481 -> 658 KKT solves/s).
 // Per-problem work uses the normal entry points on cip_batch_handle(b, i) (the "leading problem index").
 #include "cip_handle.h"
-#include "../../include/cipkkt.h"
-#include <atomic>
+#include "cip_batch_front.h"
 #include <string>
-#include <thread>
 #include <vector>
+
+using namespace cipdrv;
 
 struct cip_batch {
     std::vector<cip_handle *> h;
     std::vector<hipStream_t> streams;
 };
 
+// problem i of a call through the one-problem loop on handle h
+static int solve_one(const BatchCall &k, cip_handle *h, int i) {
+    return cip_conicip(h, k.c[i], k.b ? k.b[i] : nullptr, k.d ? k.d[i] : nullptr, k.opt, k.y[i], k.w ? k.w[i] : nullptr,
+                       k.v ? k.v[i] : nullptr, &k.res[i], nullptr, 0);
+}
+
 extern "C" int cip_conicip_many(cip_handle *const *handles, int count, const double *const *c, const double *const *b,
                                 const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                                 double *const *v, cip_result *res, int in_flight) {
-    if (count < 0 || (count > 0 && (!handles || !c || !y || !res))) { cip_set_error("cip_conicip_many: null argument"); return CIP_E_INVALID; }
+    const BatchCall k = {count, nullptr, handles, c, b, d, opt, y, w, v, res};
+    CIP_TRY(check_batch_call("cip_conicip_many", k, CHECK_ARRAYS));
     if (count == 0) return 0;
-    if (in_flight < 1) in_flight = 1;
-    if (in_flight > count) in_flight = count;
-    std::atomic<int> next(0), first_rc(0);
-    std::string first_err;
-    std::atomic<bool> have_err(false);
-    auto worker = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= count) return;
-            const int rc = cip_conicip(handles[i], c[i], b ? b[i] : nullptr, d ? d[i] : nullptr, opt, y[i], w ? w[i] : nullptr,
-                                       v ? v[i] : nullptr, &res[i], nullptr, 0);
-            if (rc != 0) {
-                res[i].status = CIP_STATUS_ERROR;
-                bool expected = false;
-                if (have_err.compare_exchange_strong(expected, true)) { first_rc = rc; first_err = cip_last_error(); }
-            }
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < in_flight; ++t) pool.emplace_back(worker);
-    worker();                                   // the calling thread is the first worker
-    for (auto &t : pool) t.join();
-    if (have_err) { cip_set_error("problem failed: %s", first_err.c_str()); return first_rc; }
-    return 0;
+    return run_pool(k, in_flight, [] { return 0; }, [&](int, int i) { return solve_one(k, handles[i], i); });
 }
 
 // Problems in, solutions out: `in_flight` worker threads, each with ONE handle on its own stream that is re-loaded
@@ -54,49 +38,28 @@ extern "C" int cip_conicip_many(cip_handle *const *handles, int count, const dou
 extern "C" int cip_conicip_problems(int count, const cip_problem *probs, const double *const *c, const double *const *b,
                                     const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                                     double *const *v, cip_result *res, int in_flight) {
-    if (count < 0 || (count > 0 && (!probs || !c || !y || !res))) { cip_set_error("cip_conicip_problems: null argument"); return CIP_E_INVALID; }
+    const BatchCall k = {count, probs, nullptr, c, b, d, opt, y, w, v, res};
+    CIP_TRY(check_batch_call("cip_conicip_problems", k, CHECK_ARRAYS));
     if (count == 0) return 0;
-    if (in_flight < 1) in_flight = 1;
-    if (in_flight > count) in_flight = count;
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) { cip_set_error("no HIP device"); return CIP_E_NODEVICE; }
-    std::atomic<int> next(0), first_rc(0);
-    std::string first_err;
-    std::atomic<bool> have_err(false);
-    auto worker = [&]() {
-        (void)hipSetDevice(device);
+    struct Worker {                // a thread's handle and stream
         cip_handle *h = nullptr;
         hipStream_t st = nullptr;
-        auto fail = [&](int i, int rc) {
-            res[i].status = CIP_STATUS_ERROR;
-            bool expected = false;
-            if (have_err.compare_exchange_strong(expected, true)) { first_rc = rc; first_err = cip_last_error(); }
-        };
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr;
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= count) break;
-            int rc = 0;
-            // (refused for another shape -- another Q form, dense or CSR, or another nnz of a CSR Q or A included: new handle)
-            if (h && cip_update_problem(h, &probs[i]) != 0) { cip_destroy(h); h = nullptr; }     // other shape: new handle
-            if (!h) {
-                rc = cip_create_ex(&probs[i], &h);
-                if (rc == 0 && st) rc = cip_set_stream(h, st);
-            }
-            if (rc == 0)
-                rc = cip_conicip(h, c[i], b ? b[i] : nullptr, d ? d[i] : nullptr, opt, y[i], w ? w[i] : nullptr,
-                                 v ? v[i] : nullptr, &res[i], nullptr, 0);
-            if (rc != 0) fail(i, rc);
-        }
-        if (h) cip_destroy(h);
-        if (st) (void)hipStreamDestroy(st);
+        explicit Worker(int dev) { (void)hipSetDevice(dev); if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr; }
+        Worker(const Worker &) = delete;
+        ~Worker() { if (h) cip_destroy(h); if (st) (void)hipStreamDestroy(st); }
     };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < in_flight; ++t) pool.emplace_back(worker);
-    worker();
-    for (auto &t : pool) t.join();
-    if (have_err) { cip_set_error("problem failed: %s", first_err.c_str()); return first_rc; }
-    return 0;
+    return run_pool(k, in_flight, [&] { return Worker(device); }, [&](Worker &t, int i) {
+        int rc = 0;
+        // (refused for another shape -- another Q form, dense or CSR, or another nnz of a CSR Q or A included: new handle)
+        if (t.h && cip_update_problem(t.h, &probs[i]) != 0) { cip_destroy(t.h); t.h = nullptr; }     // other shape: new handle
+        if (!t.h) {
+            rc = cip_create_ex(&probs[i], &t.h);
+            if (rc == 0 && t.st) rc = cip_set_stream(t.h, t.st);
+        }
+        return rc ? rc : solve_one(k, t.h, i);
+    });
 }
 
 extern "C" int cip_batch_create(int count, const cip_problem *probs, cip_batch **out) {

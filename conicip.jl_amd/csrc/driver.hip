@@ -13,6 +13,7 @@
 // iteration (:737 precedes :786), rPr ignores the equality residual (:765), norm(v4x1) is the sum of the
 // block 2-norms (:61), the returned (y, w, v) is the last iterate.
 #include "cip_driver.h"
+#include "cip_batch_front.h"
 #include <chrono>
 #include <vector>
 
@@ -41,8 +42,7 @@ int cipdrv::Loop::run(const double *const *c, const double *const *b, const doub
         if (m > 0) CIP_HIP_CHECK(hipMemcpyAsync((char *)b_d + off, b[z], sizeof(double) * m, hipMemcpyHostToDevice, s));
         if (p > 0) CIP_HIP_CHECK(hipMemcpyAsync((char *)d_d + off, d[z], sizeof(double) * p, hipMemcpyHostToDevice, s));
         nm[z] = host_norms(n, m, p, c[z], m > 0 ? b[z] : nullptr, p > 0 ? d[z] : nullptr);
-        res[z] = cip_result{};
-        res[z].prFeas = res[z].duFeas = res[z].muFeas = INFINITY; res[z].pobj = INFINITY; res[z].dobj = -INFINITY;
+        res[z] = fresh_result();
     }
     const double conedim = cone_degree(h);          // (:547-552); e (:559-565) below
     const double *f = cip_loop_all_r(h);            // diag F when every cone is an R cone (the loop's cone operations are then fused into its vector kernels), else NULL

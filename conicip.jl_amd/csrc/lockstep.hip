@@ -26,6 +26,7 @@
 // Not supported in lock-step (the caller falls back to the thread pool of batch.hip): S cones of order >= 133 (their
 // chip-wide kernels own one workspace), problems of differing shape.
 #include "cip_driver.h"
+#include "cip_batch_front.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -68,10 +69,7 @@ static thread_local bool g_stats_accumulate = false;     // cip_conicip_mixed: t
 std::atomic<int> g_ragged{0};
 // ragged: the numbers of non-zeros of CSR matrices do not count (dense beside CSR still does)
 bool same_shape(const cip_problem &a, const cip_problem &b, bool ragged) {
-    if (a.n != b.n || a.m != b.m || a.p != b.p || a.ncones != b.ncones || a.route != b.route) return false;
-    if ((a.A == nullptr) != (b.A == nullptr) || (a.flags & CIP_FLAG_DEVICE_PTRS) != (b.flags & CIP_FLAG_DEVICE_PTRS)) return false;
-    for (int c = 0; c < a.ncones; ++c)
-        if (a.cone_type[c] != b.cone_type[c] || a.cone_dim[c] != b.cone_dim[c]) return false;
+    if (!same_dims(a, b) || a.route != b.route || (a.A == nullptr) != (b.A == nullptr)) return false;
     // CSR A: the slab layout depends on the number of non-zeros -- part of the shape when the row pointers can be read here
     // (host memory); device-resident row pointers are caught by the slab-layout check of lockstep_group instead
     auto host_rowptr = [](const cip_problem &q) {
@@ -308,17 +306,14 @@ static int lockstep_group(int B, int call_count, bool ragged, const cip_problem 
     CipCsrCap cap = {0, 0};
     for (int z = 0; z < B; ++z) {
         if ((rc = cip_plan(&probs[z], G.stream, &G.h[z]))) return rc;
-        if (z == 0 && G.h[0]->cs.nlarge > 0) { cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN); return CIP_E_UNSUPPORTED; }
+        if (z == 0 && G.h[0]->cs.nlarge > 0) return refuse_chipwide_s_cone();      // (the backstop: has_chipwide_s_cone looked at the description)
         cap.A_nnz = std::max(cap.A_nnz, (size_t)G.h[z]->A_nnz);
         cap.Q_nnz = std::max(cap.Q_nnz, (size_t)G.h[z]->Q_nnz);
     }
     const CipCsrCap *csr_cap = ragged ? &cap : nullptr;      // (not ragged: every handle's own nnz, which must then agree with problem 0's)
     const size_t slab = cip_handle_layout(nullptr, G.h[0], extras, csr_cap);
     t_plan = since();
-    // odd number of 256-byte granules: the same buffer of consecutive problems does not land on the same HBM channel
-    size_t gran = (slab + 255) / 256;
-    if ((gran & 1) == 0) ++gran;
-    G.stride = gran * 256;
+    G.stride = slab_stride(slab);
     const size_t gather_bytes = sizeof(double) * (size_t)B * CIP_GATHER;
     G.arena_bytes = G.stride * (size_t)B + gather_bytes;
     if ((rc = arena_acquire(G.arena_bytes, &G.arena, &G.arena_bytes))) return rc;
@@ -399,17 +394,12 @@ extern "C" int cip_set_lockstep_split(int k) { return cip_lockstep_split_set(k);
 extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const double *const *c, const double *const *b,
                                     const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                                     double *const *v, cip_result *res) {
-    if (count < 0 || (count > 0 && (!probs || !c || !y || !res))) { cip_set_error("cip_conicip_lockstep: null argument"); return CIP_E_INVALID; }
+    CIP_TRY(check_batch_call("cip_conicip_lockstep", {count, probs, nullptr, c, b, d, opt, y, w, v, res}, CHECK_PROBLEM0));
     if (count == 0) return 0;
-    if ((probs[0].m > 0 && (!b || !v)) || (probs[0].p > 0 && (!d || !w))) { cip_set_error("cip_conicip_lockstep: null argument"); return CIP_E_INVALID; }
     const bool ragged = g_ragged.load() != 0;                  // (read once: the shape check and every group's slab must agree)
     for (int i = 1; i < count; ++i)
         if (!same_shape(probs[0], probs[i], ragged)) { cip_set_error("lock-step batch: problem %d differs in shape from problem 0", i); return CIP_E_UNSUPPORTED; }
-    for (int c0 = 0; c0 < probs[0].ncones; ++c0)       // S cones of order >= 133 take chip-wide kernels with a single workspace (sdp_large.hip)
-        if (probs[0].cone_type[c0] == CIP_CONE_S && probs[0].cone_dim[c0] >= CIP_LARGE_S_MIN * (CIP_LARGE_S_MIN + 1) / 2) {
-            cip_set_error("lock-step batch: S cones of order >= %d are not supported", CIP_LARGE_S_MIN);
-            return CIP_E_UNSUPPORTED;
-        }
+    if (has_chipwide_s_cone(probs[0])) return refuse_chipwide_s_cone();
     if (cip_tl_builder) { cip_set_error("lock-step batch inside a graph recording"); return CIP_E_INVALID; }
     if (!g_stats_accumulate) for (int &q : g_last_stats) q = 0;
     auto range = [&](int i0, int i1) -> int {                // groups of up to 64 over [i0, i1), one after the other, on the calling thread
@@ -465,20 +455,12 @@ extern "C" int cip_conicip_lockstep(int count, const cip_problem *probs, const d
 extern "C" int cip_conicip_mixed(int count, const cip_problem *probs, const double *const *c, const double *const *b,
                                  const double *const *d, const cip_options *opt, double *const *y, double *const *w,
                                  double *const *v, cip_result *res, int in_flight) {
-    if (count < 0 || (count > 0 && (!probs || !c || !y || !res))) { cip_set_error("cip_conicip_mixed: null argument"); return CIP_E_INVALID; }
+    const BatchCall call = {count, probs, nullptr, c, b, d, opt, y, w, v, res};
+    CIP_TRY(check_batch_call("cip_conicip_mixed", call, CHECK_EVERY));
     if (count == 0) return 0;
-    auto lockstep_ok = [](const cip_problem &q) {
-        for (int c0 = 0; c0 < q.ncones; ++c0)
-            if (q.cone_type[c0] == CIP_CONE_S && q.cone_dim[c0] >= CIP_LARGE_S_MIN * (CIP_LARGE_S_MIN + 1) / 2) return false;
-        return true;
-    };
     const bool ragged = g_ragged.load() != 0;
     std::vector<std::vector<int>> bins;                         // bins[k][0] is the representative
     for (int i = 0; i < count; ++i) {
-        if ((probs[i].m > 0 && (!b || !v || !b[i] || !v[i])) || (probs[i].p > 0 && (!d || !w || !d[i] || !w[i])) || !c[i] || !y[i]) {
-            cip_set_error("cip_conicip_mixed: null vector for problem %d", i);
-            return CIP_E_INVALID;
-        }
         size_t k = 0;
         for (; k < bins.size(); ++k)
             if (same_shape(probs[bins[k][0]], probs[i], ragged)) break;
@@ -489,25 +471,15 @@ extern "C" int cip_conicip_mixed(int count, const cip_problem *probs, const doub
     struct Acc { Acc() { g_stats_accumulate = true; } ~Acc() { g_stats_accumulate = false; } } acc;
     std::vector<int> rest;
     auto run = [&](const std::vector<int> &idx, bool lock) -> int {
-        const size_t k = idx.size();
-        std::vector<cip_problem> gp(k);
-        std::vector<const double *> gc(k), gb(k), gd(k);
-        std::vector<double *> gy(k), gw(k), gv(k);
-        std::vector<cip_result> gr(k);
-        for (size_t j = 0; j < k; ++j) {
-            const int i = idx[j];
-            gp[j] = probs[i]; gc[j] = c[i]; gy[j] = y[i];
-            gb[j] = b ? b[i] : nullptr; gv[j] = v ? v[i] : nullptr;
-            gd[j] = d ? d[i] : nullptr; gw[j] = w ? w[i] : nullptr;
-        }
-        const int rc = lock ? cip_conicip_lockstep((int)k, gp.data(), gc.data(), gb.data(), gd.data(), opt, gy.data(), gw.data(), gv.data(), gr.data())
-                            : cip_conicip_problems((int)k, gp.data(), gc.data(), gb.data(), gd.data(), opt, gy.data(), gw.data(), gv.data(), gr.data(), in_flight);
-        if (rc == 0 || !lock)                                   // the thread pool writes a status for every problem it reached
-            for (size_t j = 0; j < k; ++j) res[idx[j]] = gr[j];
+        SubBatch sub(call, idx);
+        const BatchCall g = sub.view();
+        const int rc = lock ? cip_conicip_lockstep(g.count, g.probs, g.c, g.b, g.d, g.opt, g.y, g.w, g.v, g.res)
+                            : cip_conicip_problems(g.count, g.probs, g.c, g.b, g.d, g.opt, g.y, g.w, g.v, g.res, in_flight);
+        if (rc == 0 || !lock) sub.scatter();                    // the thread pool writes a status for every problem it reached
         return rc;
     };
     for (const auto &bin : bins) {
-        if (bin.size() < 2 || !lockstep_ok(probs[bin[0]])) { rest.insert(rest.end(), bin.begin(), bin.end()); continue; }
+        if (bin.size() < 2 || has_chipwide_s_cone(probs[bin[0]])) { rest.insert(rest.end(), bin.begin(), bin.end()); continue; }
         const int rc = run(bin, true);
         // a bin that turns out not to qualify (same shape, yet a different slab layout: CSR arrays in device memory with differing
         // numbers of non-zeros, or a CSR Q of another mat-vec form -- neither with cip_set_lockstep_ragged(1)) has written nothing: its problems join the thread pool's share instead of failing the batch

@@ -26,9 +26,8 @@
 // k_cone_prod :282-308, k_cone_div :311-340, k_maxstep :345-408) and the element-wise chains of vecops.hip (k_loop_resid, k_loop_corr,
 // k_loop_refine); they are copies for one workgroup per problem, not shared device functions: a shared tile body has changed another
 // kernel's code generation before (k_gemm_nt_16_batched).
-#include "cip_internal.h"
+#include "cip_batch_front.h"
 #include "cip_driver_scalars.h"
-#include "../../include/cipkkt.h"
 #include <math.h>
 #include <algorithm>
 #include <chrono>
@@ -717,9 +716,7 @@ int small_run(int count, const cip_problem *probs, const double *const *c, const
     SmallArgs a = {};
     size_t host_prefix = 0, dev_prefix = 0;
     const size_t slab = small_layout(nullptr, n, m, p, scal_len, &a.S, &host_prefix, &dev_prefix);
-    size_t gran = (slab + 255) / 256;
-    if ((gran & 1) == 0) ++gran;                 // (an odd number of granules: lockstep.hip)
-    const size_t stride = gran * 256, prefix = dev ? dev_prefix : host_prefix;
+    const size_t stride = slab_stride(slab), prefix = dev ? dev_prefix : host_prefix;
     struct Arena { char *slabs; double *dots; int *flags, *nref, *live; SmallCone *cones; SmallSrc *src; };
     auto arena_layout = [&](const void *base, Arena *A) {
         CipLayout L(base);
@@ -800,8 +797,7 @@ int small_run(int count, const cip_problem *probs, const double *const *c, const
     std::vector<char> gone(count, 0);
     for (int z = 0; z < count; ++z) {
         live[z] = z; live_h[z] = z;
-        res[z] = cip_result{};
-        res[z].prFeas = res[z].duFeas = res[z].muFeas = INFINITY; res[z].pobj = INFINITY; res[z].dobj = -INFINITY;
+        res[z] = fresh_result();
     }
     CIP_HIP_CHECK(hipMemcpyAsync(A.live, live_h, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, s));
     auto read_back = [&]() -> int {
@@ -883,46 +879,31 @@ extern "C" int cip_conicip_small(int count, const cip_problem *probs, const doub
                                  double *const *v, cip_result *res) {
     for (int &q : g_small_stats) q = 0;
     g_small_time[0] = g_small_time[1] = 0.0;
-    if (count < 0 || (count > 0 && (!probs || !c || !y || !res))) { cip_set_error("cip_conicip_small: null argument"); return CIP_E_INVALID; }
+    using namespace cipdrv;
+    const char *who = "cip_conicip_small";
+    const BatchCall call = {count, probs, nullptr, c, bvec, d, opt, y, w, v, res};
+    CIP_TRY(check_batch_call(who, call, CHECK_ARRAYS));
     if (count == 0) return 0;
     const auto t_start = std::chrono::steady_clock::now();
-    for (int i = 0; i < count; ++i) CIP_TRY(small_check(&probs[i], "cip_conicip_small"));
-    const cip_problem &q0 = probs[0];
-    for (int i = 1; i < count; ++i) {
-        const cip_problem &q = probs[i];
-        bool same = q.n == q0.n && q.m == q0.m && q.p == q0.p && q.ncones == q0.ncones &&
-                    (q.flags & CIP_FLAG_DEVICE_PTRS) == (q0.flags & CIP_FLAG_DEVICE_PTRS);
-        for (int k = 0; same && k < q0.ncones; ++k) same = q.cone_type[k] == q0.cone_type[k] && q.cone_dim[k] == q0.cone_dim[k];
-        if (!same) { cip_set_error("cip_conicip_small: problem %d differs in shape from problem 0", i); return CIP_E_UNSUPPORTED; }
-    }
-    if ((q0.m > 0 && (!bvec || !v)) || (q0.p > 0 && (!d || !w))) { cip_set_error("cip_conicip_small: null argument"); return CIP_E_INVALID; }
-    for (int i = 0; i < count; ++i)
-        if (!c[i] || !y[i] || (q0.m > 0 && (!bvec[i] || !v[i])) || (q0.p > 0 && (!d[i] || !w[i]))) {
-            cip_set_error("cip_conicip_small: null vector for problem %d", i);
-            return CIP_E_INVALID;
-        }
-    const cip_options o = cipdrv::resolve_options(opt);
+    for (int i = 0; i < count; ++i) CIP_TRY(small_check(&probs[i], who));
+    // (same_dims, not lock-step's same_shape: small_check has pinned the route and the matrix forms; whether an m = 0 problem's A is null does not count)
+    for (int i = 1; i < count; ++i)
+        if (!same_dims(probs[0], probs[i])) { cip_set_error("%s: problem %d differs in shape from problem 0", who, i); return CIP_E_UNSUPPORTED; }
+    CIP_TRY(check_batch_call(who, call, CHECK_PROBLEM0));
+    CIP_TRY(check_batch_call(who, call, CHECK_EVERY));
+    const cip_options o = resolve_options(opt);
     std::vector<int> fallback;
     CIP_TRY(small_run(count, probs, c, bvec, d, o, y, w, v, res, fallback));
     // ---- the problems the kernels could not finish (a bad pivot: LPs, singular Q with free variables): from the start through
     // cip_conicip_mixed, whose results they get bit for bit
     if (!fallback.empty()) {
-        const size_t k = fallback.size();
-        std::vector<cip_problem> gp(k);
-        std::vector<const double *> gc(k), gb(k), gd(k);
-        std::vector<double *> gy(k), gw(k), gv(k);
-        std::vector<cip_result> gr(k);
-        for (size_t j = 0; j < k; ++j) {
-            const int i = fallback[j];
-            gp[j] = probs[i]; gc[j] = c[i]; gy[j] = y[i];
-            gb[j] = bvec ? bvec[i] : nullptr; gv[j] = v ? v[i] : nullptr;
-            gd[j] = d ? d[i] : nullptr; gw[j] = w ? w[i] : nullptr;
-        }
+        SubBatch sub(call, fallback);
+        const BatchCall g = sub.view();
         cip_options quiet;
         if (opt) { quiet = *opt; quiet.verbose = 0; }
-        CIP_TRY(cip_conicip_mixed((int)k, gp.data(), gc.data(), gb.data(), gd.data(), opt ? &quiet : nullptr, gy.data(), gw.data(), gv.data(), gr.data(), 4));
-        for (size_t j = 0; j < k; ++j) res[fallback[j]] = gr[j];
-        g_small_stats[1] = (int)k;
+        CIP_TRY(cip_conicip_mixed(g.count, g.probs, g.c, g.b, g.d, opt ? &quiet : nullptr, g.y, g.w, g.v, g.res, 4));
+        sub.scatter();
+        g_small_stats[1] = g.count;
     }
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     for (int i = 0; i < count; ++i) res[i].wall_s = wall;

@@ -8,6 +8,7 @@
 //      group of ONE -- round 4's NULL write lived there), CSR problems of equal shape but different nnz, problems with p > 0, a
 //      problem with a chip-wide S cone (lock-step refuses it: thread pool), and a batch holding an S cone beyond the envelope
 //      (refused at level 1: the call must fail cleanly and free everything);
+//      and the worker pool alone (cip_batch_conicip, cip_conicip_many, cip_conicip_problems), a failing problem among sound ones included;
 //   4. the same entry points from several caller threads at once (thread-local batch contexts, the cached arena, the pool);
 //   5. the stand-alone LDL' entry points with a caller-owned workspace in both solve modes, and their refusals of bad arguments;
 //   6. the handle's device block: one "device" allocation per handle (two with a chip-wide S cone), lock-step calls of one shape
@@ -228,6 +229,52 @@ static void refused_batch(void) {
     REQUIRE(y3[0] == 777.0);
 }
 
+// ---- the worker pool of batch.hip on three problems of the smallest shape: handles built once (cip_batch_create, cip_batch_conicip,
+// cip_conicip_many) and problems in (cip_conicip_problems), with every problem sound and with the middle one failing -- once with one
+// worker (the failure is the calling thread's) and once with more (it may be another thread's)
+static Batch three_small(int middle_cone_dim = 5) {
+    Batch B;
+    for (int i = 0; i < 3; ++i) B.P.push_back(make(6, 1, {{CIP_CONE_R, 5}, {CIP_CONE_Q, 3}}, 1.0));
+    B.P[1].cdim[0] = middle_cone_dim;                              // (another value: the cone list no longer covers m = 8)
+    B.finish();
+    return B;
+}
+static void poison(Batch &B) { for (auto &r : B.res) memset(&r, 0x5a, sizeof(cip_result)); }
+static bool final_status(const cip_result &r) { return r.status >= CIP_STATUS_OPTIMAL && r.status <= CIP_STATUS_ERROR; }
+static void middle_failed(int rc, const Batch &B) {
+    REQUIRE(rc != CIP_OK);
+    REQUIRE(!strncmp(cip_last_error(), "problem failed:", 15));
+    REQUIRE(B.res[1].status == CIP_STATUS_ERROR);
+    REQUIRE(final_status(B.res[0]) && final_status(B.res[2]));     // reached: no longer the poison
+}
+static void pool_cases(void) {
+    cip_options o = opts();
+    {
+        Batch B = three_small();
+        cip_batch *bt = nullptr;
+        REQUIRE(cip_batch_create(3, B.desc.data(), &bt) == CIP_OK && cip_batch_size(bt) == 3);
+        for (int in_flight : {1, 3}) {
+            poison(B);
+            REQUIRE(cip_batch_conicip(bt, B.c.data(), B.b.data(), B.d.data(), &o, B.yp.data(), B.wp.data(), B.vp.data(), B.res.data(), in_flight) == CIP_OK);
+            for (const auto &r : B.res) REQUIRE(final_status(r));
+        }
+        // a NULL c: refused by cip_conicip, hence a failed problem of cip_conicip_many
+        cip_handle *hs[3] = {cip_batch_handle(bt, 0), cip_batch_handle(bt, 1), cip_batch_handle(bt, 2)};
+        REQUIRE(cip_conicip(hs[1], nullptr, B.b[1], B.d[1], &o, B.yp[1], B.wp[1], B.vp[1], &B.res[1], nullptr, 0) == CIP_E_INVALID);
+        B.c[1] = nullptr;
+        for (int in_flight : {1, 2}) {
+            poison(B);
+            middle_failed(cip_conicip_many(hs, 3, B.c.data(), B.b.data(), B.d.data(), &o, B.yp.data(), B.wp.data(), B.vp.data(), B.res.data(), in_flight), B);
+        }
+        REQUIRE(cip_batch_destroy(bt) == CIP_OK);
+    }
+    Batch B = three_small(4);                                      // level 1 refuses the middle problem
+    for (int in_flight : {1, 2}) {
+        poison(B);
+        middle_failed(cip_conicip_problems(3, B.desc.data(), B.c.data(), B.b.data(), B.d.data(), &o, B.yp.data(), B.wp.data(), B.vp.data(), B.res.data(), in_flight), B);
+    }
+}
+
 static void standalone_ldlt(void) {
     const int N = 384;
     size_t bytes = 0;
@@ -388,6 +435,7 @@ int main(int argc, char **argv) {
     standalone_ldlt();
     run_mixed(65, true, 3);
     run_mixed(1, false, 1);
+    pool_cases();
     refused_batch();
     // concurrent callers: every thread its own batches, all through the same process-wide state
     std::vector<std::thread> th;

@@ -113,6 +113,13 @@ static void refusals() {
     // the edges that are taken
     { Batch B(1, 100, 1024, 28); REQUIRE(cip_conicip_small_fits(&B.pr[0]) == CIP_OK); }
     { Batch B(1, 128, 0, 0); REQUIRE(cip_conicip_small_fits(&B.pr[0]) == CIP_OK); }
+    // without rows A is never read: whether its pointer is NULL is no part of the shape (lock-step's rule, which refuses such a pair, is another)
+    {
+        Batch B(2, 3, 0, 1);
+        B.pr[1].A = B.A.data();
+        REQUIRE(B.pr[0].A == nullptr && B.run() == CIP_OK);
+        for (int i = 0; i < 2; ++i) REQUIRE(B.res[i].status == CIP_STATUS_OPTIMAL && B.res[i].iter == 1);
+    }
 }
 
 static void runs(int count, int n, int m, int p, bool device) {
